@@ -1,11 +1,18 @@
 #!/usr/bin/env python
 """bench.py — BASELINE.json's metric on MI355X: training patches/s (fwd + Dice_spvPA + bwd + Adam) on synthetic
-384x128x128 bf16 patches, batch 4 per GPU, plus sliding-window volumes/s (512x512x120, roi 384x128x128, overlap 0.5).
+384x128x128 bf16 patches, batch 4 per GPU; with --full also sliding-window volumes/s (512x512x120, roi 384x128x128, overlap 0.5).
 
-    python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]   (N>1: launched by torch.distributed.run, one rank per GPU)
 
-Prints ONE JSON line on rank 0 (contract in the task description): whole-job patches/s, the roofline of the dominant
-kernel (HIP-event timed inside the timed region) and, at N=1, the CPU baseline (oracle on the host cores, bounded sample).
+Prints ONE JSON line on rank 0: whole-job patches/s and ms_per_step of the K timed training steps.  A plain run does only that: set-up,
+warm-up, the timed steps, the outputs (--dump-outputs) and the line.  --full adds everything else the benchmark measures or checks: the
+parity check against the reference golden, the per-kernel HIP-event breakdown and the roofline of the dominant kernel (HIP-event timed
+inside the timed region), the fp32 parity mode, sliding-window and sharded-case throughput, the data side and, at N=1, the CPU baseline
+(oracle on the host cores, bounded sample).
+
+--dump-outputs DIR writes what the last timed step computed, as rank 0 holds it afterwards (float32 .npy files): loss.npy, the fp32
+parameters after its Adam update (parameters.npy), the summed gradient Adam consumed (gradients.npy) and the BatchNorm running statistics
+(running_stats.npy), each in state_dict order.  Inputs, weights and dropout masks are seeded, so equal arguments give equal inputs.
 """
 from __future__ import annotations
 
@@ -24,7 +31,7 @@ sys.path.insert(0, ROOT)
 PATCH = (384, 128, 128)
 HP = dict(channels=(16, 32, 48, 64, 80, 96), strides=((2, 2, 1), (2, 2, 1), (2, 2, 2), (2, 2, 2), (2, 2, 2)), kernel_sizes=((3, 3, 1), (3, 3, 1), (3, 3, 3), (3, 3, 3), (3, 3, 3), (3, 3, 3)),
           sample_kernel_sizes=((3, 3, 1), (3, 3, 1), (3, 3, 3), (3, 3, 3), (3, 3, 3)))
-PEAK = {"bf16": 2500.0, "fp32": 157.3}  # dense TFLOP/s, /opt/skills/guides/MI355X_MICROARCH.md
+PEAK = {"bf16": 2500.0, "fp32": 157.3}  # dense TFLOP/s of the MI355X (CDNA4 microarchitecture guide)
 FWD_BWD_GFLOP_PER_PATCH = 2053.9  # convolutions only, 2 FLOP/MAC
 
 
@@ -76,8 +83,8 @@ def summarize_events(events):
 
 def parity_block(args, dev):
     """Parity of exactly what is timed below (compute dtype, batch, tuned launch plans) against the reference's own golden of one
-    training step at 384x128x128 (tests/golden/net_train_b1_384x128x128.npz, produced by importing /root/reference in the build
-    container): the golden's input is replicated over the batch (tests/parity_check.py explains why that is exact).  Dropout is
+    training step at 384x128x128 (tests/golden/net_train_b1_384x128x128.npz, produced by tests/golden/make_goldens.py from the
+    reference implementation): the golden's input is replicated over the batch (tests/parity_check.py explains why that is exact).  Dropout is
     off for this check (torch's dropout stream cannot be reproduced); it is on in the timed region."""
     import vs_seg_amd as V
     from tests import parity_check as PC
@@ -288,9 +295,9 @@ def sharded_cases(model, n_cases, rank, world, dev, barrier, t2_shape=(448, 448,
 
 
 def self_launch(args):
-    """`python bench.py --gpus N` (N > 1) outside a torchrun environment starts its own N ranks: the process replaces itself by
+    """`python bench.py --gpus N` (N > 1) outside a torchrun environment starts its own N ranks: the process runs
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py <same arguments>`
-    (one rank per GPU over RCCL; rank 0 prints the one JSON line with n_gpus = N).  Fewer than N visible GPUs is an error, not a warning —
+    as a child and exits with its status (one rank per GPU over RCCL; rank 0 prints the one JSON line with n_gpus = N).  Fewer than N visible GPUs is an error, not a warning —
     except with VSSEG_SHARE_DEVICE=1 (+ VSSEG_DIST_BACKEND=gloo), the smoke-test mode in which the ranks share the GPUs that are there."""
     if args.gpus <= 1 or "WORLD_SIZE" in os.environ:
         return
@@ -308,7 +315,54 @@ def self_launch(args):
            os.path.abspath(__file__), *sys.argv[1:]]
     print(f"[bench] --gpus {args.gpus} without a launcher environment: {' '.join(cmd)}", file=sys.stderr, flush=True)
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    import subprocess
+
+    rc = subprocess.call(cmd)  # a fresh child process: this one has touched the HIP runtime (device_count) and must not exec
+    raise SystemExit(rc if rc >= 0 else 128 - rc)
+
+
+def result_line(args, world, dt, loss_val):
+    """The headline fields of the JSON line, the same with and without --full."""
+    patches_per_s = args.steps * args.batch * world / dt
+    return {
+        "metric": "train_patches_per_sec_fwd_bwd_384x128x128",
+        "value": patches_per_s,
+        "unit": "patches/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * dt / args.steps,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": args.dtype,
+        "data": "synthetic",
+        "config": {"workload": f"BASELINE config 2: 2.5D attention-UNet fwd + Dice_spvPA(attention+hardness) + bwd + Adam on random 384x128x128 patches, batch {args.batch} per GPU, dropout {args.dropout:g}, random-init weights",
+                   "global_batch": args.batch * world, "patch": "384x128x128", "parallelism": f"dp{world}"},
+        "conv_stack_mfma_frac": FWD_BWD_GFLOP_PER_PATCH * patches_per_s / world / 1e3 / PEAK[args.dtype],
+        "loss": loss_val,
+        "full": bool(args.full),
+        "bench_phases_s": _PHASES,
+    }
+
+
+DUMP_MAX_ELEMS = 1 << 22  # per array (16 MB of float32): 3 arrays + the loss stay under 64 MB
+
+
+def dump_outputs(out_dir, model, loss):
+    """What the last timed step computed, as float32 .npy files under out_dir: the loss, the parameters after its Adam update, the gradient
+    Adam consumed and the BatchNorm running statistics (state_dict order).  An array longer than DUMP_MAX_ELEMS is written as a fixed,
+    seeded sample of its elements (the same indices on every run with the same arguments)."""
+    torch.cuda.synchronize()
+    flat, gflat = model.flat_parameters()
+    stats = [v.detach().reshape(-1).float() for k, v in model.state_dict().items() if "running" in k]
+    arrays = {"loss": loss.detach().reshape(1).float(), "parameters": flat.detach(), "gradients": gflat.detach(), "running_stats": torch.cat(stats) if stats else torch.zeros(0)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.float().cpu().numpy().astype(np.float32, copy=False)
+        if a.size > DUMP_MAX_ELEMS:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def main():
@@ -326,8 +380,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the parity check of the benchmarked configuration against the reference golden")
     ap.add_argument("--no-c3-parity", action="store_true", help="skip the BASELINE config 3 part of the parity block (sliding window at 512x512x120 + hard Dice against its fixture)")
-    ap.add_argument("--profile", action="store_true", help="print the per-kernel HIP-event breakdown of one step to stderr")
+    ap.add_argument("--profile", action="store_true", help="print the per-kernel HIP-event breakdown of one step to stderr (with --full)")
+    ap.add_argument("--full", action="store_true", help="also run everything beside the headline: parity check, per-kernel and roofline figures, fp32 mode, sliding window, "
+                    "sharded cases, data side, CPU baseline (the --no-* / --swi-* / --fp32-steps options select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     self_launch(args)
 
     import torch.distributed as dist
@@ -343,7 +402,7 @@ def main():
 
     phase("imports + process group done")
     parity = None
-    if rank == 0 and not args.no_parity and args.batch >= 1:
+    if args.full and rank == 0 and not args.no_parity and args.batch >= 1:
         parity = parity_block(args, dev)  # before the timed region, same launch-plan signatures (dtype, batch) as the timed steps
         phase("parity check against the reference golden done")
     model = build_model(args.dtype, dev, dropout=args.dropout)
@@ -360,6 +419,23 @@ def main():
 
     for _ in range(max(1, args.warmup)):
         trainer.step(img, lab)
+    if not args.full:
+        # the step that --full event-times, here without events: the timed steps start from the same trained state either way
+        trainer.step(img, lab)
+        barrier()
+        phase("warm-up done")
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            loss = trainer.step(img, lab)
+        barrier()
+        dt = DP.allreduce_max_float(time.perf_counter() - t0, dev)
+        phase(f"timed region done ({dt:.2f} s)")
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, model, loss)
+            phase("outputs written")
+        if rank == 0:
+            print(json.dumps(result_line(args, world, dt, float(loss))))
+        return
     plan = next(p for k, p in model._engine.plans.items() if k[2])
     # one fully event-timed step: finds the dominant kernel (not part of the timed region)
     plan.timer = dict(only=None, events=[])
@@ -400,8 +476,10 @@ def main():
     dom = summarize_events(plan.timer["events"])[dominant]
     plan.timer = None
     phase(f"timed region done ({dt:.2f} s)")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss)
+        phase("outputs written")
     loss_val = float(loss)
-    patches_per_s = args.steps * args.batch * world / dt
 
     # ---- the same step in the fp32 parity mode (exact-fp32 MFMA: logits within 1e-3 of the reference, tests/test_gpu_network.py), not the headline
     fp32 = None
@@ -524,24 +602,9 @@ def main():
             roof["traffic"] = (traffic.get(dominant) or {}).get("hbm_bytes_per_launch")  # PMC FETCH_SIZE(x2)+WRITE_SIZE, see profiles/
         except Exception:
             pass
-    res = {
-        "metric": "train_patches_per_sec_fwd_bwd_384x128x128",
-        "value": patches_per_s,
-        "unit": "patches/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": 1e3 * dt / args.steps,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": args.dtype,
-        "data": "synthetic",
-        "config": {"workload": f"BASELINE config 2: 2.5D attention-UNet fwd + Dice_spvPA(attention+hardness) + bwd + Adam on random 384x128x128 patches, batch {args.batch} per GPU, dropout {args.dropout:g}, random-init weights",
-                   "global_batch": args.batch * world, "patch": "384x128x128", "parallelism": f"dp{world}"},
-        "conv_stack_mfma_frac": FWD_BWD_GFLOP_PER_PATCH * patches_per_s / world / 1e3 / peak,
-        **{k: round(v, 4) if isinstance(v, float) else v for k, v in fractions.items()},
-        "loss": loss_val,
+    res = result_line(args, world, dt, loss_val)
+    res.update({k: round(v, 4) if isinstance(v, float) else v for k, v in fractions.items()})
+    res.update({
         "roofline": roof,
         "roofline_table": roofline_table(full, peak, traffic),
         "parity": parity,
@@ -549,7 +612,7 @@ def main():
         "sliding_window": swi,
         "sharded_cases": c5,
         "data_side": data_side,
-    }
+    })
     phase("sliding window / sharded cases / data side done")
     if world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline()

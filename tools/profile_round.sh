@@ -7,7 +7,7 @@ TRAIN="--swi-volumes 0 --swi-cases 0 --fp32-steps 0 --no-cpu-baseline --no-parit
 rocprofv3 --pmc FETCH_SIZE -d $OUT/fetch -- python $R/bench.py --steps 2 --warmup 1 $TRAIN > $OUT/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE -d $OUT/write -- python $R/bench.py --steps 2 --warmup 1 $TRAIN > $OUT/write.log 2>&1
 (cd $R && python tools/rocprof_summary.py pmc $OUT/fetch/*/*.db $OUT/write/*/*.db $OUT/roofline_traffic.json > $OUT/pmc_hbm.txt && cp $OUT/roofline_traffic.json profiles/roofline_traffic.json)
-python $R/bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+python $R/bench.py --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err
 # kernel trace of the training steps with ONE stream and eager launches (VSSEG_OVERLAP=0 VSSEG_GRAPHS=0): no kernel shares the GPU with a concurrent weight gradient,
 # so the per-kernel durations of kernel_stats.txt are clean (the product's default schedule — two streams, hipGraph replay — is what bench.json times)
 VSSEG_OVERLAP=0 VSSEG_GRAPHS=0 rocprofv3 --kernel-trace --stats -d $OUT/kt -- python $R/bench.py --steps 5 --warmup 2 $TRAIN > $OUT/kt.log 2>&1
@@ -35,7 +35,7 @@ open(out + "/bench.json", "w").write(json.dumps(d) + "\n")
 PYEOF
 rm -rf $OUT/ktd
 # BASELINE config 5 at its full case count, once per round (the default bench line carries 8 cases)
-python bench.py --steps 2 --warmup 1 --swi-volumes 0 --fp32-steps 0 --no-cpu-baseline --no-parity --swi-cases 242 2> /dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(json.dumps(d['sharded_cases']))" > $OUT/sharded_242.json
+python bench.py --steps 2 --warmup 1 --full --swi-volumes 0 --fp32-steps 0 --no-cpu-baseline --no-parity --swi-cases 242 2> /dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(json.dumps(d['sharded_cases']))" > $OUT/sharded_242.json
 # what a dependent stage boundary costs (launch / hipGraph node / in-kernel grid barrier) and the deep-level kernel against the other plans, launch by launch
 (tools/probes/chain_probe > $OUT/chain_probe.txt 2>&1 || true)
 (tools/probes/fork_probe > $OUT/fork_probe.txt 2>&1 || true)  # what a fork of the side stream costs the main one: event record against an event bound to the kernel
