@@ -2,6 +2,8 @@
 """Sliding-window inference on the test set — the reference's VS_inference.py (ref:VS_inference.py) on the MI355X hot path.
 
     python VS_inference.py --results_folder_name run1 [--dataset T2] [--no_attention] [--debug]
+
+`--surface_metrics` also reports HD95 and ASSD (mm) per test case, computed on the GPU, and writes figures/test_surface_metrics.csv.
 """
 import argparse
 import random

@@ -224,7 +224,7 @@ int vsseg_fork_event_destroy(void* ev);
 int vsseg_fork_arm(void* ev);
 int vsseg_fork_disarm(void);
 int vsseg_stream_wait_event(void* stream, void* ev);
-int vsseg_version(void); /* 7: + vsseg_dice_pred_bwd_to, vsseg_dice_level_sums, vsseg_dice_tail_sums, vsseg_dice_att_bwd_levels, vsseg_fork_*, vsseg_stream_wait_event; 6: + launch plans with depth -8 (transition kernel) and -9 (gathering marching kernel); 5: vsseg_wgrad march = 2 (compute weight-gradient kernel), + vsseg_conv_to1, vsseg_conv_chain_desc without h_out (the training variant measured no gain and was deleted); 4: + vsseg_conv_chain; 3: the BatchNorm-block-on-load fields (in_bn_*, keep_*, x_bn_*: round-4 experiment, measured a loss, deleted) left the descriptors, depth -7 plans;
+int vsseg_version(void); /* 8: + vsseg_surface_distances, vsseg_surface_scratch_bytes; 7: + vsseg_dice_pred_bwd_to, vsseg_dice_level_sums, vsseg_dice_tail_sums, vsseg_dice_att_bwd_levels, vsseg_fork_*, vsseg_stream_wait_event; 6: + launch plans with depth -8 (transition kernel) and -9 (gathering marching kernel); 5: vsseg_wgrad march = 2 (compute weight-gradient kernel), + vsseg_conv_to1, vsseg_conv_chain_desc without h_out (the training variant measured no gain and was deleted); 4: + vsseg_conv_chain; 3: the BatchNorm-block-on-load fields (in_bn_*, keep_*, x_bn_*: round-4 experiment, measured a loss, deleted) left the descriptors, depth -7 plans;
                             * 2: fixed-point accumulators documented + vsseg_fx_status; 1: the buffers below were described as plain doubles */
 
 /* ---- Accumulator buffers are 64-bit FIXED-POINT integers, not doubles ------------------------------------------------------------------
@@ -408,6 +408,17 @@ int vsseg_swi_finalize(const float* out, const float* cnt, const int32_t pdims[3
 /* hard Dice of argmax vs label (ref:params/VSparams.py:393-408): counts[0]=|P∩G|, [1]=|P|, [2]=|G| */
 int vsseg_hard_dice_counts(const float* logits, int32_t pitch, const float* label, int64_t nvox, double* counts, void* stream);
 int vsseg_argmax2(const float* logits, int32_t pitch, int64_t nvox, uint8_t* dst, void* stream);
+
+/* Surface distances of the argmax prediction P (ties -> class 0, as vsseg_argmax2) against the label G = ((int)label == 1), as vsseg_hard_dice_counts reads them
+   (ABI version 8): edges E(M) = M AND NOT erode(M) with the 6-connected cross, voxels outside the volume background; d(P->G) = for every voxel of E(P) the Euclidean
+   distance in mm (voxel extents `spacing`) to the nearest voxel of E(G), d(G->P) the same the other way round.  out[0] = hd = max of the two directions' `percentile`
+   (numpy.percentile, linear interpolation; 100 = the maximum), out[1] = assd = (sum d(P->G) + sum d(G->P)) / (|E(P)| + |E(G)|); both masks empty: NaN, one empty: +inf.
+   One volume [X][Y][Z] per call: logits [X][Y][Z][2] fp32 (pitch 2, 8-byte aligned), label [X][Y][Z] fp32, out 2 fp32 in device memory.  A sequence of launches on
+   `stream` without host synchronisation: the counts stay on the device.  Bit-identical from call to call.  scratch: device memory of vsseg_surface_scratch_bytes(dims)
+   bytes, 256-byte aligned, overwritten (a call on another stream needs its own).  dims: 1 .. 8192 on every axis. */
+int64_t vsseg_surface_scratch_bytes(const int32_t dims[3]); /* bytes of scratch, or VSSEG_EINVAL */
+int vsseg_surface_distances(const float* logits, int32_t pitch, const float* label, const int32_t dims[3], const float spacing[3] /* mm per voxel along x, y, z */,
+                            double percentile /* 0 .. 100 */, void* scratch, int64_t scratch_bytes, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -204,6 +204,7 @@ SYMBOLS = [
     "vsseg_dropout_mask", "vsseg_att_apply_fwd", "vsseg_att_apply_bwd", "vsseg_channel_sum", "vsseg_add_inplace", "vsseg_copy_cast",
     "vsseg_maxpool_label", "vsseg_dice_pred_sums", "vsseg_dice_att_sums", "vsseg_dice_finalize", "vsseg_dice_pred_bwd", "vsseg_dice_pred_bwd_to", "vsseg_dice_att_bwd", "vsseg_dice_level_sums", "vsseg_dice_tail_sums", "vsseg_dice_att_bwd_levels", "vsseg_fork_event_create", "vsseg_fork_event_destroy", "vsseg_fork_arm", "vsseg_fork_disarm", "vsseg_stream_wait_event",
     "vsseg_adam", "vsseg_swi_accumulate", "vsseg_swi_finalize", "vsseg_hard_dice_counts", "vsseg_argmax2",
+    "vsseg_surface_scratch_bytes", "vsseg_surface_distances",
 ]  # fmt: skip
 
 _lib = None
@@ -274,6 +275,8 @@ def lib():
         L.vsseg_swi_finalize.argtypes = [vp, vp, I3, I3, I3, i32, vp, vp]
         L.vsseg_hard_dice_counts.argtypes = [vp, i32, vp, i64, vp, vp]
         L.vsseg_argmax2.argtypes = [vp, i32, i64, vp, vp]
+        L.vsseg_surface_scratch_bytes.argtypes, L.vsseg_surface_scratch_bytes.restype = [I3], i64
+        L.vsseg_surface_distances.argtypes = [vp, i32, vp, I3, C.POINTER(C.c_float), f64, vp, i64, vp, vp]
         _lib = L
     return _lib
 

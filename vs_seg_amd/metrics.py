@@ -1,0 +1,90 @@
+"""Surface-distance metrics next to `compute_dice_score`: the 95th-percentile Hausdorff distance and the average symmetric surface distance
+of the argmax segmentation against the label, computed on the device (`vsseg_surface_distances`, csrc/surface.hip).
+
+Conventions (those of MONAI's `compute_hausdorff_distance(directed=False)` / `compute_average_surface_distance(symmetric=True)`): the
+prediction mask is the argmax over the two class channels (ties -> class 0), the label mask `(int)label == 1`, as `compute_dice_score` reads
+them; distances run from edge voxels (mask AND NOT its 6-connected erosion, outside the volume = background) to the nearest edge voxel of the
+other mask, in mm.  Both masks empty: NaN; one empty: +inf.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .inferers import _as_cl
+
+_SCRATCH_CACHE: Dict[tuple, torch.Tensor] = {}  # (device, dims, stream) -> scratch of vsseg_surface_distances
+
+
+def voxel_spacing(affine) -> Tuple[float, float, float]:
+    """Voxel extents in mm: the column norms of the 3x3 block of a 4x4 affine (e.g. the RAS affine `load_case` keeps as label_meta["affine"])."""
+    a = np.asarray(affine, dtype=np.float64)
+    if a.shape != (4, 4):
+        raise ValueError(f"expected a 4x4 affine, got shape {a.shape}")
+    return tuple(float(v) for v in np.linalg.norm(a[:3, :3], axis=0))
+
+
+def _scratch(device, dims, stream) -> torch.Tensor:
+    key = (str(device), tuple(dims), stream)
+    buf = _SCRATCH_CACHE.get(key)
+    if buf is None:
+        nbytes = int(L.lib().vsseg_surface_scratch_bytes(L.i3(dims)))
+        if nbytes < 0:
+            L.check(nbytes, "surface_scratch_bytes")
+        while len(_SCRATCH_CACHE) >= 4:
+            _SCRATCH_CACHE.pop(next(iter(_SCRATCH_CACHE)))
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=device)  # (the caching allocator's blocks are 512-byte aligned)
+        _SCRATCH_CACHE[key] = buf
+    return buf
+
+
+def compute_surface_distances(predicted_probabilities: torch.Tensor, label: torch.Tensor, spacing: Optional[Sequence[float]] = None,
+                              percentile: Optional[float] = 95.0) -> torch.Tensor:
+    """[B,2] fp32 on the device: column 0 the Hausdorff distance at `percentile` (None: the maximum), column 1 the average symmetric surface
+    distance, in mm for voxel extents `spacing` (x, y, z; None: voxel units).  `predicted_probabilities` [B,2,X,Y,Z] logits or probabilities in
+    any layout (as `compute_dice_score` takes them), `label` [B,1,X,Y,Z].  No host synchronisation."""
+    if percentile is None:
+        percentile = 100.0  # numpy.percentile at 100 is the maximum
+    try:
+        percentile = float(percentile)
+    except (TypeError, ValueError):
+        raise ValueError(f"percentile must be a number in [0, 100] or None, got {percentile!r}") from None
+    if not 0.0 <= percentile <= 100.0:
+        raise ValueError(f"percentile must be in [0, 100], got {percentile}")
+    if spacing is None:
+        spacing = (1.0, 1.0, 1.0)
+    try:
+        spacing = tuple(float(s) for s in spacing)
+    except (TypeError, ValueError):
+        raise ValueError(f"spacing must be three positive numbers (mm) or None, got {spacing!r}") from None
+    if len(spacing) != 3 or not all(math.isfinite(s) and s > 0 for s in spacing):
+        raise ValueError(f"spacing must be three positive finite numbers (mm) or None, got {spacing!r}")
+    if predicted_probabilities.dim() != 5 or predicted_probabilities.shape[1] != 2:
+        raise ValueError(f"expected predicted_probabilities [B,2,X,Y,Z], got {tuple(predicted_probabilities.shape)}")
+    B, _, X, Y, Z = predicted_probabilities.shape
+    if tuple(label.shape) != (B, 1, X, Y, Z):
+        raise ValueError(f"expected label [B,1,X,Y,Z] = {(B, 1, X, Y, Z)}, got {tuple(label.shape)}")
+    if not (predicted_probabilities.is_cuda and label.is_cuda):
+        raise RuntimeError("vs_seg_amd.compute_surface_distances runs on an MI355X only; there is no CPU fallback")
+    if label.device != predicted_probabilities.device:
+        raise ValueError(f"predicted_probabilities on {predicted_probabilities.device}, label on {label.device}")
+    lib = L.lib()
+    stream = torch.cuda.current_stream(predicted_probabilities.device).cuda_stream
+    lg = _as_cl(predicted_probabilities)  # [B,X,Y,Z,2] fp32: a view of the sliding window's channels-last output, no copy
+    lab = label.detach()
+    if lab.dtype != torch.float32 or not lab.is_contiguous():
+        lab = lab.to(torch.float32).contiguous()
+    dims = (int(X), int(Y), int(Z))
+    nv = dims[0] * dims[1] * dims[2]
+    scratch = _scratch(lg.device, dims, stream)
+    sp = (ctypes.c_float * 3)(*spacing)
+    out = torch.empty((B, 2), dtype=torch.float32, device=lg.device)
+    for b in range(B):
+        L.check(lib.vsseg_surface_distances(lg.data_ptr() + 8 * b * nv, 2, lab.data_ptr() + 4 * b * nv, L.i3(dims), sp, percentile, scratch.data_ptr(), scratch.numel(),
+                                            out.data_ptr() + 8 * b, stream), "surface_distances")
+    return out

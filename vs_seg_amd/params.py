@@ -28,6 +28,7 @@ import torch
 
 from . import Adam, Dice_spvPA, UNet2d5_spvPA, compute_dice_score, sliding_window_inference
 from .inferers import argmax_segmentation
+from .metrics import compute_surface_distances, voxel_spacing
 from . import parallel as DP
 from .data import nifti
 from .data.transforms import PatchSampler, epoch_batches, load_case
@@ -90,6 +91,7 @@ class VSparams:
         parser.add_argument("--data_root", type=str, default="./data/VS_defaced/", help="data set root (the reference hard-codes this path)")
         parser.add_argument("--compute_dtype", type=str, default="bf16", choices=["bf16", "fp32"], help="bf16 MFMA (benchmark) or exact-fp32 MFMA (parity)")
         parser.add_argument("--num_epochs", type=int, default=None)
+        parser.add_argument("--surface_metrics", action="store_true", help="run_inference also reports HD95 and ASSD per test case (mm, on the GPU) and writes figures/test_surface_metrics.csv")
         args = parser.parse_args(argv)
 
         self.debug, self.dataset, self.data_root = args.debug, args.dataset, args.data_root
@@ -110,6 +112,7 @@ class VSparams:
         self.attention, self.hardness = args.attention, args.hardness
         self.export_inferred_segmentations = True
         self.compute_dtype = args.compute_dtype
+        self.surface_metrics = args.surface_metrics
         self.results_folder_path = os.path.join(self.data_root, "results", "debug" if self.debug else args.results_folder_name)
         self.logs_path = os.path.join(self.results_folder_path, "logs")
         self.model_path = os.path.join(self.results_folder_path, "model")
@@ -143,7 +146,7 @@ class VSparams:
         log("Parameters: ")
         for k in ("dataset", "data_root", "split_csv", "pad_crop_shape", "pad_crop_shape_test", "num_workers", "torch_device_arg", "train_batch_size", "initial_learning_rate",
                   "epochs_with_const_lr", "lr_divisor", "weight_decay", "num_epochs", "val_interval", "model", "sliding_window_inferer_roi_size", "attention", "hardness",
-                  "results_folder_path", "export_inferred_segmentations", "compute_dtype"):
+                  "results_folder_path", "export_inferred_segmentations", "compute_dtype") + (("surface_metrics",) if self.surface_metrics else ()):
             log("{:<34s} {}".format(k + " =", getattr(self, k)))
         log("-" * 10)
 
@@ -339,6 +342,7 @@ class VSparams:
         model.eval()
         n = len(data_loader)
         dice_dev = torch.zeros(n, dtype=torch.float32, device=self.device)
+        surf_dev = torch.zeros((2, n), dtype=torch.float32, device=self.device) if self.surface_metrics else None  # [hd95, assd] per case, mm
         predictor = model.segmentation_predictor() if hasattr(model, "segmentation_predictor") else (lambda *a, **k: model(*a, **k)[0])  # model_segmentation, ref:params/VSparams.py:560
         mine = DP.shard_indices(n)  # the unpadded, unshuffled test loader yields exactly these cases, in this order
         with torch.no_grad():
@@ -348,14 +352,40 @@ class VSparams:
                 outputs = sliding_window_inference(inputs=data["image"], roi_size=self.sliding_window_inferer_roi_size, sw_batch_size=1, predictor=predictor, mode="gaussian")
                 gi = mine[i]
                 dice_dev[gi] = self.compute_dice_score(outputs, data["label"]).reshape(())
+                if surf_dev is not None:
+                    surf_dev[:, gi] = compute_surface_distances(outputs, data["label"], voxel_spacing(data["label_meta_dict"]["affine"]), 95.0)[0]
                 if self.export_inferred_segmentations:
                     self.export_segmentation(outputs, data["label_meta_dict"])
-        dice_scores = DP.allreduce_sum(dice_dev).double().cpu().numpy() if self.world > 1 else dice_dev.double().cpu().numpy()
+        if surf_dev is not None:
+            both = torch.cat([dice_dev[None], surf_dev])  # one all-reduce; a case that is not this rank's is 0 here (NaN / inf + 0 stay NaN / inf)
+            both = (DP.allreduce_sum(both) if self.world > 1 else both).double().cpu().numpy()
+            dice_scores, surf = both[0], both[1:]
+        else:
+            dice_scores = DP.allreduce_sum(dice_dev).double().cpu().numpy() if self.world > 1 else dice_dev.double().cpu().numpy()
         for i, v in enumerate(dice_scores):
             logger.info(f"dice_score[{i}] = {v}")
         logger.info(f"all_dice_scores = {dice_scores}")
         logger.info(f"mean_dice_score = {dice_scores.mean()} +- {dice_scores.std()}")
+        if surf_dev is not None:
+            self._log_surface_metrics(dice_scores, surf[0], surf[1])
         return dice_scores
+
+    def _log_surface_metrics(self, dice, hd95, assd):
+        """Per-case HD95 / ASSD lines, their mean +- std over the finite cases, and figures/test_surface_metrics.csv (rank 0)."""
+        log = self.logger.info
+        for i, (h, a) in enumerate(zip(hd95, assd)):
+            log(f"hd95_mm[{i}] = {h}")
+            log(f"assd_mm[{i}] = {a}")
+        for name, v in (("mean_hd95_mm", hd95), ("mean_assd_mm", assd)):
+            fin = v[np.isfinite(v)]
+            m, sd = (fin.mean(), fin.std()) if len(fin) else (float("nan"), float("nan"))
+            log(f"{name} = {m} +- {sd} ({len(v) - len(fin)} of {len(v)} cases non-finite)")
+        if self.rank == 0:
+            os.makedirs(self.figures_path, exist_ok=True)
+            with open(os.path.join(self.figures_path, "test_surface_metrics.csv"), "w") as f:
+                f.write("case,dice,hd95_mm,assd_mm\n")
+                for i, (d, h, a) in enumerate(zip(dice, hd95, assd)):
+                    f.write(f"{i},{float(d)!r},{float(h)!r},{float(a)!r}\n")
 
     def export_segmentation(self, outputs, label_meta):
         """N3: argmax → uint8 NIfTI in the label's original orientation / affine, under
