@@ -4,6 +4,8 @@
     python VS_inference.py --results_folder_name run1 [--dataset T2] [--no_attention] [--debug]
 
 `--surface_metrics` also reports HD95 and ASSD (mm) per test case, computed on the GPU, and writes figures/test_surface_metrics.csv.
+`--keep_largest_component [--component_connectivity 26]` keeps only the largest connected component of each predicted segmentation (on the GPU) before
+the Dice, the surface metrics and the NIfTI export; the raw Dice and the component counts go to the log and figures/test_postprocessing.csv.
 """
 import argparse
 import random

@@ -224,7 +224,7 @@ int vsseg_fork_event_destroy(void* ev);
 int vsseg_fork_arm(void* ev);
 int vsseg_fork_disarm(void);
 int vsseg_stream_wait_event(void* stream, void* ev);
-int vsseg_version(void); /* 8: + vsseg_surface_distances, vsseg_surface_scratch_bytes; 7: + vsseg_dice_pred_bwd_to, vsseg_dice_level_sums, vsseg_dice_tail_sums, vsseg_dice_att_bwd_levels, vsseg_fork_*, vsseg_stream_wait_event; 6: + launch plans with depth -8 (transition kernel) and -9 (gathering marching kernel); 5: vsseg_wgrad march = 2 (compute weight-gradient kernel), + vsseg_conv_to1, vsseg_conv_chain_desc without h_out (the training variant measured no gain and was deleted); 4: + vsseg_conv_chain; 3: the BatchNorm-block-on-load fields (in_bn_*, keep_*, x_bn_*: round-4 experiment, measured a loss, deleted) left the descriptors, depth -7 plans;
+int vsseg_version(void); /* 9: + vsseg_components_scratch_bytes, vsseg_components_label, vsseg_keep_largest_component; 8: + vsseg_surface_distances, vsseg_surface_scratch_bytes; 7: + vsseg_dice_pred_bwd_to, vsseg_dice_level_sums, vsseg_dice_tail_sums, vsseg_dice_att_bwd_levels, vsseg_fork_*, vsseg_stream_wait_event; 6: + launch plans with depth -8 (transition kernel) and -9 (gathering marching kernel); 5: vsseg_wgrad march = 2 (compute weight-gradient kernel), + vsseg_conv_to1, vsseg_conv_chain_desc without h_out (the training variant measured no gain and was deleted); 4: + vsseg_conv_chain; 3: the BatchNorm-block-on-load fields (in_bn_*, keep_*, x_bn_*: round-4 experiment, measured a loss, deleted) left the descriptors, depth -7 plans;
                             * 2: fixed-point accumulators documented + vsseg_fx_status; 1: the buffers below were described as plain doubles */
 
 /* ---- Accumulator buffers are 64-bit FIXED-POINT integers, not doubles ------------------------------------------------------------------
@@ -419,6 +419,26 @@ int vsseg_argmax2(const float* logits, int32_t pitch, int64_t nvox, uint8_t* dst
 int64_t vsseg_surface_scratch_bytes(const int32_t dims[3]); /* bytes of scratch, or VSSEG_EINVAL */
 int vsseg_surface_distances(const float* logits, int32_t pitch, const float* label, const int32_t dims[3], const float spacing[3] /* mm per voxel along x, y, z */,
                             double percentile /* 0 .. 100 */, void* scratch, int64_t scratch_bytes, float* out, void* stream);
+
+/* Connected components of the foreground of a two-class prediction and the prediction filtered to the largest of them (ABI version 9; the post-transform that MONAI
+   spells AsDiscrete + KeepLargestConnectedComponent; beyond the reference, which reports and exports the raw argmax).  One volume [X][Y][Z] per call: logits
+   [X][Y][Z][2] fp32 (pitch 2, 8-byte aligned), never written.
+   Foreground P = logits[v][1] > logits[v][0], the rule of vsseg_argmax2 (ties and NaN are background).  connectivity 6, 18 or 26: two foreground voxels are neighbours
+   when their index offset d has every |d_a| <= 1 and |dx| + |dy| + |dz| <= 1, 2 or 3; voxels outside the volume are background.
+   labels: int32 [X][Y][Z], 0 on the background and 1 + the smallest linear index (x * Y + y) * Z + z of its component on a foreground voxel: a function of the mask alone.
+   Largest component: most voxels, ties to the smallest label (the component met first in raster order, as numpy.bincount(...).argmax() picks it); P empty: none.
+   out: fp32 [X][Y][Z][2] (8-byte aligned), channel 1 = 1.0 on the largest component and 0.0 elsewhere, channel 0 = 1 - channel 1: a one-hot "probability" tensor that
+   vsseg_hard_dice_counts, vsseg_argmax2 and vsseg_surface_distances read like any other prediction.
+   stats: four int64 in device memory (8-byte aligned): [0] |P|, [1] number of components, [2] voxels of the largest, [3] its label (0 when P is empty); may be NULL
+   for vsseg_keep_largest_component.
+   A sequence of launches on `stream` without host synchronisation; only integer atomics decide anything, so a call is bit-identical from run to run.  No kernel waits
+   for another workgroup.  scratch: device memory of vsseg_components_scratch_bytes(dims) bytes (8 B per voxel), 256-byte aligned, overwritten (a call on another stream
+   needs its own).  dims: 1 .. 8192 on every axis and X * Y * Z < 2^31 - 1. */
+int64_t vsseg_components_scratch_bytes(const int32_t dims[3]); /* bytes of scratch, or VSSEG_EINVAL */
+int vsseg_components_label(const float* logits, int32_t pitch, const int32_t dims[3], int32_t connectivity, void* scratch, int64_t scratch_bytes, int32_t* labels, int64_t* stats,
+                           void* stream);
+int vsseg_keep_largest_component(const float* logits, int32_t pitch, const int32_t dims[3], int32_t connectivity, void* scratch, int64_t scratch_bytes, float* out,
+                                 int64_t* stats /* may be NULL */, void* stream);
 
 #ifdef __cplusplus
 }

@@ -205,6 +205,7 @@ SYMBOLS = [
     "vsseg_maxpool_label", "vsseg_dice_pred_sums", "vsseg_dice_att_sums", "vsseg_dice_finalize", "vsseg_dice_pred_bwd", "vsseg_dice_pred_bwd_to", "vsseg_dice_att_bwd", "vsseg_dice_level_sums", "vsseg_dice_tail_sums", "vsseg_dice_att_bwd_levels", "vsseg_fork_event_create", "vsseg_fork_event_destroy", "vsseg_fork_arm", "vsseg_fork_disarm", "vsseg_stream_wait_event",
     "vsseg_adam", "vsseg_swi_accumulate", "vsseg_swi_finalize", "vsseg_hard_dice_counts", "vsseg_argmax2",
     "vsseg_surface_scratch_bytes", "vsseg_surface_distances",
+    "vsseg_components_scratch_bytes", "vsseg_components_label", "vsseg_keep_largest_component",
 ]  # fmt: skip
 
 _lib = None
@@ -277,6 +278,9 @@ def lib():
         L.vsseg_argmax2.argtypes = [vp, i32, i64, vp, vp]
         L.vsseg_surface_scratch_bytes.argtypes, L.vsseg_surface_scratch_bytes.restype = [I3], i64
         L.vsseg_surface_distances.argtypes = [vp, i32, vp, I3, C.POINTER(C.c_float), f64, vp, i64, vp, vp]
+        L.vsseg_components_scratch_bytes.argtypes, L.vsseg_components_scratch_bytes.restype = [I3], i64
+        L.vsseg_components_label.argtypes = [vp, i32, I3, i32, vp, i64, vp, vp, vp]
+        L.vsseg_keep_largest_component.argtypes = [vp, i32, I3, i32, vp, i64, vp, vp, vp]
         _lib = L
     return _lib
 

@@ -1,0 +1,409 @@
+// Connected components of the foreground of a two-class prediction, the largest of them, and the prediction filtered to it: one volume per call, as a
+// sequence of launches on the caller's stream (no host synchronisation, no allocation).  Foreground P = logits[v][1] > logits[v][0] (the rule of vsseg_argmax2:
+// ties and NaN are background); connectivity 6 / 18 / 26 = index offsets with every |d_a| <= 1 and |dx| + |dy| + |dz| <= 1 / 2 / 3; outside the volume = background.
+//
+//   init      zero the record in scratch (foreground count, bounding box of P, number of components, the selection key)
+//   local     the only pass that reads the logits: a workgroup owns a tile of CT_X x CT_Y x CT_Z voxels (one wave per z row of 64), keeps the mask as one 64-bit word
+//             per row in LDS, labels the tile in LDS with a lock-free union-find (every z run starts out pointing at its first voxel, so only contacts between
+//             rows are united, one per pair of touching runs) and writes each voxel's parent as a global linear index (-1: background).  A tile-local root is the
+//             smallest index of its tile-local component, so every parent link points to a smaller or equal index from the start.  |P| and the bounding box go
+//             into the record with one set of integer atomics per workgroup that saw foreground.  Reads 8 B and writes 4 B per voxel.
+//   merge     foreground voxels whose forward neighbour (13 of the 26 offsets, so that each pair is met once) lies in another tile unite with it in global
+//             memory: find both roots, atomicMin the larger root's parent to the smaller, continue with the value returned.  Parents only ever decrease, so the
+//             final root of a component is its smallest index whatever the order of the unions.
+//   flatten   parent[v] = root(v); a root zeroes its own size counter (the only counters that are ever read).
+//   sizes     voxels per root: a workgroup sums the component of its smallest root in LDS (one atomic per tile for a compact component), the others per wave.
+//   select    every root offers (size << 32) | (0xFFFFFFFF - label) to one 64-bit atomicMax (largest size, then smallest label) and is counted.
+//   write     the whole volume: int32 labels (root + 1), or the one-hot fp32 prediction of the selected component; parents are read inside the box only.
+//             Writes 4 B (labels) or 8 B (one-hot) per voxel.  Block 0 also writes the four statistics.
+//
+// merge .. select run on grids sized for the volume; workgroups whose tile misses the bounding box (which lives in device memory) exit at once.  No kernel waits for
+// another workgroup: every loop either walks parent links towards strictly smaller indices or retries an atomicMin with a strictly smaller operand.  Only integer
+// atomics decide anything, so the result is a function of the mask alone.
+#include <limits.h>
+#include "common.h"
+
+namespace {
+
+constexpr int CT_X = 4, CT_Y = 8, CT_Z = 64;  // tile: CT_X * CT_Y rows of one wave each
+constexpr int CT_ROWS = CT_X * CT_Y;          // 32 rows, 8 per wave of the 256-thread workgroup
+constexpr int CC_MAX_EXTENT = 8192;
+
+struct CompRec {
+  unsigned long long fg;    // |P|
+  unsigned long long best;  // max over roots of (size << 32) | (0xFFFFFFFF - label); 0: P is empty
+  unsigned ncomp;           // number of roots
+  int bmin[3], bmax[3];     // bounding box of P; bmax = -1: empty
+};
+
+struct CompLayout {
+  int64_t parent, cnt, total;
+};
+inline int64_t cc_align(int64_t v) { return (v + 255) & ~(int64_t)255; }
+CompLayout cc_layout(int64_t nvox) {
+  CompLayout l;
+  l.parent = cc_align(sizeof(CompRec));
+  l.cnt = l.parent + cc_align(nvox * 4);
+  l.total = l.cnt + cc_align(nvox * 4);
+  return l;
+}
+
+// the four forward neighbour rows of a row (with dz = -1, 0, 1 each) and the row itself (dz = +1 only): the 13 offsets that follow (0, 0, 0) in raster order
+__device__ __forceinline__ int cc_dx(int n) { return n >= 2 ? 1 : 0; }      // n = 0 .. 4: (0, 0), (0, 1), (1, -1), (1, 0), (1, 1)
+__device__ __forceinline__ int cc_dy(int n) { return n < 2 ? n : n - 3; }
+
+__device__ __forceinline__ int cc_wave_min(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ int cc_wave_max(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ bool cc_bit(unsigned long long m, int i) { return (m >> i) & 1ull; }
+
+// Union-find over an array of parent links with L[i] <= i (a root has L[i] == i).  LDS: workgroup scope; global memory: agent scope, so that a link another
+// compute unit has just lowered is seen (a stale link would still be a valid ancestor: links only decrease, and the atomicMin below returns the current one).
+template <bool GLOBAL>
+__device__ __forceinline__ int cc_find(const int* L, int i) {
+  for (;;) {
+    const int p = GLOBAL ? __hip_atomic_load(L + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : __hip_atomic_load(L + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (p == i) return i;
+    i = p;  // p < i
+  }
+}
+template <bool GLOBAL>
+__device__ __forceinline__ void cc_union(int* L, int a, int b) {
+  for (;;) {
+    a = cc_find<GLOBAL>(L, a);
+    b = cc_find<GLOBAL>(L, b);
+    if (a == b) return;
+    if (a < b) {
+      const int t = a;
+      a = b;
+      b = t;
+    }
+    const int old = atomicMin(L + a, b);  // a > b
+    if (old == a) return;                 // a was a root and now hangs below b
+    a = old;                              // a had a parent old < a already (which now is min(old, b)): unite that one with b
+  }
+}
+
+__device__ __forceinline__ bool cc_tile_outside_box(const CompRec* __restrict__ rec, int x0, int y0, int z0) {
+  return rec->bmax[0] < x0 || rec->bmin[0] >= x0 + CT_X || rec->bmax[1] < y0 || rec->bmin[1] >= y0 + CT_Y || rec->bmax[2] < z0 || rec->bmin[2] >= z0 + CT_Z;
+}
+
+__global__ __launch_bounds__(256) void cc_init_kernel(CompRec* rec) {
+  if (threadIdx.x == 0) {
+    rec->fg = 0;
+    rec->best = 0;
+    rec->ncomp = 0;
+  }
+  if (threadIdx.x < 3) {
+    rec->bmin[threadIdx.x] = INT_MAX;
+    rec->bmax[threadIdx.x] = -1;
+  }
+}
+
+__global__ __launch_bounds__(256) void cc_local_kernel(const float* __restrict__ logits, int X, int Y, int Z, int conn, int* __restrict__ parent, CompRec* __restrict__ rec) {
+  __shared__ unsigned long long rowmask[CT_ROWS];
+  __shared__ int L[CT_ROWS * CT_Z];
+  const int z0 = blockIdx.x * CT_Z, y0 = blockIdx.y * CT_Y, x0 = blockIdx.z * CT_X;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int z = z0 + lane;
+  float2 lg[CT_ROWS / 4];
+#pragma unroll
+  for (int k = 0; k < CT_ROWS / 4; ++k) {
+    const int r = k * 4 + wave, x = x0 + (r >> 3), y = y0 + (r & 7);
+    lg[k] = make_float2(0.f, 0.f);
+    if (x < X && y < Y && z < Z) lg[k] = *reinterpret_cast<const float2*>(logits + 2 * (((int64_t)x * Y + y) * Z + z));
+  }
+  bool any = false;
+#pragma unroll
+  for (int k = 0; k < CT_ROWS / 4; ++k) {
+    const int r = k * 4 + wave;
+    const bool m = lg[k].y > lg[k].x;
+    const unsigned long long bits = __ballot(m);
+    if (lane == 0) rowmask[r] = bits;
+    const unsigned long long gaps = ~bits & ((1ull << lane) - 1ull);  // background voxels below this one: the run starts behind the highest of them
+    L[r * CT_Z + lane] = m ? r * CT_Z + (gaps ? 64 - __builtin_clzll(gaps) : 0) : -1;
+    any |= bits != 0;
+  }
+  if (!__syncthreads_or(any)) {  // no foreground in the tile
+#pragma unroll
+    for (int k = 0; k < CT_ROWS / 4; ++k) {
+      const int r = k * 4 + wave, x = x0 + (r >> 3), y = y0 + (r & 7);
+      if (x < X && y < Y && z < Z) parent[((int64_t)x * Y + y) * Z + z] = -1;
+    }
+    return;
+  }
+  for (int k = 0; k < CT_ROWS / 4; ++k) {
+    const int r = k * 4 + wave, lx = r >> 3, ly = r & 7;
+    const unsigned long long me = rowmask[r];
+    if (!cc_bit(me, lane)) continue;
+    const int i = r * CT_Z + lane;
+    for (int n = 1; n < 5; ++n) {
+      const int dx = cc_dx(n), dy = cc_dy(n), s = dx + (dy < 0 ? -dy : dy);
+      if (s > conn || lx + dx >= CT_X || ly + dy < 0 || ly + dy >= CT_Y) continue;
+      const int r2 = (lx + dx) * CT_Y + ly + dy;
+      const unsigned long long nb = rowmask[r2];
+      if (!nb) continue;
+      if (cc_bit(nb, lane)) {  // this contact stands for the whole overlap of the two runs: the first voxel of the overlap makes the union
+        if (!(lane > 0 && cc_bit(me, lane - 1) && cc_bit(nb, lane - 1))) cc_union<false>(L, i, r2 * CT_Z + lane);
+      } else if (s + 1 <= conn) {  // diagonal contacts, unless this run's voxel beside them touches the same run head-on
+        if (lane > 0 && cc_bit(nb, lane - 1) && !cc_bit(me, lane - 1)) cc_union<false>(L, i, r2 * CT_Z + lane - 1);
+        if (lane < 63 && cc_bit(nb, lane + 1) && !cc_bit(me, lane + 1)) cc_union<false>(L, i, r2 * CT_Z + lane + 1);
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < CT_ROWS / 4; ++k) {
+    const int r = k * 4 + wave, x = x0 + (r >> 3), y = y0 + (r & 7);
+    if (x >= X || y >= Y || z >= Z) continue;
+    int p = -1;
+    if (cc_bit(rowmask[r], lane)) {
+      const int root = cc_find<false>(L, r * CT_Z + lane);  // local order = raster order inside the tile: the root is the tile-local component's smallest index
+      p = (int)((((int64_t)(x0 + (root >> 9))) * Y + (y0 + ((root >> 6) & 7))) * Z + z0 + (root & 63));
+    }
+    parent[((int64_t)x * Y + y) * Z + z] = p;
+  }
+  if (wave == 0) {  // lanes 0 .. 31: one row each
+    const unsigned long long bits = lane < CT_ROWS ? rowmask[lane & (CT_ROWS - 1)] : 0ull;
+    const bool has = bits != 0;
+    unsigned n = (unsigned)__builtin_popcountll(bits);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+    const int x = x0 + (lane >> 3), y = y0 + (lane & 7);
+    const int lo0 = cc_wave_min(has ? x : INT_MAX), lo1 = cc_wave_min(has ? y : INT_MAX), lo2 = cc_wave_min(has ? z0 + __builtin_ctzll(bits | (1ull << 63)) : INT_MAX);
+    const int hi0 = cc_wave_max(has ? x : -1), hi1 = cc_wave_max(has ? y : -1), hi2 = cc_wave_max(has ? z0 + 63 - __builtin_clzll(bits | 1ull) : -1);
+    if (lane == 0) {  // integer atomics: the record does not depend on the order in which workgroups finish
+      atomicAdd(&rec->fg, (unsigned long long)n);
+      atomicMin(&rec->bmin[0], lo0), atomicMin(&rec->bmin[1], lo1), atomicMin(&rec->bmin[2], lo2);
+      atomicMax(&rec->bmax[0], hi0), atomicMax(&rec->bmax[1], hi1), atomicMax(&rec->bmax[2], hi2);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void cc_merge_kernel(const CompRec* __restrict__ rec, int X, int Y, int Z, int conn, int* parent) {
+  const int z0 = blockIdx.x * CT_Z, y0 = blockIdx.y * CT_Y, x0 = blockIdx.z * CT_X;
+  if (cc_tile_outside_box(rec, x0, y0, z0)) return;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int z = z0 + lane;
+  for (int k = 0; k < CT_ROWS / 4; ++k) {
+    const int r = k * 4 + wave, lx = r >> 3, ly = r & 7, x = x0 + lx, y = y0 + ly;
+    if (x >= X || y >= Y) continue;  // (the same in every lane of the wave)
+    const int64_t row = ((int64_t)x * Y + y) * Z;
+    const bool mine = z < Z && parent[row + z] >= 0;  // (whether a voxel is foreground never changes)
+    const unsigned long long me = __ballot(mine);
+    if (!me) continue;
+    const int v = (int)(row + z);
+    // the foreground of the five rows at z - 1, z, z + 1 first (no divergent work between the ballots): bits of the 64 voxels of this tile's z range, and the
+    // two voxels just outside it, which lanes 0 and 63 read
+    unsigned long long nb[5];
+    bool qm[5], qp[5];
+#pragma unroll
+    for (int n = 0; n < 5; ++n) {
+      const int dx = cc_dx(n), dy = cc_dy(n), s = dx + (dy < 0 ? -dy : dy);
+      const int xn = x + dx, yn = y + dy;
+      nb[n] = 0, qm[n] = qp[n] = false;
+      if (s > conn || xn >= X || yn < 0 || yn >= Y) continue;  // (the same in every lane)
+      const int64_t row2 = ((int64_t)xn * Y + yn) * Z;
+      nb[n] = __ballot(z < Z && parent[row2 + z] >= 0);
+      qm[n] = lane == 0 ? (z >= 1 && parent[row2 + z - 1] >= 0) : cc_bit(nb[n], lane - 1);
+      qp[n] = lane == 63 ? (z + 1 < Z && parent[row2 + z + 1] >= 0) : cc_bit(nb[n], lane + 1);
+    }
+    if (!mine) continue;
+    const bool me_m = lane > 0 && cc_bit(me, lane - 1), me_p = lane < 63 && cc_bit(me, lane + 1);  // this run's voxels beside this one, in this tile
+#pragma unroll
+    for (int n = 0; n < 5; ++n) {
+      const int dx = cc_dx(n), dy = cc_dy(n), s = dx + (dy < 0 ? -dy : dy);
+      const int xn = x + dx, yn = y + dy;
+      if (s > conn || xn >= X || yn < 0 || yn >= Y) continue;
+      const bool other_xy = lx + dx >= CT_X || ly + dy < 0 || ly + dy >= CT_Y;  // the neighbour row belongs to another tile
+      const int64_t row2 = ((int64_t)xn * Y + yn) * Z;
+      const bool q0 = cc_bit(nb[n], lane);
+      // head-on: the first voxel of the overlap of the two runs makes the union for all of it
+      if (s > 0 && other_xy && q0 && !(me_m && cc_bit(nb[n], lane - 1))) cc_union<true>(parent, v, (int)(row2 + z));
+      // a diagonal neighbour counts when it lies in another tile; inside the z range of this tile it is already joined through a head-on contact if there is one
+      if (s > 0 && s + 1 <= conn && qm[n] && (lane == 0 || (other_xy && !q0 && !me_m))) cc_union<true>(parent, v, (int)(row2 + z - 1));
+      if ((s == 0 || s + 1 <= conn) && qp[n] && (lane == 63 || (other_xy && !q0 && !me_p))) cc_union<true>(parent, v, (int)(row2 + z + 1));
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void cc_flatten_kernel(const CompRec* __restrict__ rec, int X, int Y, int Z, int* parent, unsigned* __restrict__ cnt) {
+  const int z0 = blockIdx.x * CT_Z, y0 = blockIdx.y * CT_Y, x0 = blockIdx.z * CT_X;
+  if (cc_tile_outside_box(rec, x0, y0, z0)) return;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int z = z0 + lane;
+  if (z >= Z) return;
+  for (int k = 0; k < CT_ROWS / 4; ++k) {
+    const int r = k * 4 + wave, x = x0 + (r >> 3), y = y0 + (r & 7);
+    if (x >= X || y >= Y) continue;
+    const int v = (int)(((int64_t)x * Y + y) * Z + z);
+    if (parent[v] < 0) continue;
+    const int root = cc_find<true>(parent, v);  // (a link another thread has flattened meanwhile is as good as the old one)
+    parent[v] = root;
+    if (root == v) cnt[v] = 0;
+  }
+}
+
+__global__ __launch_bounds__(256) void cc_sizes_kernel(const CompRec* __restrict__ rec, int X, int Y, int Z, const int* __restrict__ parent, unsigned* cnt) {
+  __shared__ int s_root;
+  __shared__ unsigned s_cnt;
+  const int z0 = blockIdx.x * CT_Z, y0 = blockIdx.y * CT_Y, x0 = blockIdx.z * CT_X;
+  if (cc_tile_outside_box(rec, x0, y0, z0)) return;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int z = z0 + lane;
+  if (threadIdx.x == 0) s_root = INT_MAX, s_cnt = 0;
+  __syncthreads();
+  int p[CT_ROWS / 4], lo = INT_MAX;
+#pragma unroll
+  for (int k = 0; k < CT_ROWS / 4; ++k) {
+    const int r = k * 4 + wave, x = x0 + (r >> 3), y = y0 + (r & 7);
+    p[k] = (x < X && y < Y && z < Z) ? parent[((int64_t)x * Y + y) * Z + z] : -1;
+    if (p[k] >= 0) lo = min(lo, p[k]);
+  }
+  lo = cc_wave_min(lo);
+  if (lane == 0 && lo != INT_MAX) atomicMin(&s_root, lo);
+  __syncthreads();
+  const int first = s_root;  // the smallest root seen in this tile: summed in LDS; INT_MAX: no foreground here
+  if (first == INT_MAX) return;
+  unsigned mine = 0;
+#pragma unroll
+  for (int k = 0; k < CT_ROWS / 4; ++k) {
+    mine += (unsigned)__builtin_popcountll(__ballot(p[k] == first));
+    bool act = p[k] >= 0 && p[k] != first;
+    unsigned long long m = __ballot(act);
+    while (m) {  // the other roots of this row: one atomic per root and wave
+      const int leader = __builtin_ctzll(m);
+      const int root = __shfl(p[k], leader, 64);
+      const unsigned long long same = __ballot(act && p[k] == root);
+      if (lane == leader) atomicAdd(cnt + root, (unsigned)__builtin_popcountll(same));
+      if (p[k] == root) act = false;
+      m &= ~same;
+    }
+  }
+  if (lane == 0 && mine) atomicAdd(&s_cnt, mine);
+  __syncthreads();
+  if (threadIdx.x == 0 && s_cnt) atomicAdd(cnt + first, s_cnt);
+}
+
+__global__ __launch_bounds__(256) void cc_select_kernel(CompRec* __restrict__ rec, int X, int Y, int Z, const int* __restrict__ parent, const unsigned* __restrict__ cnt) {
+  const int z0 = blockIdx.x * CT_Z, y0 = blockIdx.y * CT_Y, x0 = blockIdx.z * CT_X;
+  if (cc_tile_outside_box(rec, x0, y0, z0)) return;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int z = z0 + lane;
+  unsigned long long key = 0;
+  unsigned roots = 0;
+  for (int k = 0; k < CT_ROWS / 4; ++k) {
+    const int r = k * 4 + wave, x = x0 + (r >> 3), y = y0 + (r & 7);
+    if (x >= X || y >= Y || z >= Z) continue;
+    const int v = (int)(((int64_t)x * Y + y) * Z + z);
+    if (parent[v] != v) continue;
+    const unsigned long long mykey = ((unsigned long long)cnt[v] << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)(v + 1));
+    key = mykey > key ? mykey : key;
+    ++roots;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long other = __shfl_xor(key, o, 64);
+    key = other > key ? other : key;
+    roots += __shfl_xor(roots, o, 64);
+  }
+  if (lane == 0 && roots) {
+    atomicMax(&rec->best, key);
+    atomicAdd(&rec->ncomp, roots);
+  }
+}
+
+// LABELS: out = int32 labels [X][Y][Z]; otherwise out = fp32 one-hot [X][Y][Z][2] of the selected component.
+template <bool LABELS>
+__global__ __launch_bounds__(256) void cc_write_kernel(const CompRec* __restrict__ rec, int Y, int Z, int64_t nvox, const int* __restrict__ parent, void* __restrict__ out,
+                                                      long long* __restrict__ stats) {
+  const unsigned long long best = rec->best;
+  const int keep = best ? (int)(0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull)) - 1 : -2;  // root of the selected component
+  if (stats && blockIdx.x == 0 && threadIdx.x == 0) {
+    stats[0] = (long long)rec->fg;
+    stats[1] = (long long)rec->ncomp;
+    stats[2] = (long long)(best >> 32);
+    stats[3] = best ? (long long)keep + 1 : 0;
+  }
+  const int b0x = rec->bmin[0], b0y = rec->bmin[1], b0z = rec->bmin[2], b1x = rec->bmax[0], b1y = rec->bmax[1], b1z = rec->bmax[2];
+  for (unsigned v = blockIdx.x * 256u + threadIdx.x; v < (unsigned)nvox; v += gridDim.x * 256u) {  // (nvox < 2^31 and the stride < 2^24: no wrap)
+    const unsigned xy = v / (unsigned)Z, x = xy / (unsigned)Y;
+    const int z = (int)(v - xy * (unsigned)Z), y = (int)(xy - x * (unsigned)Y);
+    int p = -1;
+    if ((int)x >= b0x && (int)x <= b1x && y >= b0y && y <= b1y && z >= b0z && z <= b1z) p = parent[v];
+    if (LABELS) {
+      static_cast<int*>(out)[v] = p + 1;
+    } else {
+      const float f = p == keep ? 1.f : 0.f;
+      static_cast<float2*>(out)[v] = make_float2(1.f - f, f);
+    }
+  }
+}
+
+bool cc_dims_ok(const int32_t* dims) {
+  if (!dims) return false;
+  for (int a = 0; a < 3; ++a)
+    if (dims[a] < 1 || dims[a] > CC_MAX_EXTENT) return false;
+  return true;
+}
+
+int cc_run(const char* name, const float* logits, int32_t pitch, const int32_t* dims, int32_t connectivity, void* scratch, int64_t scratch_bytes, void* out, int out_align, bool labels,
+           int64_t* stats, bool stats_required, void* stream) {
+  VSSEG_CHECK(logits && scratch && out && (stats || !stats_required), "%s: null pointer (logits, scratch, %s)", name, labels ? "labels, stats" : "out");
+  VSSEG_CHECK(pitch == 2, "%s: pitch must be 2 (channels-last two-class logits), got %d", name, pitch);
+  VSSEG_CHECK(cc_dims_ok(dims), "%s: dims must be 1 .. %d on every axis", name, CC_MAX_EXTENT);
+  const int64_t nvox = (int64_t)dims[0] * dims[1] * dims[2];
+  VSSEG_CHECK(nvox < (int64_t)INT32_MAX, "%s: dims %d x %d x %d hold %lld voxels, the int32 labels allow fewer than 2^31 - 1", name, dims[0], dims[1], dims[2], (long long)nvox);
+  VSSEG_CHECK(connectivity == 6 || connectivity == 18 || connectivity == 26, "%s: connectivity must be 6, 18 or 26, got %d", name, connectivity);
+  VSSEG_CHECK((reinterpret_cast<uintptr_t>(logits) & 7) == 0 && (reinterpret_cast<uintptr_t>(out) & (uintptr_t)(out_align - 1)) == 0 && (reinterpret_cast<uintptr_t>(stats) & 7) == 0 &&
+                  (reinterpret_cast<uintptr_t>(scratch) & 255) == 0,
+              "%s: misaligned operand (logits / stats 8 B, %s, scratch 256 B)", name, labels ? "labels 4 B" : "out 8 B");
+  const CompLayout l = cc_layout(nvox);
+  VSSEG_CHECK(scratch_bytes >= l.total, "%s: %lld bytes of scratch, %lld needed (vsseg_components_scratch_bytes)", name, (long long)scratch_bytes, (long long)l.total);
+  const int X = dims[0], Y = dims[1], Z = dims[2];
+  const int conn = connectivity == 6 ? 1 : connectivity == 18 ? 2 : 3;  // largest |dx| + |dy| + |dz| of a neighbour
+  hipStream_t s = as_stream(stream);
+  char* base = static_cast<char*>(scratch);
+  CompRec* rec = reinterpret_cast<CompRec*>(base);
+  int* parent = reinterpret_cast<int*>(base + l.parent);
+  unsigned* cnt = reinterpret_cast<unsigned*>(base + l.cnt);
+  const dim3 tiles((Z + CT_Z - 1) / CT_Z, (Y + CT_Y - 1) / CT_Y, (X + CT_X - 1) / CT_X);
+  hipLaunchKernelGGL(cc_init_kernel, dim3(1), dim3(64), 0, s, rec);
+  hipLaunchKernelGGL(cc_local_kernel, tiles, dim3(256), 0, s, logits, X, Y, Z, conn, parent, rec);
+  hipLaunchKernelGGL(cc_merge_kernel, tiles, dim3(256), 0, s, (const CompRec*)rec, X, Y, Z, conn, parent);
+  hipLaunchKernelGGL(cc_flatten_kernel, tiles, dim3(256), 0, s, (const CompRec*)rec, X, Y, Z, parent, cnt);
+  hipLaunchKernelGGL(cc_sizes_kernel, tiles, dim3(256), 0, s, (const CompRec*)rec, X, Y, Z, (const int*)parent, cnt);
+  hipLaunchKernelGGL(cc_select_kernel, tiles, dim3(256), 0, s, rec, X, Y, Z, (const int*)parent, (const unsigned*)cnt);
+  const int wg = grid_for(nvox, 256, 256 * 32);
+  if (labels) hipLaunchKernelGGL(cc_write_kernel<true>, dim3(wg), dim3(256), 0, s, (const CompRec*)rec, Y, Z, nvox, (const int*)parent, out, reinterpret_cast<long long*>(stats));
+  else hipLaunchKernelGGL(cc_write_kernel<false>, dim3(wg), dim3(256), 0, s, (const CompRec*)rec, Y, Z, nvox, (const int*)parent, out, reinterpret_cast<long long*>(stats));
+  VSSEG_LAUNCH_CHECK(name);
+  return VSSEG_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t vsseg_components_scratch_bytes(const int32_t dims[3]) {
+  VSSEG_CHECK(cc_dims_ok(dims), "vsseg_components_scratch_bytes: dims must be 1 .. %d on every axis", CC_MAX_EXTENT);
+  const int64_t nvox = (int64_t)dims[0] * dims[1] * dims[2];
+  VSSEG_CHECK(nvox < (int64_t)INT32_MAX, "vsseg_components_scratch_bytes: dims %d x %d x %d hold %lld voxels, the int32 labels allow fewer than 2^31 - 1", dims[0], dims[1], dims[2],
+              (long long)nvox);
+  return cc_layout(nvox).total;
+}
+
+extern "C" int vsseg_components_label(const float* logits, int32_t pitch, const int32_t dims[3], int32_t connectivity, void* scratch, int64_t scratch_bytes, int32_t* labels,
+                                      int64_t* stats, void* stream) {
+  return cc_run("vsseg_components_label", logits, pitch, dims, connectivity, scratch, scratch_bytes, labels, 4, true, stats, true, stream);
+}
+
+extern "C" int vsseg_keep_largest_component(const float* logits, int32_t pitch, const int32_t dims[3], int32_t connectivity, void* scratch, int64_t scratch_bytes, float* out,
+                                            int64_t* stats, void* stream) {
+  return cc_run("vsseg_keep_largest_component", logits, pitch, dims, connectivity, scratch, scratch_bytes, out, 8, false, stats, false, stream);
+}

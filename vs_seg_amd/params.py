@@ -29,6 +29,7 @@ import torch
 from . import Adam, Dice_spvPA, UNet2d5_spvPA, compute_dice_score, sliding_window_inference
 from .inferers import argmax_segmentation
 from .metrics import compute_surface_distances, voxel_spacing
+from .postprocess import keep_largest_component
 from . import parallel as DP
 from .data import nifti
 from .data.transforms import PatchSampler, epoch_batches, load_case
@@ -92,6 +93,8 @@ class VSparams:
         parser.add_argument("--compute_dtype", type=str, default="bf16", choices=["bf16", "fp32"], help="bf16 MFMA (benchmark) or exact-fp32 MFMA (parity)")
         parser.add_argument("--num_epochs", type=int, default=None)
         parser.add_argument("--surface_metrics", action="store_true", help="run_inference also reports HD95 and ASSD per test case (mm, on the GPU) and writes figures/test_surface_metrics.csv")
+        parser.add_argument("--keep_largest_component", action="store_true", help="run_inference keeps only the largest connected component of each predicted segmentation (on the GPU) before the Dice, the surface metrics and the NIfTI export, and writes figures/test_postprocessing.csv")
+        parser.add_argument("--component_connectivity", type=int, default=26, choices=[6, 18, 26], help="voxel connectivity of --keep_largest_component (26: MONAI's KeepLargestConnectedComponent)")
         args = parser.parse_args(argv)
 
         self.debug, self.dataset, self.data_root = args.debug, args.dataset, args.data_root
@@ -113,6 +116,7 @@ class VSparams:
         self.export_inferred_segmentations = True
         self.compute_dtype = args.compute_dtype
         self.surface_metrics = args.surface_metrics
+        self.keep_largest_component, self.component_connectivity = args.keep_largest_component, args.component_connectivity
         self.results_folder_path = os.path.join(self.data_root, "results", "debug" if self.debug else args.results_folder_name)
         self.logs_path = os.path.join(self.results_folder_path, "logs")
         self.model_path = os.path.join(self.results_folder_path, "model")
@@ -146,7 +150,8 @@ class VSparams:
         log("Parameters: ")
         for k in ("dataset", "data_root", "split_csv", "pad_crop_shape", "pad_crop_shape_test", "num_workers", "torch_device_arg", "train_batch_size", "initial_learning_rate",
                   "epochs_with_const_lr", "lr_divisor", "weight_decay", "num_epochs", "val_interval", "model", "sliding_window_inferer_roi_size", "attention", "hardness",
-                  "results_folder_path", "export_inferred_segmentations", "compute_dtype") + (("surface_metrics",) if self.surface_metrics else ()):
+                  "results_folder_path", "export_inferred_segmentations", "compute_dtype") + (("surface_metrics",) if self.surface_metrics else ()) + (
+                      ("keep_largest_component", "component_connectivity") if self.keep_largest_component else ()):
             log("{:<34s} {}".format(k + " =", getattr(self, k)))
         log("-" * 10)
 
@@ -343,6 +348,8 @@ class VSparams:
         n = len(data_loader)
         dice_dev = torch.zeros(n, dtype=torch.float32, device=self.device)
         surf_dev = torch.zeros((2, n), dtype=torch.float32, device=self.device) if self.surface_metrics else None  # [hd95, assd] per case, mm
+        # --keep_largest_component: [raw Dice, foreground voxels, components, kept voxels] per case (fp64: the voxel counts of a full volume are not exact in fp32)
+        post_dev = torch.zeros((4, n), dtype=torch.float64, device=self.device) if self.keep_largest_component else None
         predictor = model.segmentation_predictor() if hasattr(model, "segmentation_predictor") else (lambda *a, **k: model(*a, **k)[0])  # model_segmentation, ref:params/VSparams.py:560
         mine = DP.shard_indices(n)  # the unpadded, unshuffled test loader yields exactly these cases, in this order
         with torch.no_grad():
@@ -351,24 +358,51 @@ class VSparams:
                 logger.info("starting image {}".format(mine[i]))
                 outputs = sliding_window_inference(inputs=data["image"], roi_size=self.sliding_window_inferer_roi_size, sw_batch_size=1, predictor=predictor, mode="gaussian")
                 gi = mine[i]
+                if post_dev is not None:  # everything below describes the filtered prediction; the raw Dice is kept beside it
+                    post_dev[0, gi] = self.compute_dice_score(outputs, data["label"]).reshape(())
+                    outputs, stats = keep_largest_component(outputs, self.component_connectivity, return_stats=True)
+                    post_dev[1:, gi] = stats[0, :3]
                 dice_dev[gi] = self.compute_dice_score(outputs, data["label"]).reshape(())
                 if surf_dev is not None:
                     surf_dev[:, gi] = compute_surface_distances(outputs, data["label"], voxel_spacing(data["label_meta_dict"]["affine"]), 95.0)[0]
                 if self.export_inferred_segmentations:
                     self.export_segmentation(outputs, data["label_meta_dict"])
-        if surf_dev is not None:
-            both = torch.cat([dice_dev[None], surf_dev])  # one all-reduce; a case that is not this rank's is 0 here (NaN / inf + 0 stay NaN / inf)
+        surf = post = None
+        if surf_dev is not None or post_dev is not None:
+            rows = [dice_dev[None]] + ([surf_dev] if surf_dev is not None else []) + ([post_dev] if post_dev is not None else [])
+            both = torch.cat(rows)  # one all-reduce; a case that is not this rank's is 0 here (NaN / inf + 0 stay NaN / inf)
             both = (DP.allreduce_sum(both) if self.world > 1 else both).double().cpu().numpy()
-            dice_scores, surf = both[0], both[1:]
+            dice_scores = both[0]
+            if surf_dev is not None:
+                surf = both[1:3]
+            if post_dev is not None:
+                post = both[-4:]
         else:
             dice_scores = DP.allreduce_sum(dice_dev).double().cpu().numpy() if self.world > 1 else dice_dev.double().cpu().numpy()
         for i, v in enumerate(dice_scores):
             logger.info(f"dice_score[{i}] = {v}")
         logger.info(f"all_dice_scores = {dice_scores}")
         logger.info(f"mean_dice_score = {dice_scores.mean()} +- {dice_scores.std()}")
-        if surf_dev is not None:
+        if post is not None:
+            self._log_postprocessing(dice_scores, *post)
+        if surf is not None:
             self._log_surface_metrics(dice_scores, surf[0], surf[1])
         return dice_scores
+
+    def _log_postprocessing(self, dice, dice_raw, foreground, components, kept):
+        """Per-case lines of --keep_largest_component beside the (filtered) dice_score lines, and figures/test_postprocessing.csv (rank 0)."""
+        log = self.logger.info
+        for i, (d, f, c, k) in enumerate(zip(dice_raw, foreground, components, kept)):
+            log(f"dice_score_raw[{i}] = {d}")
+            log(f"components[{i}] = {int(c)}")
+            log(f"removed_voxels[{i}] = {int(f) - int(k)}")
+        log(f"mean_dice_score_raw = {dice_raw.mean()} +- {dice_raw.std()}")
+        if self.rank == 0:
+            os.makedirs(self.figures_path, exist_ok=True)
+            with open(os.path.join(self.figures_path, "test_postprocessing.csv"), "w") as f:
+                f.write("case,dice_raw,dice,components,foreground_voxels,kept_voxels\n")
+                for i, (r, d, c, fg, k) in enumerate(zip(dice_raw, dice, components, foreground, kept)):
+                    f.write(f"{i},{float(r)!r},{float(d)!r},{int(c)},{int(fg)},{int(k)}\n")
 
     def _log_surface_metrics(self, dice, hd95, assd):
         """Per-case HD95 / ASSD lines, their mean +- std over the finite cases, and figures/test_surface_metrics.csv (rank 0)."""
