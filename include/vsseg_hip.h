@@ -61,6 +61,17 @@ typedef struct {
 } vsseg_tensor;
 #define VSSEG_ZERO_PADDED 1
 
+/* Negative values of vsseg_igemm_desc.depth: which kernel runs the launch */
+#define VSSEG_DEPTH_NOPREFETCH (-1)     /* the general kernel without prefetch: one halo buffer (half the LDS, more resident workgroups) */
+#define VSSEG_DEPTH_STREAM (-2)         /* streaming kernel (sconv.hip) */
+#define VSSEG_DEPTH_COMPUTE (-3)        /* compute kernel (cconv.hip) */
+#define VSSEG_DEPTH_STREAM_SHUFFLE (-4) /* streaming kernel, fused output-parity classes */
+#define VSSEG_DEPTH_MARCH (-5)          /* marching kernel (mconv.hip) */
+#define VSSEG_DEPTH_MARCH_WREG (-6)     /* marching kernel, packed weights in registers */
+#define VSSEG_DEPTH_DEEP (-7)           /* deep-level kernel (dconv.hip) */
+#define VSSEG_DEPTH_TRANSITION (-8)     /* level 2 <-> 3 transition kernel (tconv.hip) */
+#define VSSEG_DEPTH_GATHER (-9)         /* gathering marching kernel (gconv.hip) */
+
 /* One implicit-GEMM launch over an output lattice q in [0,q): out[q*os+oo][n] = epi( sum_t sum_c in[q*is+off_t][c] * W[t][c][n] ).
  * Covers Conv3d forward, every parity class of ConvTranspose3d forward, and both data-gradients
  * (ref:params/networks/blocks/convolutions.py:114-146 and their autograd at ref:params/VSparams.py:461). */
@@ -77,12 +88,12 @@ typedef struct {
   int32_t ck;              /* input channels staged per chunk (multiple of 8, divides padded Cin) */
   int32_t nchunks;
   int32_t ksteps;          /* K-steps (4 groups of 8 channels) per chunk */
-  int32_t depth;           /* LDS-DMA prefetch distance in stages (1..3; 0 = 1): the halo ring holds depth+1 buffers.  -1: no prefetch, one buffer (half the LDS, more resident workgroups) */
-                           /* negative depths below -1 select a specialised kernel with the same contract (outside its domain: VSSEG_EINVAL, never a fallback): -2 / -4 streaming (sconv.hip), -3 compute (cconv.hip),
-                            * -5 / -6 marching (mconv.hip), -7 deep levels (dconv.hip), -8 the level 2 <-> 3 transition kernel (tconv.hip: class_split = 8 parity classes of a 3x3x3 stride-(2,2,2) transposed
-                            * convolution / strided data gradient, 48 or 64 input and 48 output channels, tile 4x8x8 with mtw = 16, nt = 3, ck = in.c, bf16, plain / statistics / eval affine / accumulate epilogue),
-                            * -9 the gathering marching kernel (gconv.hip: is = (2, 2, 1) 3x3x1 launches that read the fine level and write the coarse one — strided convolutions 16 -> 16 / 32 -> 32, data
-                            * gradients of the transposed convolutions 32 -> 16 / 48 -> 32 —, tile = (x steps, 64 * mtw / tz rows, tz), ck = in.c in {16, 32}, one-part bf16 tensors, the same four epilogues) */
+  int32_t depth;           /* LDS-DMA prefetch distance in stages (1..3; 0 = 1): the halo ring holds depth+1 buffers.  Negative: one of the VSSEG_DEPTH_* selectors below — the general kernel without
+                            * prefetch, or a specialised kernel with the same contract (outside its domain, or a value that is none of them: VSSEG_EINVAL, never a fallback).  The kernels' domains:
+                            * VSSEG_DEPTH_TRANSITION (tconv.hip): class_split = 8 parity classes of a 3x3x3 stride-(2,2,2) transposed
+                            * convolution / strided data gradient, 48 or 64 input and 48 output channels, tile 4x8x8 with mtw = 16, nt = 3, ck = in.c, bf16, plain / statistics / eval affine / accumulate epilogue;
+                            * VSSEG_DEPTH_GATHER (gconv.hip): is = (2, 2, 1) 3x3x1 launches that read the fine level and write the coarse one — strided convolutions 16 -> 16 / 32 -> 32, data
+                            * gradients of the transposed convolutions 32 -> 16 / 48 -> 32 —, tile = (x steps, 64 * mtw / tz rows, tz), ck = in.c in {16, 32}, one-part bf16 tensors, the same four epilogues */
   const void* wpack;       /* [nsplit][nchunks][ksteps][nt][64 lanes][8] in the compute dtype (== in.dtype) */
   /* epilogue: v = acc + bias; stats(v); v = v*scale+shift; v = act(v); residual; accumulate; store */
   const float* bias;       /* [cout] or NULL */
@@ -102,7 +113,7 @@ typedef struct {
   int32_t cout_mod;
   const float* gate;       /* VSSEG_RES_GATE: fp32 attention map [N][X][Y][Z] of the output tensor, or NULL */
   const float* in_gate;    /* fp32 attention map [N][X][Y][Z] of the INPUT tensor, or NULL: input voxel v is multiplied by (1 + in_gate[v]) on load
-                            * (AttentionBlock2 folded into the convolution that reads its output; marching kernel, depth -5, only) */
+                            * (AttentionBlock2 folded into the convolution that reads its output; marching kernel, VSSEG_DEPTH_MARCH, only) */
   /* All output-parity classes of a strided transposed convolution / data gradient in ONE launch of the general kernel (class_split = number of
    * classes, 2..8; 0 = off): `nsplit` = class_split, workgroup row s of the grid computes class s — ALL output channels (out.c = nt*16) at output
    * voxels q*os + class_oo[s] — from the class's own taps class_tap[s][0..class_ntaps[s]) (indices into tap_off, which lists the union of the classes'
@@ -113,7 +124,7 @@ typedef struct {
   int32_t class_ntaps[8];
   int32_t class_tap[8][8];
   /* A 1x1x1 convolution of the SAME input riding along (the ResidualUnit's residual convolution, ref:params/networks/blocks/convolutions.py:241-255; marching kernel,
-   * depth -5 / -6, plain or statistics epilogue only): res_tiles more 16-channel output tiles that run only the K-steps of the centre tap; the input is read once
+   * VSSEG_DEPTH_MARCH / _MARCH_WREG, plain or statistics epilogue only): res_tiles more 16-channel output tiles that run only the K-steps of the centre tap; the input is read once
    * for both convolutions.  res_out.ptr != NULL: their values (+ bias_res) are stored there (bf16) — training, where the add sits behind the BatchNorm pass;
    * res_out.ptr == NULL: they are added to the main tiles behind their activation — eval: out = act(bn(conv(x))) + residual(x).  0: off. */
   int32_t res_tiles;
@@ -186,7 +197,7 @@ int vsseg_conv_bwd_fused(const vsseg_conv_bwd_desc* d, void* stream);
  * h (cmid channels) lives in LDS only.  The pairs of the sliding-window predictor (ref:params/VSparams.py:553-567): the first ResidualUnit of the encoder, 1 -> 16 -> 16 with the
  * 1x1x1 residual convolution of the one-channel input added behind the second activation (ref:params/networks/blocks/convolutions.py:241-255), and the attention block of the
  * finest decoder level, 32 -> 16 -> 1 + sigmoid (ref:params/networks/blocks/attentionblock.py:20-41).  Results are bit-identical to the two vsseg_igemm marching launches
- * (depth -5) with the same packed weights.  With a BatchNorm in stage A it is not applicable in training (the BatchNorm needs the
+ * (VSSEG_DEPTH_MARCH) with the same packed weights.  With a BatchNorm in stage A it is not applicable in training (the BatchNorm needs the
  * statistics of all of h first). */
 typedef struct {
   vsseg_tensor in;         /* bf16: a multiple of 8 channels (16-byte aligned voxel rows; may be two-part) or a COMPACT one-channel tensor (c = pitch = 1) standing for one zero-extended group */

@@ -6,6 +6,7 @@ import torch
 
 from vs_seg_amd import _lib as L
 from vs_seg_amd import planner as P
+from vs_seg_amd.engine import fill_igemm_desc, fill_wgrad_desc
 
 DT = {"fp32": torch.float32, "bf16": torch.bfloat16}
 
@@ -60,19 +61,8 @@ def pack(plan: P.IgemmPlan, w: torch.Tensor, dtype) -> torch.Tensor:
 def igemm_desc(plan: P.IgemmPlan, wpack: torch.Tensor, inp: L.Tensor, out: L.Tensor, **kw) -> L.IgemmDesc:
     d = L.IgemmDesc()
     d.inp, d.out = inp, out
-    d.q, d.is_, d.os, d.oo = L.i3(plan.q), L.i3(plan.cls.is_), L.i3(plan.cls.os), L.i3(plan.cls.oo)
-    d.ntaps = plan.ntaps
-    for t, (off, _) in enumerate(plan.cls.taps):
-        d.tap_off[t][0], d.tap_off[t][1], d.tap_off[t][2] = off
-    d.tile = L.i3(plan.tile)
-    d.mtw, d.nt, d.nsplit, d.ck, d.nchunks, d.ksteps, d.depth = plan.mtw, plan.nt, plan.nsplit, plan.ck, plan.nchunks, plan.ksteps, plan.depth
+    fill_igemm_desc(d, plan)
     d.wpack = wpack.data_ptr()
-    d.class_split = len(plan.classes) if plan.classes is not None else 0
-    for s_, c_ in enumerate(plan.classes or ()):
-        d.class_oo[s_][0], d.class_oo[s_][1], d.class_oo[s_][2] = c_.oo
-        d.class_ntaps[s_] = len(c_.taps)
-        for i, t in enumerate(plan.class_taps(s_)):
-            d.class_tap[s_][i] = t
     for k, v in kw.items():
         setattr(d, k, v)
     return d
@@ -117,13 +107,8 @@ def run_wgrad(transposed, wshape, kernel, stride, p_cl, h_cl, cp_valid, ch_valid
     dw = torch.zeros(int(np.prod(wshape)), dtype=torch.float32, device="cuda")
     d = L.WgradDesc()
     d.p, d.h, d.cp_valid, d.ch_valid = tdesc(p_cl), (two_part(*h_cl) if isinstance(h_cl, tuple) else tdesc(h_cl)), cp_valid, ch_valid
-    d.q, d.hs, d.ntaps = L.i3(wp.q), L.i3(wp.hs), len(wp.taps)
-    for t, (off, widx) in enumerate(wp.taps):
-        d.tap_off[t][0], d.tap_off[t][1], d.tap_off[t][2] = off
-        d.tap_widx[t] = widx
-    d.tile, d.ntp = L.i3(wp.tile), wp.ntp
+    fill_wgrad_desc(d, wp)
     d.dw = dw.data_ptr()
-    d.stride_p, d.stride_h, d.stride_tap = wp.stride_p, wp.stride_h, wp.stride_tap
     d.persistent_blocks = wp.blocks
     d.hgroup, d.single_buffer = hgroup, single_buffer
     if march_tile is not None:  # the marching kernel (csrc/mwgrad.hip): tile = (x steps per workgroup, rows, z slices)

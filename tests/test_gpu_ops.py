@@ -609,7 +609,7 @@ def test_every_candidate_plan_gives_the_same_convolution(kind, k, cin, cout, dim
         inp_cl, want, nout, bias = H.to_cl(gy, H.DT[dt]), xd.grad, cin, None
     cls = P.lattice_classes(kind, k, (1, 1, 1))[0]
     cands = P.candidate_plans(kind, tuple(w.shape), cls, dims, inp_cl.element_size(), kc_pad=inp_cl.shape[-1], aux_es=inp_cl.element_size(), in_split=split)
-    assert len(cands) >= 2 and (dt == "fp32" or (len(cands) >= 4 and (any(c.depth == -1 for c in cands) or all(c.nt >= 3 for c in cands if c.depth >= -1)) and len({(c.ck, c.mtw, c.nsplit) for c in cands}) >= 3))  # nt >= 3: producer / consumer kernels always prefetch
+    assert len(cands) >= 2 and (dt == "fp32" or (len(cands) >= 4 and (any(c.depth == L.DEPTH_NOPREFETCH for c in cands) or all(c.nt >= 3 for c in cands if c.depth >= L.DEPTH_NOPREFETCH)) and len({(c.ck, c.mtw, c.nsplit) for c in cands}) >= 3))  # nt >= 3: producer / consumer kernels always prefetch
     parts = H._split_cl(inp_cl, split) if split else None
     for mode in ("plain", "stats", "accumulate"):
         for pl in cands:
@@ -683,7 +683,7 @@ def test_streaming_kernel_equals_general_kernel(kind, k, cin, cout, dims, split)
     gen.pack_map = P.pack_map(gen, tuple(w.shape))
     kreal, nreal = P.gemm_dims(kind, tuple(w.shape))
     sp = P.stream_plan(kind, tuple(w.shape), cls, dims, 2, kc, nreal, kreal)
-    assert sp is not None and sp.depth == -2
+    assert sp is not None and sp.depth == L.DEPTH_STREAM
     sp.pack_map = P.pack_map(sp, tuple(w.shape))
     parts = H._split_cl(inp_cl, split) if split else None
     odt = torch.float32 if nout == 2 else H.DT[dt]
@@ -780,7 +780,7 @@ def test_marching_kernel_equals_general_kernel(kind, cin, cout, dims, split, sha
             m_ = dataclasses.replace(m_[0], tile=(lx, m_[0].tile[1], tz))
             m_.pack_map = P.pack_map(m_, tuple(w.shape))
             mps.append(m_)
-    assert mps and mps[0].depth == -5
+    assert mps and mps[0].depth == L.DEPTH_MARCH
     parts = H._split_cl(inp_cl, split) if split else None
     odt = torch.float32 if nout == 2 else H.DT[dt]
     res_t = H.to_cl(_round(torch.randn(2, nout, *dims), dt), H.DT[dt])
@@ -912,7 +912,7 @@ def test_gathering_marching_kernel_equals_general_kernel(kind, cin, cout, dims, 
             elif mode == "accumulate":
                 kw.update(accumulate=1)
             d = H.igemm_desc(pl, H.pack(pl, w, inp_cl.dtype), H.tdesc(inp_cl), H.tdesc(out), **kw)
-            if pl.depth == -9:
+            if pl.depth == L.DEPTH_GATHER:
                 assert lib.vsseg_igemm_lds_bytes(C.byref(d)) == pl.lds
             L.check(lib.vsseg_igemm(C.byref(d), H.stream()), f"igemm D={pl.depth} {mode}")
             torch.cuda.synchronize()
@@ -1143,7 +1143,7 @@ def test_marching_kernel_with_residual_tiles(cin, cout, dims, shape, lx):
     tz, mtw = shape
     for depth in P.MARCH_DEPTHS:
         mp = [pl for pl in P.march_res_plans(tuple(w.shape), tuple(wr.shape), cls, dims, 2, cin, n=n) if (pl.tile[2], pl.mtw, pl.depth) == (tz, mtw, depth)]
-        if not mp and depth == -6:  # (weights-in-registers twins exist for some shapes only)
+        if not mp and depth == L.DEPTH_MARCH_WREG:  # (weights-in-registers twins exist for some shapes only)
             continue
         assert mp, (depth, [(p_.tile, p_.mtw, p_.depth) for p_ in P.march_res_plans(tuple(w.shape), tuple(wr.shape), cls, dims, 2, cin, n=n)])
         mp = dataclasses.replace(mp[0], tile=(lx, mp[0].tile[1], tz))
@@ -1168,7 +1168,7 @@ def test_marching_kernel_with_residual_tiles(cin, cout, dims, shape, lx):
         # one launch, residual tensor stored
         y, r = torch.full_like(y_ref, float("nan")), torch.full_like(y_ref, float("nan"))
         st = torch.zeros_like(st_ref)
-        d = H.igemm_desc(mp, wp, H.tdesc(xcl), H.tdesc(y), bias=b.data_ptr(), stats=st.data_ptr(), stats_stride=cout, res_tiles=mp.res_tiles, wpack_res=wpr.data_ptr(), bias_res=br.data_ptr(), res_out=H.tdesc(r))
+        d = H.igemm_desc(mp, wp, H.tdesc(xcl), H.tdesc(y), bias=b.data_ptr(), stats=st.data_ptr(), stats_stride=cout, wpack_res=wpr.data_ptr(), bias_res=br.data_ptr(), res_out=H.tdesc(r))
         L.check(lib.vsseg_igemm(C.byref(d), H.stream()), "igemm + residual tiles")
         torch.cuda.synchronize()
         assert torch.equal(y, y_ref) and torch.equal(r, r_ref), (depth, float((y.float() - y_ref.float()).abs().max()), float((r.float() - r_ref.float()).abs().max()))
@@ -1177,7 +1177,7 @@ def test_marching_kernel_with_residual_tiles(cin, cout, dims, shape, lx):
         # eval form: folded BatchNorm + PReLU, residual added in the epilogue
         sc, sh, al = (torch.rand(cout) + 0.5).cuda(), torch.randn(cout).cuda() * 0.1, torch.tensor([0.25], device="cuda")
         out = torch.full_like(y_ref, float("nan"))
-        d = H.igemm_desc(mp, wp, H.tdesc(xcl), H.tdesc(out), bias=b.data_ptr(), scale=sc.data_ptr(), shift=sh.data_ptr(), alpha=al.data_ptr(), act=L.ACT_PRELU, res_tiles=mp.res_tiles, wpack_res=wpr.data_ptr(), bias_res=br.data_ptr())
+        d = H.igemm_desc(mp, wp, H.tdesc(xcl), H.tdesc(out), bias=b.data_ptr(), scale=sc.data_ptr(), shift=sh.data_ptr(), alpha=al.data_ptr(), act=L.ACT_PRELU, wpack_res=wpr.data_ptr(), bias_res=br.data_ptr())
         L.check(lib.vsseg_igemm(C.byref(d), H.stream()), "igemm + residual tiles (eval)")
         torch.cuda.synchronize()
         yy = F.conv3d(x.double(), w.double(), b.double().cpu(), padding=P.same_pad(k)) * sc.double().cpu().view(1, -1, 1, 1, 1) + sh.double().cpu().view(1, -1, 1, 1, 1)
@@ -1191,10 +1191,10 @@ def test_marching_kernel_with_residual_tiles(cin, cout, dims, shape, lx):
             res = []
             for inp, kw in ((H.tdesc(gated), {}), (H.two_part(*parts), dict(in_gate=att.data_ptr()))):
                 yg, rg, stg = torch.full_like(y_ref, float("nan")), torch.full_like(y_ref, float("nan")), torch.zeros_like(st_ref)
-                d = H.igemm_desc(mp, wp, inp, H.tdesc(yg), bias=b.data_ptr(), stats=stg.data_ptr(), stats_stride=cout, res_tiles=mp.res_tiles, wpack_res=wpr.data_ptr(), bias_res=br.data_ptr(), res_out=H.tdesc(rg), **kw)
+                d = H.igemm_desc(mp, wp, inp, H.tdesc(yg), bias=b.data_ptr(), stats=stg.data_ptr(), stats_stride=cout, wpack_res=wpr.data_ptr(), bias_res=br.data_ptr(), res_out=H.tdesc(rg), **kw)
                 L.check(lib.vsseg_igemm(C.byref(d), H.stream()), "igemm + residual tiles + gate")
                 og = torch.full_like(y_ref, float("nan"))
-                d = H.igemm_desc(mp, wp, inp, H.tdesc(og), bias=b.data_ptr(), scale=sc.data_ptr(), shift=sh.data_ptr(), alpha=al.data_ptr(), act=L.ACT_PRELU, res_tiles=mp.res_tiles, wpack_res=wpr.data_ptr(), bias_res=br.data_ptr(), **kw)
+                d = H.igemm_desc(mp, wp, inp, H.tdesc(og), bias=b.data_ptr(), scale=sc.data_ptr(), shift=sh.data_ptr(), alpha=al.data_ptr(), act=L.ACT_PRELU, wpack_res=wpr.data_ptr(), bias_res=br.data_ptr(), **kw)
                 L.check(lib.vsseg_igemm(C.byref(d), H.stream()), "igemm + residual tiles + gate (eval)")
                 torch.cuda.synchronize()
                 res.append((yg, rg, H.stat_decode(stg).view(L.STAT_SHARDS, 2, -1).sum(0), og))
@@ -1318,7 +1318,7 @@ def test_chained_marching_convolution_equals_the_two_launches(cin, cout, dims, s
 
     def march(w, kc, n_t):
         kreal, nreal = P.gemm_dims("conv_fwd", tuple(w.shape))
-        got = [pl for pl in P.march_plans("conv_fwd", tuple(w.shape), cls, dims, 2, kc, nreal, kreal, n=2) if pl.depth == -5 and pl.nt == n_t]
+        got = [pl for pl in P.march_plans("conv_fwd", tuple(w.shape), cls, dims, 2, kc, nreal, kreal, n=2) if pl.depth == L.DEPTH_MARCH and pl.nt == n_t]
         assert got, "no marching plan"
         pl = got[0]
         pl.pack_map = P.pack_map(pl, tuple(w.shape))
@@ -1382,7 +1382,7 @@ def test_chained_marching_convolution_with_residual_tiles(dims, shape, lx):
 
     def march(w, kc, nt):
         kreal, nreal = P.gemm_dims("conv_fwd", tuple(w.shape))
-        pl = [p_ for p_ in P.march_plans("conv_fwd", tuple(w.shape), cls, dims, 2, kc, nreal, kreal, n=2) if p_.depth == -5 and p_.nt == nt][0]
+        pl = [p_ for p_ in P.march_plans("conv_fwd", tuple(w.shape), cls, dims, 2, kc, nreal, kreal, n=2) if p_.depth == L.DEPTH_MARCH and p_.nt == nt][0]
         pl.pack_map = P.pack_map(pl, tuple(w.shape))
         return pl, H.pack(pl, w, H.DT[dt])
 
@@ -1475,7 +1475,7 @@ def test_compute_kernel_equals_general_kernel(kind, cin, cout, dims, split):
     gen = next(c for c in P.candidate_plans(kind, tuple(w.shape), cls, dims, 2, kc_pad=kc, in_split=split, aux_es=2) if c.ck == 16 and c.depth >= 0)
     kreal, nreal = P.gemm_dims(kind, tuple(w.shape))
     cp = P.compute_plan(kind, tuple(w.shape), cls, dims, 2, kc, nreal, kreal, split)
-    assert cp is not None and cp.depth == -3 and gen.depth != -3
+    assert cp is not None and cp.depth == L.DEPTH_COMPUTE and gen.depth != L.DEPTH_COMPUTE
     cp.pack_map = P.pack_map(cp, tuple(w.shape))
     parts = H._split_cl(inp_cl, split) if split else None
     res_t = H.to_cl(_round(torch.randn(2, nout, *dims), dt), H.DT[dt])
@@ -1559,11 +1559,11 @@ def test_fused_parity_classes_equal_per_class_launches(kind, cin, cout, dims, mo
     # fused
     kreal, nreal = P.gemm_dims(kind, tuple(w.shape))
     pls = P.shuffle_plans(kind, tuple(w.shape), k, st, dims, 2, inp_cl.shape[-1], nreal, kreal)
-    assert pls is not None and len(pls) == nout // 16 and all(pl.depth == -4 for pl in pls)  # 16 channels: one launch; 32: one per px
+    assert pls is not None and len(pls) == nout // 16 and all(pl.depth == L.DEPTH_STREAM_SHUFFLE for pl in pls)  # 16 channels: one launch; 32: one per px
     out_b = prev.clone() if mode == "accumulate" else torch.zeros_like(out_a)
     sb = stats_buf()
     for pl in pls:
-        d = H.igemm_desc(pl, H.pack(pl, w, inp_cl.dtype), H.tdesc(inp_cl), H.tdesc(out_b), cout_mod=nout, **(dict(stats=sb.data_ptr(), stats_stride=nout) if mode == "stats" else kw))
+        d = H.igemm_desc(pl, H.pack(pl, w, inp_cl.dtype), H.tdesc(inp_cl), H.tdesc(out_b), **(dict(stats=sb.data_ptr(), stats_stride=nout) if mode == "stats" else kw))
         L.check(lib.vsseg_igemm(C.byref(d), H.stream()), "fused classes")
     torch.cuda.synchronize()
     np.testing.assert_allclose(H.from_cl(out_b).numpy(), want.float().numpy(), atol=_tol(dt, want))
@@ -1580,7 +1580,7 @@ def test_fused_parity_classes_equal_per_class_launches(kind, cin, cout, dims, mo
             mp2 = dataclasses.replace(mp, tile=(lx, mp.tile[1], mp.tile[2]))
             out_c = prev.clone() if mode == "accumulate" else torch.full_like(out_a, float("nan"))
             sc = stats_buf()
-            d = H.igemm_desc(mp2, H.pack(mp2, w, inp_cl.dtype), H.tdesc(inp_cl), H.tdesc(out_c), cout_mod=nout, **(dict(stats=sc.data_ptr(), stats_stride=nout) if mode == "stats" else kw))
+            d = H.igemm_desc(mp2, H.pack(mp2, w, inp_cl.dtype), H.tdesc(inp_cl), H.tdesc(out_c), **(dict(stats=sc.data_ptr(), stats_stride=nout) if mode == "stats" else kw))
             L.check(lib.vsseg_igemm(C.byref(d), H.stream()), f"marching fused classes {mp2.tile} depth {mp2.depth}")
             torch.cuda.synchronize()
             assert torch.equal(out_c, out_b), f"marching variant tile {mp2.tile} mtw {mp2.mtw} depth {mp2.depth} differs (max {float((out_c.float() - out_b.float()).abs().max())})"
@@ -1597,7 +1597,7 @@ def test_fused_parity_classes_equal_per_class_launches(kind, cin, cout, dims, mo
             mp2 = dataclasses.replace(mp, tile=(lx, mp.tile[1], mp.tile[2]))
             out_c = prev.clone() if mode == "accumulate" else torch.full_like(out_a, float("nan"))
             sc = stats_buf()
-            d = H.igemm_desc(mp2, H.pack(mp2, w, inp_cl.dtype), H.tdesc(inp_cl), H.tdesc(out_c), cout_mod=nout, **(dict(stats=sc.data_ptr(), stats_stride=nout) if mode == "stats" else kw))
+            d = H.igemm_desc(mp2, H.pack(mp2, w, inp_cl.dtype), H.tdesc(inp_cl), H.tdesc(out_c), **(dict(stats=sc.data_ptr(), stats_stride=nout) if mode == "stats" else kw))
             L.check(lib.vsseg_igemm(C.byref(d), H.stream()), f"marching all classes {mp2.tile}")
             torch.cuda.synchronize()
             assert torch.equal(out_c, out_b), f"all-class marching launch tile {mp2.tile} mtw {mp2.mtw} differs (max {float((out_c.float() - out_b.float()).abs().max())})"
@@ -1724,7 +1724,7 @@ def test_transition_kernel_equals_class_split_launch_and_definition(kind, cin, c
 
     kreal, nreal = P.gemm_dims(kind, tuple(w.shape))
     tps = P.transition_plans(kind, tuple(w.shape), k, st, coarse, 2, inp_cl.shape[-1], nreal, kreal)
-    assert len(tps) == 1 and tps[0].depth == -8 and len(tps[0].classes) == 8
+    assert len(tps) == 1 and tps[0].depth == L.DEPTH_TRANSITION and len(tps[0].classes) == 8
     tp = tps[0]
     out_t = prev.clone() if mode == "accumulate" else torch.full((n, *fine, nout), float("nan"), dtype=tdt, device="cuda")
     st_t = stats_buf()
@@ -1891,9 +1891,9 @@ def test_deep_kernel_matches_definition_and_general_kernel(kind, k, st, cin, cou
         variants.append([pc[min(i, len(pc) - 1)] for pc in per_class])
     if len(classes) > 1:
         cps = P.deep_class_plans(kind, tuple(w.shape), k, st, q, 2, inp_cl.shape[-1], nreal, kreal, n)
-        assert cps and all(pl.classes is not None and pl.depth == -7 for pl in cps)
+        assert cps and all(pl.classes is not None and pl.depth == L.DEPTH_DEEP for pl in cps)
         variants += [[pl] for pl in cps]
-    assert all(pl.depth == -7 for v in variants for pl in v)
+    assert all(pl.depth == L.DEPTH_DEEP for v in variants for pl in v)
     for v in variants:
         tag = " | ".join(f"tile={pl.tile} mt={pl.mtw} nt={pl.nt} ns={pl.nsplit} ck={pl.ck} cls={len(pl.classes or [])}" for pl in v[:1])
         out, st_ = launch(v)
@@ -1940,7 +1940,7 @@ def test_compute_kernel_rejects_what_it_does_not_cover():
     x = torch.zeros(1, *dims, cin, dtype=torch.bfloat16, device="cuda")
     out = torch.zeros(1, *dims, cout, dtype=torch.bfloat16, device="cuda")
     d = H.igemm_desc(pl, H.pack(pl, w, x.dtype), H.tdesc(x), H.tdesc(out))
-    d.depth = -3
+    d.depth = L.DEPTH_COMPUTE
     assert lib.vsseg_igemm(C.byref(d), H.stream()) == L.EINVAL
     assert b"compute kernel" in lib.vsseg_last_error()
 
@@ -1957,7 +1957,7 @@ def test_streaming_kernel_rejects_what_it_does_not_cover():
     x = torch.zeros(1, *dims, cin, dtype=torch.bfloat16, device="cuda")
     out = torch.zeros(1, *dims, cout, dtype=torch.bfloat16, device="cuda")
     d = H.igemm_desc(pl, H.pack(pl, w, x.dtype), H.tdesc(x), H.tdesc(out))
-    d.depth = -2
+    d.depth = L.DEPTH_STREAM
     assert lib.vsseg_igemm(C.byref(d), H.stream()) == L.EINVAL
     assert b"streaming kernel" in lib.vsseg_last_error()
 

@@ -29,6 +29,31 @@ def test_invalid_descriptor_is_rejected_with_message():
     assert b"vsseg_igemm" in lib.vsseg_last_error()
 
 
+def test_kernel_selector_names_match_the_header():
+    """The VSSEG_DEPTH_* values of include/vsseg_hip.h and the DEPTH_* constants of the binding are the same names with the same values."""
+    header = open("include/vsseg_hip.h").read()
+    declared = {name: int(val) for name, val in re.findall(r"#define\s+VSSEG_(DEPTH_[A-Z_]+)\s+\((-\d+)\)", header)}
+    bound = {name: getattr(L, name) for name in dir(L) if name.startswith("DEPTH_")}
+    assert declared == bound and sorted(declared.values()) == list(range(-9, 0)), (declared, bound)
+
+
+def test_depth_that_selects_no_kernel_is_rejected():
+    """A negative depth that is none of the VSSEG_DEPTH_* values is an error that names the value (it used to run the general kernel without prefetch)."""
+    from tests import gpu_harness as H
+    from vs_seg_amd import planner as P
+
+    lib = L.lib()
+    w = (16, 16, 3, 3, 3)
+    pl = P.plan_igemm("conv_fwd", w, P.lattice_classes("conv_fwd", w[2:], (1, 1, 1))[0], (8, 8, 8), 2, kc_pad=16)
+    d = H.igemm_desc(pl, torch.zeros(1), L.Tensor(4096, L.BF16, 16, 16, 1, 8, 8, 8), L.Tensor(8192, L.BF16, 16, 16, 1, 8, 8, 8))
+    for depth in (pl.depth, L.DEPTH_NOPREFETCH):  # the descriptor is valid ...
+        d.depth = depth
+        assert lib.vsseg_igemm_lds_bytes(ctypes.byref(d)) > 0, lib.vsseg_last_error()
+    d.depth = -10
+    assert lib.vsseg_igemm_lds_bytes(ctypes.byref(d)) == L.EINVAL
+    assert b"-10" in lib.vsseg_last_error()
+
+
 @pytest.mark.parametrize("att", [True, False])
 @pytest.mark.parametrize("dt", ["bf16", "fp32"])
 def test_plans_lower_on_cpu(att, dt):

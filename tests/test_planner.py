@@ -11,6 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from vs_seg_amd import _lib as L
 from vs_seg_amd import planner as P
 
 CASES = [
@@ -127,7 +128,6 @@ def test_transition_plans_compute_the_transition_and_mirror_the_kernels_lds(kind
     import ctypes
 
     from tests import gpu_harness as H
-    from vs_seg_amd import _lib as L
 
     k, s, coarse = (3, 3, 3), (2, 2, 2), (4, 8, 8)
     fine = tuple(2 * c for c in coarse)
@@ -148,7 +148,7 @@ def test_transition_plans_compute_the_transition_and_mirror_the_kernels_lds(kind
     plans = P.transition_plans(kind, tuple(w.shape), k, s, coarse, 2, kc, nreal, kreal)
     assert len(plans) == 1
     pl = plans[0]
-    assert pl.depth == -8 and pl.tile == P.TRANSITION_TILE and pl.mtw == 16 and pl.nt == 3 and pl.nsplit == 8 and len(pl.classes) == 8 and pl.ck == kc and pl.nchunks == 1
+    assert pl.depth == L.DEPTH_TRANSITION and pl.tile == P.TRANSITION_TILE and pl.mtw == 16 and pl.nt == 3 and pl.nsplit == 8 and len(pl.classes) == 8 and pl.ck == kc and pl.nchunks == 1
     assert sorted(len(c.taps) for c in pl.classes) == [1, 2, 2, 2, 4, 4, 4, 8] and pl.lds == P.transition_lds_bytes(kc) <= P.LDS_LIMIT
     np.testing.assert_allclose(P.simulate_igemm(pl, xin, w.numpy().reshape(-1), fine), _cl(want), atol=1e-9)
     d = H.igemm_desc(pl, torch.zeros(1), L.Tensor(4096, L.BF16, kc, kc, 1, *coarse), L.Tensor(8192, L.BF16, 48, 48, 1, *fine))
@@ -165,7 +165,6 @@ def test_gather_plans_compute_the_strided_launches_and_mirror_the_kernels_lds(ki
     import ctypes
 
     from tests import gpu_harness as H
-    from vs_seg_amd import _lib as L
 
     k, s = (3, 3, 1), (2, 2, 1)
     fine = (2 * coarse[0], 2 * coarse[1], coarse[2])
@@ -185,14 +184,14 @@ def test_gather_plans_compute_the_strided_launches_and_mirror_the_kernels_lds(ki
     cls = P.lattice_classes(kind, k, s)
     assert len(cls) == 1 and tuple(cls[0].is_) == (2, 2, 1)
     plans = P.gather_plans(kind, tuple(w.shape), cls[0], coarse, 2, kreal, nreal, kreal)
-    assert plans and all(pl.depth == -9 and pl.nchunks == 1 and pl.ck == kreal and pl.tile[1] == 64 * pl.mtw // pl.tile[2] for pl in plans)
+    assert plans and all(pl.depth == L.DEPTH_GATHER and pl.nchunks == 1 and pl.ck == kreal and pl.tile[1] == 64 * pl.mtw // pl.tile[2] for pl in plans)
     for pl in plans:
         assert pl.lds == P.gather_lds_bytes(kreal, pl.nt, pl.tile[2], pl.mtw) <= P.LDS_LIMIT and (kreal, pl.nt, pl.tile[2], pl.mtw) in P.GATHER_SHAPES
         pl.pack_map = P.pack_map(pl, tuple(w.shape))
         np.testing.assert_allclose(P.simulate_igemm(pl, xin, w.numpy().reshape(-1), coarse)[..., :nreal], _cl(want), atol=1e-9)
         d = H.igemm_desc(pl, torch.zeros(1), L.Tensor(4096, L.BF16, kreal, kreal, 1, *fine), L.Tensor(8192, L.BF16, nreal, nreal, 1, *coarse))
         assert L.lib().vsseg_igemm_lds_bytes(ctypes.byref(d)) == pl.lds, L.lib().vsseg_last_error()
-    assert any(pl.depth == -9 for pl in P.candidate_plans(kind, tuple(w.shape), cls[0], coarse, 2, kc_pad=kreal, aux_es=0))
+    assert any(pl.depth == L.DEPTH_GATHER for pl in P.candidate_plans(kind, tuple(w.shape), cls[0], coarse, 2, kc_pad=kreal, aux_es=0))
     assert P.gather_plans(kind, tuple(w.shape), cls[0], coarse, 4, kreal, nreal, kreal) == []  # fp32
 
 
@@ -309,11 +308,11 @@ def test_march_plans_cover_the_benchmark_layers_and_mirror_the_kernel_lds():
         assert pls, (cin, cout)
         for pl in pls:
             lx, tyb, tz = pl.tile
-            assert pl.depth in (-5, -6) and tyb == 64 * pl.mtw // tz and dims[1] % tyb == 0 and dims[2] % tz == 0 and 1 <= lx <= dims[0]
+            assert P.is_march(pl) and tyb == 64 * pl.mtw // tz and dims[1] % tyb == 0 and dims[2] % tz == 0 and 1 <= lx <= dims[0]
             g = cin // 8
-            wbytes = 0 if pl.depth == -6 else ((9 * g + 3) // 4) * pl.nt * 1024  # depth -6: the packed weights live in registers
+            wbytes = 0 if pl.depth == L.DEPTH_MARCH_WREG else ((9 * g + 3) // 4) * pl.nt * 1024  # the packed weights live in registers
             assert pl.lds == wbytes + 4 * (tyb + 2) * tz * g * 16 + 5 * pl.nt * 16 * 4 + 16 <= 160 * 1024
-            assert pl.depth == -5 or (cin, pl.nt, tz, pl.mtw) in P.MARCH_WREG_SHAPES
+            assert pl.depth == L.DEPTH_MARCH or (cin, pl.nt, tz, pl.mtw) in P.MARCH_WREG_SHAPES
             assert pl.ksteps == (9 * g + 3) // 4 and pl.nchunks == 1 and pl.ck == cin
     # outside the domain: strided, 3x3x3, fp32
     assert P.march_plans("conv_fwd", (16, 16, 3, 3, 1), P.lattice_classes("conv_fwd", (3, 3, 1), (2, 2, 1))[0], (192, 64, 128), 2, 16, 16, 16) == []
@@ -339,7 +338,7 @@ def test_chained_launch_plans_cover_the_benchmark_window_and_nothing_else():
     for wshape, kc in [((16, 1, 3, 3, 1), 8), ((16, 16, 3, 3, 1), 16), ((1, 16, 3, 3, 1), 16), ((32, 16, 3, 3, 1), 16), ((32, 32, 3, 3, 1), 32)]:
         dims = (384, 128, 128) if wshape[0] <= 16 else (192, 64, 128)
         pl = P.chain_pack_plan(wshape, dims, 2, kc, 1)
-        assert pl is not None and pl.depth == -5 and pl.nt == (wshape[0] + 15) // 16
+        assert pl is not None and pl.depth == L.DEPTH_MARCH and pl.nt == (wshape[0] + 15) // 16
         assert pl.pack_map.size == ((9 * (kc // 8) + 3) // 4) * pl.nt * 64 * 8
         real = pl.pack_map[pl.pack_map >= 0]
         assert real.size == int(np.prod(wshape)) and len(set(real.tolist())) == real.size  # every weight element exactly once
@@ -355,7 +354,6 @@ def test_deep_class_plans_mirror_the_kernels_lds_request(kind, k, st, cin, cout,
     import ctypes
 
     from tests import gpu_harness as H
-    from vs_seg_amd import _lib as L
 
     lib = L.lib()
     coarse = tuple(f // s for f, s in zip(fine, st))
@@ -368,3 +366,40 @@ def test_deep_class_plans_mirror_the_kernels_lds_request(kind, k, st, cin, cout,
         out = L.Tensor(8192, L.BF16, pl.nt * 16, pl.nt * 16, 1, *fine)
         d = H.igemm_desc(pl, torch.zeros(1), inp, out)
         assert lib.vsseg_igemm_lds_bytes(ctypes.byref(d)) == pl.lds, (pl.tile, pl.mtw, pl.nt, len(pl.classes), lib.vsseg_last_error())
+
+
+def test_kernel_of_names_every_generated_plan():
+    """planner.kernel_of is defined for every plan the candidate generators return (the shapes of the tests above), the generators together reach all seven
+    kernels, and a depth that selects no kernel raises instead of reading as the general kernel."""
+    plans = []
+    c1 = P.lattice_classes("conv_fwd", (3, 3, 1), (1, 1, 1))[0]
+    for cin, cout, dims in [(16, 16, (384, 128, 128)), (32, 16, (384, 128, 128)), (16, 32, (192, 64, 128)), (32, 32, (192, 64, 128)), (64, 32, (192, 64, 128))]:
+        plans += P.candidate_plans("conv_fwd", (cout, cin, 3, 3, 1), c1, dims, 2, kc_pad=cin, aux_es=0, n=4)
+        plans += P.march_plans("conv_fwd", (cout, cin, 3, 3, 1), c1, dims, 2, cin, cout, cin, n=4)
+    plans += P.march_res_plans((32, 16, 3, 3, 1), (32, 16, 1, 1, 1), c1, (192, 64, 128), 2, 16, n=4)
+    c3 = P.lattice_classes("conv_fwd", (3, 3, 3), (1, 1, 1))[0]
+    plans += P.candidate_plans("conv_fwd", (48, 48, 3, 3, 3), c3, (96, 32, 128), 2, kc_pad=48, aux_es=0, n=4)  # (the compute kernel's 4x8x16 tile)
+    plans += P.candidate_plans("conv_fwd", (64, 64, 3, 3, 3), c3, (8, 8, 8), 2, kc_pad=64, aux_es=0)           # (a deep level)
+    plans += P.candidate_plans("conv_fwd", (16, 16, 3, 3, 3), c3, (8, 8, 8), 4, aux_es=4)                      # fp32: the general kernel only
+    for kind, cin, cout, coarse in [("conv_fwd", 16, 16, (3, 32, 4)), ("conv_fwd", 32, 32, (2, 32, 2)), ("convT_dgrad", 32, 16, (2, 32, 4)), ("convT_dgrad", 48, 32, (2, 32, 2))]:
+        wshape = (cout, cin, 3, 3, 1) if kind == "conv_fwd" else (cin, cout, 3, 3, 1)
+        kreal, nreal = P.gemm_dims(kind, wshape)
+        cg = P.lattice_classes(kind, (3, 3, 1), (2, 2, 1))[0]
+        plans += P.gather_plans(kind, wshape, cg, coarse, 2, kreal, nreal, kreal) + P.candidate_plans(kind, wshape, cg, coarse, 2, kc_pad=kreal, aux_es=0)
+    for cin, cout in [(32, 16), (48, 32)]:  # the stride-(2,2,1) transposed convolutions: fused parity classes, streaming and marching
+        sps = P.shuffle_plans("convT_fwd", (cin, cout, 3, 3, 1), (3, 3, 1), (2, 2, 1), (192, 64, 128), 2, cin, cout, cin)
+        assert sps
+        plans += sps + [mp for sp in sps for mp in P.march_shuffle_plans(sp, 4)] + P.march_shuffle_all_plans("convT_fwd", (cin, cout, 3, 3, 1), (3, 3, 1), (2, 2, 1), (192, 64, 128), 2, cin, cout, cin, 4)
+    for kind, cin, cout in [("convT_fwd", 64, 48), ("conv_dgrad", 48, 48)]:
+        wshape = (cin, cout, 3, 3, 3) if kind == "convT_fwd" else (cout, cin, 3, 3, 3)
+        kreal, nreal = P.gemm_dims(kind, wshape)
+        plans += P.transition_plans(kind, wshape, (3, 3, 3), (2, 2, 2), (4, 8, 8), 2, kreal, nreal, kreal)
+        plans += P.class_split_plans(kind, wshape, (3, 3, 3), (2, 2, 2), (4, 8, 8), 2, kreal, nreal, kreal)
+    plans += P.deep_class_plans("convT_fwd", (96, 80, 3, 3, 3), (3, 3, 3), (2, 2, 2), (4, 4, 4), 2, 96, 80, 80, 1)
+    plans += P.folded_candidate_plans("conv_fwd", (1, 16, 3, 3, 1), c1, (8, 8, 16), es=2)
+    kernels = {P.kernel_of(pl) for pl in plans}
+    assert kernels == {"igemm", "sconv", "cconv", "mconv", "dconv", "tconv", "gconv"}, kernels
+    assert all(P.is_march(pl) == (P.kernel_of(pl) == "mconv") for pl in plans)
+    assert any(pl.depth == L.DEPTH_NOPREFETCH for pl in plans) and any(pl.depth > 0 for pl in plans)
+    with pytest.raises(ValueError, match="-10"):
+        P.kernel_of(dataclasses.replace(plans[0], depth=-10))

@@ -35,7 +35,7 @@ def main():
         cands = P.candidate_plans(kind, tuple(w.shape), cls, dims, 2, kc_pad=kc, aux_es=2 if mode == "accumulate" else 0)
         res = []
         if only:
-            cands = [pl for pl in cands if pl.depth == -3]
+            cands = [pl for pl in cands if pl.depth == L.DEPTH_COMPUTE]
         for pl in cands:
             d = H.igemm_desc(pl, H.pack(pl, w, x.dtype), H.tdesc(x), H.tdesc(out), **kw)
             if lib.vsseg_igemm(C.byref(d), H.stream()):
@@ -54,8 +54,8 @@ def main():
         if only:
             print(f"{kind} K={kreal} N={nreal} {dims} x{n} {mode}: compute kernel " + ", ".join(f"{r[0] * 1e3:.1f} us ({tf / r[0]:.0f} TFLOP/s)" for r in res), flush=True)
             continue
-        bg = min((r for r in res if r[1].depth != -3), key=lambda r: r[0])
-        cc = [r for r in res if r[1].depth == -3]
+        bg = min((r for r in res if r[1].depth != L.DEPTH_COMPUTE), key=lambda r: r[0])
+        cc = [r for r in res if r[1].depth == L.DEPTH_COMPUTE]
         print(f"{kind} K={kreal} N={nreal} {dims} {mode}: general best {bg[0]:.3f} ms ({tf / bg[0]:.0f} TFLOP/s, tile={bg[1].tile} nt={bg[1].nt} ck={bg[1].ck} ns={bg[1].nsplit})"
               + (f" | compute kernel {cc[0][0]:.3f} ms ({tf / cc[0][0]:.0f} TFLOP/s)" if cc else " | compute kernel n/a"), flush=True)
 

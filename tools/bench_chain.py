@@ -57,7 +57,7 @@ def case(name, cin, cout, dims, split):
         kreal, nreal = P.gemm_dims("conv_fwd", tuple(w.shape))
         best = (1e9, None, None, None)
         for pl in P.march_plans("conv_fwd", tuple(w.shape), cls, dims, 2, kcp, nreal, kreal, n=N):
-            if inp.c == 1 and pl.depth != -5:
+            if inp.c == 1 and pl.depth != L.DEPTH_MARCH:
                 continue
             pl.pack_map = P.pack_map(pl, tuple(w.shape))
             wp = H.pack(pl, w, torch.bfloat16)
@@ -78,7 +78,7 @@ def case(name, cin, cout, dims, split):
     # packed weights of the chain: nt = 1 marching packs
     def pack1(w, kcp):
         kreal, nreal = P.gemm_dims("conv_fwd", tuple(w.shape))
-        pl = [p_ for p_ in P.march_plans("conv_fwd", tuple(w.shape), cls, dims, 2, kcp, nreal, kreal, n=N) if p_.depth == -5 and p_.nt == 1][0]
+        pl = [p_ for p_ in P.march_plans("conv_fwd", tuple(w.shape), cls, dims, 2, kcp, nreal, kreal, n=N) if p_.depth == L.DEPTH_MARCH and p_.nt == 1][0]
         pl.pack_map = P.pack_map(pl, tuple(w.shape))
         return H.pack(pl, w, torch.bfloat16)
     wpa, wpb = pack1(wa, kc), pack1(wb, cm)
@@ -150,7 +150,7 @@ def case_res(name, dims):
 
     def pack1(w, kcp, nt):
         kr_, nr_ = P.gemm_dims("conv_fwd", tuple(w.shape))
-        pl = [p_ for p_ in P.march_plans("conv_fwd", tuple(w.shape), cls, dims, 2, kcp, nr_, kr_, n=N) if p_.depth == -5 and p_.nt == nt][0]
+        pl = [p_ for p_ in P.march_plans("conv_fwd", tuple(w.shape), cls, dims, 2, kcp, nr_, kr_, n=N) if p_.depth == L.DEPTH_MARCH and p_.nt == nt][0]
         pl.pack_map = P.pack_map(pl, tuple(w.shape))
         return H.pack(pl, w, torch.bfloat16)
     wpa, wpb = pack1(wa, cin, 2), pack1(wb, cm, 2)

@@ -117,7 +117,7 @@ def main():
         best_old = ref_ms
         per_class = []
         for cls in classes:
-            cands = [pl for pl in P.candidate_plans(kind, wshape, cls, q, 2, kc_pad=kc, aux_es=aux_es, n=n) if pl.depth != -7]
+            cands = [pl for pl in P.candidate_plans(kind, wshape, cls, q, 2, kc_pad=kc, aux_es=aux_es, n=n) if pl.depth != L.DEPTH_DEEP]
             tms = [run([pl], out0)[0] for pl in cands]
             per_class.append(min(tms))
         best_old = min(best_old, sum(per_class))

@@ -51,5 +51,5 @@ for kind, wshape, coarse, mode in (("conv_fwd", (16, 16, *K), (192, 64, 128), "s
         if lib.vsseg_igemm(C.byref(d), H.stream()):
             continue
         rows.append((timed(lambda: lib.vsseg_igemm(C.byref(d), H.stream())), pl))
-    for us, pl in sorted(rows, key=lambda r: r[0])[:6] + [r for r in rows if r[1].depth == -9][:8]:
+    for us, pl in sorted(rows, key=lambda r: r[0])[:6] + [r for r in rows if r[1].depth == L.DEPTH_GATHER][:8]:
         print(f"   D={pl.depth:2d} {us:8.1f} us  {gb / us * 1e3:5.2f} TB/s   tile={pl.tile} mtw={pl.mtw} nt={pl.nt} ck={pl.ck} lds={pl.lds}")

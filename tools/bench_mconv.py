@@ -58,7 +58,7 @@ def main():
         cands = P.candidate_plans(kind, tuple(w.shape), cls, dims, 2, kc_pad=kc, aux_es=aux_es, in_split=in_split, n=n)
         ref, rows = None, []
         for pl in cands:
-            if pl.depth not in (-2, -5) and pl is not cands[0]:
+            if pl.depth not in (L.DEPTH_STREAM, L.DEPTH_MARCH) and pl is not cands[0]:
                 continue
             out = out0.clone()
             stats.zero_()

@@ -11,6 +11,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tests import gpu_harness as H  # noqa: E402
 from vs_seg_amd import _lib as L  # noqa: E402
 from vs_seg_amd import planner as P  # noqa: E402
+from vs_seg_amd.engine import fill_wgrad_desc  # noqa: E402
 
 CASES = [(16, 16, (384, 128, 128), 0), (32, 16, (384, 128, 128), 16), (32, 2, (384, 128, 128), 0), (16, 32, (192, 64, 128), 0), (32, 32, (192, 64, 128), 0), (64, 32, (192, 64, 128), 32)]
 TILES = {(16, 16): [(96, 64, 4), (192, 64, 4), (96, 32, 4), (96, 32, 8), (96, 64, 8), (192, 64, 8)], (32, 16): [(96, 64, 4), (192, 64, 4), (96, 32, 4), (192, 64, 2)], (32, 2): [(96, 64, 4), (192, 64, 4), (96, 32, 4)],
@@ -52,13 +53,8 @@ def main():
         dw = torch.zeros(int(np.prod(wshape)), dtype=torch.float32, device="cuda")
         d = L.WgradDesc()
         d.p, d.h, d.cp_valid, d.ch_valid = H.tdesc(p_cl), hd, cout, cin
-        d.q, d.hs, d.ntaps = L.i3(wp.q), L.i3(wp.hs), len(wp.taps)
-        for t, (off, widx) in enumerate(wp.taps):
-            d.tap_off[t][0], d.tap_off[t][1], d.tap_off[t][2] = off
-            d.tap_widx[t] = widx
-        d.ntp = wp.ntp
+        fill_wgrad_desc(d, wp)
         d.dw = dw.data_ptr()
-        d.stride_p, d.stride_h, d.stride_tap = wp.stride_p, wp.stride_h, wp.stride_tap
         d.scratch, d.scratch_elems = scr.data_ptr(), scr.numel()
         nq = n * dims[0] * dims[1] * dims[2]
         gb = 2 * nq * (cout + cin) / 1e9
@@ -66,7 +62,6 @@ def main():
         print(f"== wgrad {name}: {gb:.2f} GB algorithmic, {tf * 1e3:.0f} GFLOP", flush=True)
         hch = (cin + 15) // 16
         best = None
-        d.tile = L.i3(wp.tile)
         for hg in [g for g in (4, 3, 2, 1) if hch % g == 0]:
             for sb in (0, 1):
                 for wpc in (2, 3, 4):

@@ -49,8 +49,8 @@ def main():
         if os.environ.get("VSSEG_BENCH_ALL"):
             for ms, pl in res:
                 print(f"    {ms:.3f} ms tile={pl.tile} nt={pl.nt} ck={pl.ck} ns={pl.nsplit} D={pl.depth}")
-        bg = min((r for r in res if r[1].depth != -2), key=lambda r: r[0])
-        st = [r for r in res if r[1].depth == -2]
+        bg = min((r for r in res if r[1].depth != L.DEPTH_STREAM), key=lambda r: r[0])
+        st = [r for r in res if r[1].depth == L.DEPTH_STREAM]
         res = None
         print(f"{kind} {k} K={kreal} N={nreal} {dims} {mode}: general best {bg[0]:.3f} ms ({gb / bg[0]:.0f} GB/s, tile={bg[1].tile} ck={bg[1].ck} ns={bg[1].nsplit} D={bg[1].depth})"
               + (f" | streaming {st[0][0]:.3f} ms ({gb / st[0][0]:.0f} GB/s)" if st else " | streaming n/a"), flush=True)

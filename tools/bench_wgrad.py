@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tests import gpu_harness as H  # noqa: E402
 from vs_seg_amd import _lib as L  # noqa: E402
 from vs_seg_amd import planner as P  # noqa: E402
+from vs_seg_amd.engine import fill_wgrad_desc  # noqa: E402
 
 
 def main():
@@ -43,13 +44,9 @@ def main():
     scr = torch.zeros(48 * 1024 * 1024, dtype=torch.float32, device="cuda")
     d = L.WgradDesc()
     d.p, d.h, d.cp_valid, d.ch_valid = H.tdesc(p_cl), H.tdesc(h_cl), a.cout, a.cin
-    d.q, d.hs, d.ntaps = L.i3(wp.q), L.i3(wp.hs), len(wp.taps)
-    for t, (off, widx) in enumerate(wp.taps):
-        d.tap_off[t][0], d.tap_off[t][1], d.tap_off[t][2] = off
-        d.tap_widx[t] = widx
-    d.tile, d.ntp = L.i3(tile), wp.ntp
+    fill_wgrad_desc(d, wp)
+    d.tile = L.i3(tile)
     d.dw = dw.data_ptr()
-    d.stride_p, d.stride_h, d.stride_tap = wp.stride_p, wp.stride_h, wp.stride_tap
     d.scratch, d.scratch_elems = scr.data_ptr(), scr.numel()
     hch = (a.cin + 15) // 16
     tiles = a.batch

@@ -18,6 +18,8 @@ STAT_SHARDS = 256
 SEED_INDIRECT = 0x80000000
 EINVAL, ELAUNCH = -1, -2
 ZERO_PADDED = 1  # vsseg_tensor.reserved of a destination whose channels c .. pitch-1 are zero padding
+# VSSEG_DEPTH_*: the negative values of IgemmDesc.depth select the kernel (planner.kernel_of)
+DEPTH_NOPREFETCH, DEPTH_STREAM, DEPTH_COMPUTE, DEPTH_STREAM_SHUFFLE, DEPTH_MARCH, DEPTH_MARCH_WREG, DEPTH_DEEP, DEPTH_TRANSITION, DEPTH_GATHER = -1, -2, -3, -4, -5, -6, -7, -8, -9
 
 
 class Tensor(C.Structure):

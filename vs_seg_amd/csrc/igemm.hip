@@ -108,7 +108,7 @@ static int igemm_prepare(const vsseg_igemm_desc* d, IgemmK& k) {
   VSSEG_CHECK(d->nsplit >= 1 && (d->class_split ? d->nt : d->nsplit * d->nt) * 16 >= d->out.c, "vsseg_igemm: nsplit*nt*16 < cout");
   if (d->class_split) {  // all output-parity classes in one launch: workgroup row = class
     VSSEG_CHECK(d->class_split >= 2 && d->class_split <= 8 && d->nsplit == d->class_split, "vsseg_igemm: class_split must be 2..8 and equal nsplit");
-    VSSEG_CHECK(d->oo[0] == 0 && d->oo[1] == 0 && d->oo[2] == 0 && d->cout_mod == 0 && d->depth >= -1 && !d->out.ptr2 && d->res_mode != VSSEG_RES_GATE,
+    VSSEG_CHECK(d->oo[0] == 0 && d->oo[1] == 0 && d->oo[2] == 0 && d->cout_mod == 0 && d->depth >= VSSEG_DEPTH_NOPREFETCH && !d->out.ptr2 && d->res_mode != VSSEG_RES_GATE,
                 "vsseg_igemm: class_split needs oo = 0, the general kernel (depth >= -1), a one-part output and no gated residual");
     for (int c = 0; c < d->class_split; ++c) {
       VSSEG_CHECK(d->class_ntaps[c] >= 1 && d->class_ntaps[c] <= 8 && d->class_ntaps[c] <= d->ntaps, "vsseg_igemm: class %d has %d taps", c, d->class_ntaps[c]);
@@ -167,7 +167,7 @@ static int igemm_prepare(const vsseg_igemm_desc* d, IgemmK& k) {
   int off = 0;
   k.lds_ktab = off; off += ((d->ksteps * 4 * 4 + 15) / 16) * 16;
   k.lds_epi = off; off += 3 * d->nt * 16 * 4;
-  k.depth = d->depth < 0 ? 0 : (d->depth == 0 ? 1 : (d->depth > 3 ? 3 : d->depth));  // -1: no prefetch (single buffer); 0: default = 1
+  k.depth = d->depth < 0 ? 0 : (d->depth == 0 ? 1 : (d->depth > 3 ? 3 : d->depth));  // VSSEG_DEPTH_NOPREFETCH: single buffer; 0: default = 1
   if (d->nt >= 3 && k.depth < 1) k.depth = 1;  // producer / consumer wave specialisation (igemm_kernel.h) always prefetches
   const int nbuf = k.depth + 1;
   k.lds_w = off; off += k.w_bytes * (d->nchunks > 1 ? nbuf : 1);
@@ -187,63 +187,59 @@ static int igemm_prepare(const vsseg_igemm_desc* d, IgemmK& k) {
   return off;
 }
 
+// The specialised kernels, selected by a VSSEG_DEPTH_* value below VSSEG_DEPTH_NOPREFETCH.  Same contract as the general kernel; outside its domain a kernel fails loudly, never falls back.
+struct ConvKernel {
+  int depth[2];
+  int (*lds_bytes)(const vsseg_igemm_desc*);
+  int (*launch)(const vsseg_igemm_desc*, const void* zeros, hipStream_t);
+};
+static const ConvKernel conv_kernels[] = {
+    {{VSSEG_DEPTH_STREAM, VSSEG_DEPTH_STREAM_SHUFFLE}, vsseg_sconv_lds_bytes, vsseg_sconv_launch},  // streaming (sconv.hip; _SHUFFLE: fused output-parity classes)
+    {{VSSEG_DEPTH_COMPUTE, VSSEG_DEPTH_COMPUTE}, vsseg_cconv_lds_bytes, vsseg_cconv_launch},        // compute-bound (cconv.hip)
+    {{VSSEG_DEPTH_MARCH, VSSEG_DEPTH_MARCH_WREG}, vsseg_mconv_lds_bytes, vsseg_mconv_launch},       // marching streaming (mconv.hip; _WREG: packed weights in registers)
+    {{VSSEG_DEPTH_DEEP, VSSEG_DEPTH_DEEP}, vsseg_dconv_lds_bytes, vsseg_dconv_launch},              // deep levels (dconv.hip: the small launches of levels 3-5 and the stride-2 transitions around them)
+    {{VSSEG_DEPTH_TRANSITION, VSSEG_DEPTH_TRANSITION}, vsseg_tconv_lds_bytes, vsseg_tconv_launch},  // transition (tconv.hip: the eight parity classes of a 3x3x3 stride-(2,2,2) transition between levels 2 and 3 in one launch)
+    {{VSSEG_DEPTH_GATHER, VSSEG_DEPTH_GATHER}, vsseg_gconv_lds_bytes, vsseg_gconv_launch},          // gathering marching (gconv.hip: the stride-(2,2,1) 3x3x1 launches that read the fine level and write the coarse one)
+};
+
+// *row = the specialised kernel of the descriptor, or nullptr: the general kernel (which also reports a null descriptor)
+static int find_kernel(const vsseg_igemm_desc* d, const ConvKernel** row) {
+  *row = nullptr;
+  if (!d || d->depth >= VSSEG_DEPTH_NOPREFETCH) return VSSEG_OK;
+  for (const ConvKernel& k : conv_kernels)
+    if (d->depth == k.depth[0] || d->depth == k.depth[1]) {
+      *row = &k;
+      return VSSEG_OK;
+    }
+  vsseg_set_error("vsseg_igemm: depth %d selects no kernel", d->depth);
+  return VSSEG_EINVAL;
+}
+
 extern "C" int vsseg_igemm_lds_bytes(const vsseg_igemm_desc* d) {
-  if (d && (d->depth == -2 || d->depth == -4)) return vsseg_sconv_lds_bytes(d);
-  if (d && d->depth == -3) return vsseg_cconv_lds_bytes(d);
-  if (d && (d->depth == -5 || d->depth == -6)) return vsseg_mconv_lds_bytes(d);
-  if (d && d->depth == -7) return vsseg_dconv_lds_bytes(d);
-  if (d && d->depth == -8) return vsseg_tconv_lds_bytes(d);
-  if (d && d->depth == -9) return vsseg_gconv_lds_bytes(d);
+  const ConvKernel* row;
+  if (int rc = find_kernel(d, &row)) return rc;
+  if (row) return row->lds_bytes(d);
   IgemmK k;
   return igemm_prepare(d, k);
 }
 
 extern "C" int vsseg_igemm(const vsseg_igemm_desc* d, void* stream) {
-  VSSEG_CHECK(!d || !d->in_gate || d->depth == -5 || d->depth == -6, "vsseg_igemm: the input gate (in_gate) needs a marching-kernel plan (depth -5 / -6)");
-  VSSEG_CHECK(!d || d->res_mode != VSSEG_RES_IN1 || d->depth == -5 || d->depth == -6, "vsseg_igemm: VSSEG_RES_IN1 needs a marching-kernel plan (depth -5 / -6)");
-  VSSEG_CHECK(!d || !d->res_tiles || d->depth == -5 || d->depth == -6, "vsseg_igemm: residual tiles (res_tiles) need a marching-kernel plan (depth -5 / -6)");
-  if (d && (d->depth == -2 || d->depth == -4)) {  // streaming kernel (sconv.hip; -4: fused output-parity classes): fails loudly when the launch is outside its domain, never falls back
-    VSSEG_CHECK(d->in.ptr && d->out.ptr && d->wpack, "vsseg_igemm: null pointer");
-    const void* z = zero_page();
-    VSSEG_CHECK(z, "vsseg_igemm: could not allocate the zero page");
-    return vsseg_sconv_launch(d, z, as_stream(stream));
-  }
-  if (d && d->depth == -3) {  // compute-bound kernel (cconv.hip): same contract — outside its domain is an error
-    VSSEG_CHECK(d->in.ptr && d->out.ptr && d->wpack, "vsseg_igemm: null pointer");
-    const void* z = zero_page();
-    VSSEG_CHECK(z, "vsseg_igemm: could not allocate the zero page");
-    return vsseg_cconv_launch(d, z, as_stream(stream));
-  }
-  if (d && (d->depth == -5 || d->depth == -6)) {  // marching streaming kernel (mconv.hip; -6: packed weights in registers): same contract
-    VSSEG_CHECK(d->in.ptr && d->out.ptr && d->wpack, "vsseg_igemm: null pointer");
-    const void* z = zero_page();
-    VSSEG_CHECK(z, "vsseg_igemm: could not allocate the zero page");
-    return vsseg_mconv_launch(d, z, as_stream(stream));
-  }
-  if (d && d->depth == -7) {  // deep-level kernel (dconv.hip: the small launches of levels 3-5 and the stride-2 transitions around them): same contract
-    VSSEG_CHECK(d->in.ptr && d->out.ptr && d->wpack, "vsseg_igemm: null pointer");
-    const void* z = zero_page();
-    VSSEG_CHECK(z, "vsseg_igemm: could not allocate the zero page");
-    return vsseg_dconv_launch(d, z, as_stream(stream));
-  }
-  if (d && d->depth == -8) {  // transition kernel (tconv.hip: the eight parity classes of a 3x3x3 stride-(2,2,2) transition between levels 2 and 3 in one launch): same contract
-    VSSEG_CHECK(d->in.ptr && d->out.ptr && d->wpack, "vsseg_igemm: null pointer");
-    const void* z = zero_page();
-    VSSEG_CHECK(z, "vsseg_igemm: could not allocate the zero page");
-    return vsseg_tconv_launch(d, z, as_stream(stream));
-  }
-  if (d && d->depth == -9) {  // gathering marching kernel (gconv.hip: the stride-(2,2,1) 3x3x1 launches that read the fine level and write the coarse one): same contract
-    VSSEG_CHECK(d->in.ptr && d->out.ptr && d->wpack, "vsseg_igemm: null pointer");
-    const void* z = zero_page();
-    VSSEG_CHECK(z, "vsseg_igemm: could not allocate the zero page");
-    return vsseg_gconv_launch(d, z, as_stream(stream));
-  }
+  const bool march = d && (d->depth == VSSEG_DEPTH_MARCH || d->depth == VSSEG_DEPTH_MARCH_WREG);
+  VSSEG_CHECK(!d || !d->in_gate || march, "vsseg_igemm: the input gate (in_gate) needs a marching-kernel plan (depth -5 / -6)");
+  VSSEG_CHECK(!d || d->res_mode != VSSEG_RES_IN1 || march, "vsseg_igemm: VSSEG_RES_IN1 needs a marching-kernel plan (depth -5 / -6)");
+  VSSEG_CHECK(!d || !d->res_tiles || march, "vsseg_igemm: residual tiles (res_tiles) need a marching-kernel plan (depth -5 / -6)");
+  const ConvKernel* row;
+  if (int rc = find_kernel(d, &row)) return rc;
+  VSSEG_CHECK(d && d->in.ptr && d->out.ptr && d->wpack, "vsseg_igemm: null pointer");
+  const void* zeros = zero_page();
+  VSSEG_CHECK(zeros, "vsseg_igemm: could not allocate the zero page");
+  if (row) return row->launch(d, zeros, as_stream(stream));
   IgemmK k;
   int lds = igemm_prepare(d, k);
   if (lds < 0) return lds;
-  k.zeros = zero_page();
+  k.zeros = zeros;
   k.fxflag = vsseg_fx_flag();
-  VSSEG_CHECK(k.zeros && k.fxflag, "vsseg_igemm: could not allocate the zero page / flag word");
+  VSSEG_CHECK(k.fxflag, "vsseg_igemm: could not allocate the flag word");
   VSSEG_CHECK(k.total_tiles > 0 && k.total_tiles < (1ll << 31), "vsseg_igemm: bad tile count");
   k.tiles = tile_table(k, as_stream(stream));
   VSSEG_CHECK(k.tiles, "vsseg_igemm: could not allocate the tile table");

@@ -123,6 +123,33 @@ class _Slot:
         self.kind, self.name = kind, name
 
 
+def fill_igemm_desc(d: L.IgemmDesc, pl: P.IgemmPlan):
+    """Everything of a launch descriptor that its plan decides (the tensors, the packed weights and the epilogue are the caller's)."""
+    d.q, d.is_, d.os, d.oo = L.i3(pl.q), L.i3(pl.cls.is_), L.i3(pl.cls.os), L.i3(pl.cls.oo)
+    d.ntaps = pl.ntaps
+    for t, (off, _) in enumerate(pl.cls.taps):
+        d.tap_off[t][0], d.tap_off[t][1], d.tap_off[t][2] = off
+    d.tile = L.i3(pl.tile)
+    d.mtw, d.nt, d.nsplit, d.ck, d.nchunks, d.ksteps, d.depth = pl.mtw, pl.nt, pl.nsplit, pl.ck, pl.nchunks, pl.ksteps, pl.depth
+    d.res_tiles = pl.res_tiles
+    if P.is_shuffle(pl):  # fused output-parity classes: output channel tile t is class t, its channels are the real channels 0..nc-1
+        d.cout_mod = pl.nc
+    d.class_split = len(pl.classes) if pl.classes is not None else 0
+    for s_, c_ in enumerate(pl.classes or ()):  # workgroup row s_ = lattice class s_: its output offset and its taps (indices into the union tap table above)
+        d.class_oo[s_][0], d.class_oo[s_][1], d.class_oo[s_][2] = c_.oo
+        d.class_ntaps[s_] = len(c_.taps)
+        for i, t in enumerate(pl.class_taps(s_)):
+            d.class_tap[s_][i] = t
+
+
+def fill_wgrad_desc(d: L.WgradDesc, wg: P.WgradPlan):
+    """The geometry of a weight-gradient launch: lattice, taps, tile and the strides of the weight tensor."""
+    d.q, d.hs, d.ntaps = L.i3(wg.q), L.i3(wg.hs), len(wg.taps)
+    for t, (off, widx) in enumerate(wg.taps):
+        d.tap_off[t][0], d.tap_off[t][1], d.tap_off[t][2] = off
+        d.tap_widx[t] = widx
+    d.tile, d.ntp = L.i3(wg.tile), wg.ntp
+    d.stride_p, d.stride_h, d.stride_tap = wg.stride_p, wg.stride_h, wg.stride_tap
 
 
 class Plan:
@@ -268,9 +295,9 @@ class Plan:
                 if self.tune:
                     cands = P.candidate_plans(kind, Lr.wshape, cls, q, eng.es, kc_pad=kc_pad, aux_es=aux_es, in_split=in_split, n=self.n)
                     if eng.deep == "0":
-                        cands = [pl for pl in cands if pl.depth != -7]
-                    elif eng.deep == "force" and any(pl.depth == -7 for pl in cands):
-                        cands = [pl for pl in cands if pl.depth == -7]
+                        cands = [pl for pl in cands if P.kernel_of(pl) != "dconv"]
+                    elif eng.deep == "force" and any(P.kernel_of(pl) == "dconv" for pl in cands):
+                        cands = [pl for pl in cands if P.kernel_of(pl) == "dconv"]
                 else:
                     cands = [P.plan_igemm(kind, Lr.wshape, cls, q, eng.es, kc_pad=kc_pad, aux_es=aux_es, in_split=in_split)]
                     if eng.deep == "force":  # untuned lowering with the deep-level kernel wherever it is offered (tests: the whole network through csrc/dconv.hip's domain)
@@ -371,24 +398,6 @@ class Plan:
         self._tune_gflat = None
         _tune_cache_save()
 
-    @staticmethod
-    def _fill_desc(d: L.IgemmDesc, pl: P.IgemmPlan):
-        d.q, d.is_, d.os, d.oo = L.i3(pl.q), L.i3(pl.cls.is_), L.i3(pl.cls.os), L.i3(pl.cls.oo)
-        d.ntaps = pl.ntaps
-        for t, (off, _) in enumerate(pl.cls.taps):
-            d.tap_off[t][0], d.tap_off[t][1], d.tap_off[t][2] = off
-        d.tile = L.i3(pl.tile)
-        d.mtw, d.nt, d.nsplit, d.ck, d.nchunks, d.ksteps, d.depth = pl.mtw, pl.nt, pl.nsplit, pl.ck, pl.nchunks, pl.ksteps, pl.depth
-        d.res_tiles = pl.res_tiles
-        if P.is_shuffle(pl):  # fused output-parity classes: output channel tile t is class t, its channels are the real channels 0..nc-1
-            d.cout_mod = pl.nc
-        d.class_split = len(pl.classes) if pl.classes is not None else 0
-        for s_, c_ in enumerate(pl.classes or ()):  # workgroup row s_ = lattice class s_: its output offset and its taps (indices into the union tap table above)
-            d.class_oo[s_][0], d.class_oo[s_][1], d.class_oo[s_][2] = c_.oo
-            d.class_ntaps[s_] = len(c_.taps)
-            for i, t in enumerate(pl.class_taps(s_)):
-                d.class_tap[s_][i] = t
-
     def _choose(self, ch: _Choice, d: L.IgemmDesc) -> P.IgemmPlan:
         """Tuned-plan cache lookup (same launch signature measured before, in this process or in a cache file), else measure."""
         p0 = ch.cands[0]
@@ -423,7 +432,7 @@ class Plan:
             m = torch.from_numpy(np.where(pl.pack_map >= 0, pl.pack_map + ch.woff, -1).astype(np.int32)).to(eng.device)
             wp = torch.empty(m.numel(), dtype=eng.tdtype, device=eng.device)
             L.check(lib.vsseg_gather_cast(eng.flat.data_ptr(), m.data_ptr(), None, wp.data_ptr(), m.numel(), L.BF16 if eng.es == 2 else L.F32, stream), "gather_cast")
-            self._fill_desc(d, pl)
+            fill_igemm_desc(d, pl)
             d.wpack = wp.data_ptr()
             if pl.res_tiles:
                 mr = torch.from_numpy(np.where(pl.pack_map_res >= 0, pl.pack_map_res + ch.woff_res, -1).astype(np.int32)).to(eng.device)
@@ -491,7 +500,7 @@ class Plan:
         p0 = alt.cands[0]
         nb = kw.get("nb") or self.n
         if not self.tune:
-            return p0.depth == -7 or nb * p0.q[0] * p0.q[1] * p0.q[2] <= self.CLASS_SPLIT_MAX_VOXELS
+            return P.kernel_of(p0) == "dconv" or nb * p0.q[0] * p0.q[1] * p0.q[2] <= self.CLASS_SPLIT_MAX_VOXELS
         if alt.chosen is not None or chs[0].chosen is not None:  # a further launch of the same op (another sample): same decision
             return alt.chosen is not None
         key = (f"use_cs|{p0.kind}|w{alt.wshape}|q{p0.q}|n{nb}|es{self.eng.es}|kc{p0.kc}|acc{int(kw.get('accumulate', 0))}|res{int(kw.get('res_mode', 0))}"
@@ -560,7 +569,7 @@ class Plan:
                 ch.probe_plan = pl
             else:
                 self._register(ch, pl)
-        self._fill_desc(d, pl)
+        fill_igemm_desc(d, pl)
         if not probe:
             self._wpack_fixups.append((d, ch.map_off))
             if pl.res_tiles:
@@ -587,7 +596,7 @@ class Plan:
         lst.append([self.eng.lib.vsseg_igemm, [C.byref(d)], meta])
 
     def _march_cands(self, ch: _Choice, Lr: Layer) -> List[P.IgemmPlan]:
-        """The marching-kernel plans (depth -5) of a stride-1 3x3x1 forward launch: those among its candidates when the autotuner listed them, else
+        """The marching-kernel plans of a stride-1 3x3x1 forward launch: those among its candidates when the autotuner listed them, else
         planner.march_plans' deterministic list (the untuned lowering then takes the first one)."""
         got = [pl for pl in ch.cands if P.is_march(pl)]
         if got or len(ch.cands) != 1:
@@ -607,7 +616,7 @@ class Plan:
             return None  # (two real channels: the gradient of the logits, csrc/mconv.hip CC = 2)
         got = getattr(ch, "_compact", None)
         if got is None:
-            cands = [pl for pl in self._march_cands(ch, Lr) if pl.depth == -5]
+            cands = [pl for pl in self._march_cands(ch, Lr) if pl.depth == L.DEPTH_MARCH]
             got = ch._compact = _Choice(cands, ch.woff, wshape=ch.wshape, wshape2=ch.wshape2, woff2=ch.woff2) if cands else False  # (a merged residual convolution stays merged)
             if got:
                 got._is_compact, got._compact = True, got  # (asked again with the new choice: itself)
@@ -625,19 +634,11 @@ class Plan:
     @staticmethod
     def _igemm_name(pl: P.IgemmPlan, inp: L.Tensor) -> str:
         """Kernel group of a convolution launch in the profiles: which of the kernels its plan runs on."""
-        if pl.depth in (-2, -4):
-            return f"sconv<bf16,{pl.nt}>"
-        if pl.depth == -3:
-            return f"cconv<bf16,{pl.nt}>"
-        if P.is_march(pl):
-            return f"mconv<bf16,{pl.nt}>"
-        if pl.depth == -7:
-            return f"dconv<bf16,{pl.mtw},{pl.nt}>"
-        if pl.depth == -8:
-            return f"tconv<bf16,{pl.ck // 8}>"
-        if pl.depth == -9:
-            return f"gconv<bf16,{pl.nt}>"
-        return f"igemm<{'bf16' if inp.dtype == L.BF16 else 'f32'},{pl.nt},{pl.mtw}>"
+        kernel = P.kernel_of(pl)
+        if kernel == "igemm":
+            return f"igemm<{'bf16' if inp.dtype == L.BF16 else 'f32'},{pl.nt},{pl.mtw}>"
+        args = {"dconv": f"{pl.mtw},{pl.nt}", "tconv": f"{pl.ck // 8}"}.get(kernel, f"{pl.nt}")
+        return f"{kernel}<bf16,{args}>"
 
     def _ew_meta(self, name: str, level: int, passes_c: int, dtype_es: Optional[int] = None) -> dict:
         """Launch metadata of a streaming kernel: algorithmic bytes = (channels read + written per voxel, summed over its tensor
@@ -1009,15 +1010,10 @@ class Plan:
                 d.p, d.h, d.cp_valid, d.ch_valid = xin, dy, Lr.cin, Lr.cout
             else:
                 d.p, d.h, d.cp_valid, d.ch_valid = (dy_compact if pc2 else dy), xin, Lr.cout, Lr.cin
-            d.q, d.hs, d.ntaps = L.i3(wg.q), L.i3(wg.hs), len(wg.taps)
-            for t, (off, widx) in enumerate(wg.taps):
-                d.tap_off[t][0], d.tap_off[t][1], d.tap_off[t][2] = off
-                d.tap_widx[t] = widx
-            d.tile, d.ntp = L.i3(wg.tile), wg.ntp
+            fill_wgrad_desc(d, wg)
             d.dw = self._gp(Lr.wkey)
             if bias_grad and not Lr.transposed:  # bias gradient = sum of dY, reduced inside the weight-gradient kernel (P = dY)
                 d.dbias_p = self._gp(Lr.bkey)
-            d.stride_p, d.stride_h, d.stride_tap = wg.stride_p, wg.stride_h, wg.stride_tap
             hch = (d.ch_valid + 15) // 16
             tiles = self.n
             for a in range(3):
@@ -1574,14 +1570,14 @@ class Engine:
         self.res1_fuse = True  # 1-channel residual conv computed inside bn_act_fwd (training)
         self.tune_reps = int(os.environ.get("VSSEG_TUNE_REPS", "5"))  # timed launches per candidate plan (best of)
         self.class_split = True  # all parity classes of the stride-(2,2,2) transitions as one launch of the general kernel (planner.class_split_plans), where that measures faster
-        self.fuse_classes = not dry_run  # output-parity classes of the stride-(2,2,1) level transitions as one launch (depth -4)
+        self.fuse_classes = not dry_run  # output-parity classes of the stride-(2,2,1) level transitions as one launch (DEPTH_STREAM_SHUFFLE)
         self.keepmask = True  # dropout keep-masks stored by the forward (1 bit per element) instead of regenerated twice in backward
         self.compute_wgrad = os.environ.get("VSSEG_COMPUTE_WGRAD", "1") != "0"  # A/B switch of round 6: the compute weight-gradient kernel (csrc/cwgrad.hip) as a candidate for the 3x3x3 layers of levels 2-3
         self.wide_dpre = os.environ.get("VSSEG_WIDE_DPRE", "1") != "0"  # A/B switch of round 6: 16-channel rows for d(pre-sigmoid) of the 3x3x3 sigmoid convolutions (compute-kernel data gradient)
         self.early_res_wgrad = os.environ.get("VSSEG_EARLY_RES_WGRAD", "late")  # round 6, where the first unit's 1x1x1 residual-convolution weight gradient runs: "late" = with the late launches (next line), "1" = with the unit's last block, "0" = last on the side stream
         self.late_wgrad = int(os.environ.get("VSSEG_LATE_WGRAD", "1"))  # the last N tile / marching / compute weight-gradient launches run at the end of the main stream's list (see the end of the backward lowering)
         self.bound_forks = os.environ.get("VSSEG_BOUND_FORKS", "1") != "0"  # round 6: the side stream forks on events bound to the main-stream kernels' own completion (no marker packets); 0: hipEventRecord per fork
-        self.transition = os.environ.get("VSSEG_TRANSITION", "1") != "0"  # A/B switch of round 6: the level 2 <-> 3 transition kernel (csrc/tconv.hip, depth -8)
+        self.transition = os.environ.get("VSSEG_TRANSITION", "1") != "0"  # A/B switch of round 6: the level 2 <-> 3 transition kernel (csrc/tconv.hip, DEPTH_TRANSITION)
         self.narrow_fwd = os.environ.get("VSSEG_NARROW_FWD", "1") != "0"  # A/B switch of round 6: the C -> 1 attention convolutions of levels 0-1 on the vector ALUs (csrc/nconv.hip)
         self.narrow_wgrad = True  # weight gradients of the 1-channel-input / 1-channel-output convolutions as bandwidth reductions
         self.gate_fuse = True  # attention-gate backward fused into the attention conv's data gradient
@@ -1590,7 +1586,7 @@ class Engine:
         self.chain = os.environ.get("VSSEG_CHAIN", "1")  # inference: pairs of 3x3x1 convolutions as one launch, the tensor between them in LDS (csrc/chain.hip); "0": off, "l0": level 0 only
         self.compact_c1 = not dry_run  # one-real-channel convolution inputs read compact by the marching kernel (csrc/mconv.hip C1)
         self.resn = not dry_run  # forward: the unit's 1x1x1 residual convolution as extra output tiles of its first 3x3x1 convolution
-        # the deep-level kernel (csrc/dconv.hip, plans with depth -7) on the small launches of levels 3-5: "1" = a candidate the tuner measures, "0" = off, "force" = every launch
+        # the deep-level kernel (csrc/dconv.hip, DEPTH_DEEP plans) on the small launches of levels 3-5: "1" = a candidate the tuner measures, "0" = off, "force" = every launch
         # it is offered for runs on it (the untuned lowering then too: how the tests send a whole network through it)
         self.deep = os.environ.get("VSSEG_DEEP", "1")
         self.march_shuffle = True  # marching variants of the fused-parity-classes launch of the level-1 -> level-0 transposed convolution as tuner candidates

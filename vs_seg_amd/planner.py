@@ -23,6 +23,8 @@ from typing import Optional,  List, Sequence, Tuple
 
 import numpy as np
 
+from ._lib import DEPTH_COMPUTE, DEPTH_DEEP, DEPTH_GATHER, DEPTH_MARCH, DEPTH_MARCH_WREG, DEPTH_NOPREFETCH, DEPTH_STREAM, DEPTH_STREAM_SHUFFLE, DEPTH_TRANSITION
+
 LDS_LIMIT = 160 * 1024
 
 
@@ -141,14 +143,14 @@ def igemm_halo_bytes(tile, is_, taps, ck, es):
 def igemm_lds_bytes(tile, is_, taps, ck, ksteps, nt, mtw, es, nchunks=1, aux_es=4, depth=1):
     """Mirror of igemm_prepare() in csrc/igemm.hip: tap table | epilogue constants | weights (x2 when streamed) | 2 halo buffers | aux | coordinate tables."""
     w = ksteps * nt * 64 * 8 * es
-    nbuf = max(depth, 0) + 1  # depth -1: no prefetch, single buffer
+    nbuf = max(depth, 0) + 1  # DEPTH_NOPREFETCH: single buffer
     aux = nbuf * round_up(64 * mtw * nt * 16 * aux_es + 64 * mtw * 4, 1024) if (aux_es and 64 * mtw * nt * aux_es <= (12 if mtw == 8 else 8) * 256) else 0  # DMA-prefetched residual / accumulate tile (AMAX pieces per thread) + gate floats
     hb = igemm_halo_bytes(tile, is_, taps, ck, es)
     tables = ((0 if nt >= 3 else 2 * ((hb // 16 + 255) // 256)) + (64 * mtw + 255) // 256) * 1024  # per-thread tables of the DMA pieces (nt <= 2 only) + tile-voxel coordinates
     return round_up(ksteps * 16, 16) + 3 * nt * 16 * 4 + w * (nbuf if nchunks > 1 else 1) + nbuf * round_up(hb, 1024) + aux + tables  # ring buffers padded to whole 1 KiB DMA instructions
 
 
-# ---- streaming kernel (csrc/sconv.hip): depth -2 ------------------------------------------------------------------------
+# ---- streaming kernel (csrc/sconv.hip): DEPTH_STREAM ------------------------------------------------------------------------
 def stream_mt(kc, ntaps) -> int:
     """M-tiles per wave of the streaming kernel (sc_mt() in csrc/sconv.hip): tile = (2 * mt, 8, 4)."""
     return 2 if (kc >= 64 and ntaps == 9) else 4
@@ -185,30 +187,41 @@ def stream_lds_bytes(kc, nt, ntaps):
 
 
 def stream_plan(kind, wshape, cls, q, es, kc, nreal, kreal) -> Optional["IgemmPlan"]:
-    """The depth -2 candidate: the compile-time-geometry streaming kernel on the launches it covers (stride-1 3x3x1 / 1x1x1 bf16,
+    """The DEPTH_STREAM candidate: the compile-time-geometry streaming kernel on the launches it covers (stride-1 3x3x1 / 1x1x1 bf16,
     the instantiated (input channels, output tiles, taps) of STREAM_SHAPES — up to 64 channels either side, up to 96 for the 1x1x1 launches of level 2 —, extents
     divisible by the 8x8x4 tile)."""
     if not stream_eligible(cls, q, kc, nreal, es):
         return None
     nt = (nreal + 15) // 16
     ntaps = len(cls.taps)
-    return IgemmPlan(kind, cls, tuple(q), kc, nreal, kreal, stream_tile(kc, ntaps), stream_mt(kc, ntaps), nt, 1, kc, 1, (ntaps * (kc // 8) + 3) // 4, stream_lds_bytes(kc, nt, ntaps), -2)
+    return IgemmPlan(kind, cls, tuple(q), kc, nreal, kreal, stream_tile(kc, ntaps), stream_mt(kc, ntaps), nt, 1, kc, 1, (ntaps * (kc // 8) + 3) // 4, stream_lds_bytes(kc, nt, ntaps), DEPTH_STREAM)
 
 
-# ---- marching streaming kernel (csrc/mconv.hip): depth -5 ------------------------------------------------------------------
+# ---- marching streaming kernel (csrc/mconv.hip): DEPTH_MARCH ------------------------------------------------------------------
 # (input channels, 16-channel output tiles, TZ, M-tiles per wave) instantiated by mconv.hip; rows per workgroup TYB = 64 * mt / tz
 MARCH_SHAPES = {(16, 1, 4, 2), (16, 1, 8, 4), (16, 2, 4, 2), (16, 2, 8, 4), (32, 1, 4, 2), (32, 2, 4, 2), (8, 1, 8, 4), (8, 2, 8, 4), (8, 1, 8, 8), (8, 2, 8, 8), (8, 1, 4, 8), (8, 2, 4, 8), (8, 1, 4, 4), (8, 2, 4, 4), (16, 1, 4, 8), (16, 1, 4, 4), (16, 2, 4, 8), (16, 2, 4, 4), (16, 2, 8, 8), (16, 1, 8, 8),
                 (32, 1, 2, 4), (32, 1, 4, 4), (32, 1, 2, 2), (32, 2, 4, 4), (32, 2, 2, 4), (32, 2, 2, 2), (32, 4, 4, 4), (32, 4, 2, 2), (32, 4, 4, 2),
                 (64, 2, 2, 2), (64, 2, 2, 1), (64, 1, 2, 2), (64, 1, 2, 1)}
-# ... of which these also exist with the packed weights in registers instead of LDS (depth -6; csrc/mconv.hip WREG, the MC_W entries)
+# ... of which these also exist with the packed weights in registers instead of LDS (DEPTH_MARCH_WREG; csrc/mconv.hip WREG, the MC_W entries)
 MARCH_WREG_SHAPES = {(16, 2, 4, 2), (16, 2, 8, 4), (32, 1, 4, 2), (32, 2, 4, 2), (32, 1, 2, 4), (32, 1, 4, 4), (32, 1, 2, 2), (32, 2, 4, 4), (32, 2, 2, 4), (32, 2, 2, 2), (32, 4, 2, 2), (32, 4, 4, 2),
                      (64, 2, 2, 2), (64, 2, 2, 1), (64, 1, 2, 2), (64, 1, 2, 1)}
 MARCH_RING = 4
-MARCH_DEPTHS = (-5, -6)
+MARCH_DEPTHS = (DEPTH_MARCH, DEPTH_MARCH_WREG)
+_KERNEL_OF = {DEPTH_STREAM: "sconv", DEPTH_STREAM_SHUFFLE: "sconv", DEPTH_COMPUTE: "cconv", DEPTH_MARCH: "mconv", DEPTH_MARCH_WREG: "mconv", DEPTH_DEEP: "dconv", DEPTH_TRANSITION: "tconv",
+              DEPTH_GATHER: "gconv"}
+
+
+def kernel_of(pl) -> str:
+    """The kernel a plan's depth selects (the conv_kernels table of csrc/igemm.hip): "sconv", "cconv", "mconv", "dconv", "tconv", "gconv" or "igemm", the general kernel."""
+    if pl.depth >= DEPTH_NOPREFETCH:
+        return "igemm"
+    if pl.depth not in _KERNEL_OF:
+        raise ValueError(f"depth {pl.depth} selects no kernel")
+    return _KERNEL_OF[pl.depth]
 
 
 def is_march(pl) -> bool:
-    return pl.depth in MARCH_DEPTHS
+    return kernel_of(pl) == "mconv"
 
 
 def march_lds_bytes(kc, nt, tz, mt, wreg=False):
@@ -218,7 +231,7 @@ def march_lds_bytes(kc, nt, tz, mt, wreg=False):
 
 
 def march_plans(kind, wshape, cls, q, es, kc, nreal, kreal, n=1) -> List["IgemmPlan"]:
-    """The depth -5 candidates: the marching kernel (every input voxel fetched once: a workgroup owns a column of `tyb` rows x `tz` slices and
+    """The DEPTH_MARCH candidates: the marching kernel (every input voxel fetched once: a workgroup owns a column of `tyb` rows x `tz` slices and
     walks along x with a ring of planes in LDS) on the stride-1 3x3x1 bf16 launches it is instantiated for.  tile = (x steps per workgroup,
     rows per workgroup, tz); x is cut into segments so that the launch has about two (or one) rounds of 512 resident workgroups."""
     offs = [tuple(t[0]) for t in cls.taps]
@@ -234,15 +247,15 @@ def march_plans(kind, wshape, cls, q, es, kc, nreal, kreal, n=1) -> List["IgemmP
         for target in (512, 1024):
             nxs = max(1, min(q[0] // 8, -(-target // cols)))
             lx = -(-q[0] // nxs)
-            pl = IgemmPlan(kind, cls, tuple(q), kc, nreal, kreal, (lx, tyb, tz), mt, nt, 1, kc, 1, (9 * (kc // 8) + 3) // 4, march_lds_bytes(kc, nt, tz, mt), -5)
+            pl = IgemmPlan(kind, cls, tuple(q), kc, nreal, kreal, (lx, tyb, tz), mt, nt, 1, kc, 1, (9 * (kc // 8) + 3) // 4, march_lds_bytes(kc, nt, tz, mt), DEPTH_MARCH)
             if not any(o.tile == pl.tile and o.mtw == pl.mtw for o in out):
                 out.append(pl)
                 if (c, t, tz, mt) in MARCH_WREG_SHAPES:  # the same launch with the packed weights in registers (LDS bandwidth back to the operand reads)
-                    out.append(dataclasses.replace(pl, depth=-6, lds=march_lds_bytes(kc, nt, tz, mt, True)))
+                    out.append(dataclasses.replace(pl, depth=DEPTH_MARCH_WREG, lds=march_lds_bytes(kc, nt, tz, mt, True)))
     return out
 
 
-# ---- gathering marching kernel (csrc/gconv.hip): depth -9 ------------------------------------------------------------------
+# ---- gathering marching kernel (csrc/gconv.hip): DEPTH_GATHER ------------------------------------------------------------------
 # (input channels, 16-channel output tiles, tz, M-tiles per wave): gc_table of csrc/gconv.hip
 GATHER_SHAPES = {(16, 1, 4, 2), (16, 1, 8, 4), (16, 1, 4, 4), (16, 2, 4, 2), (16, 2, 8, 4), (16, 2, 4, 4), (32, 2, 2, 1), (32, 2, 4, 2), (32, 3, 2, 1), (32, 3, 4, 2)}
 
@@ -256,7 +269,7 @@ def gather_lds_bytes(kc, nt, tz, mt) -> int:
 
 
 def gather_plans(kind, wshape, cls, q, es, kc, nreal, kreal, n=1) -> List["IgemmPlan"]:
-    """The depth -9 candidates: the gathering marching kernel on the stride-(2,2,1) 3x3x1 bf16 launches that read the fine level and write the coarse one (strided convolution,
+    """The DEPTH_GATHER candidates: the gathering marching kernel on the stride-(2,2,1) 3x3x1 bf16 launches that read the fine level and write the coarse one (strided convolution,
     data gradient of a transposed convolution): a workgroup owns a column of `tyb` coarse rows x `tz` slices and walks along x with a ring of FINE planes in LDS.
     tile = (x steps per workgroup, coarse rows per workgroup, tz)."""
     offs = [tuple(t[0]) for t in cls.taps]
@@ -272,7 +285,7 @@ def gather_plans(kind, wshape, cls, q, es, kc, nreal, kreal, n=1) -> List["Igemm
         for target in (512, 1024):
             nxs = max(1, min(q[0] // 8, -(-target // cols)))
             lx = -(-q[0] // nxs)
-            pl = IgemmPlan(kind, cls, tuple(q), kc, nreal, kreal, (lx, tyb, tz), mt, nt, 1, kc, 1, (9 * (kc // 8) + 3) // 4, gather_lds_bytes(kc, nt, tz, mt), -9)
+            pl = IgemmPlan(kind, cls, tuple(q), kc, nreal, kreal, (lx, tyb, tz), mt, nt, 1, kc, 1, (9 * (kc // 8) + 3) // 4, gather_lds_bytes(kc, nt, tz, mt), DEPTH_GATHER)
             if not any(o.tile == pl.tile and o.mtw == pl.mtw for o in out):
                 out.append(pl)
     return out
@@ -298,11 +311,11 @@ def chain_plan(cin: int, compact: bool, q, n: int = 1, cmid: int = 16) -> Option
 
 
 def chain_pack_plan(wshape, q, es, kc, n=1) -> Optional["IgemmPlan"]:
-    """The packed-weight layout a chained launch reads for one of its two convolutions: that of a marching plan (depth -5) holding all output tiles."""
+    """The packed-weight layout a chained launch reads for one of its two convolutions: that of a marching plan (DEPTH_MARCH) holding all output tiles."""
     cls = lattice_classes("conv_fwd", tuple(wshape[2:]), (1, 1, 1))[0]
     kreal, nreal = gemm_dims("conv_fwd", wshape)
     for pl in march_plans("conv_fwd", wshape, cls, q, es, kc, nreal, kreal, n):
-        if pl.depth == -5 and pl.nt == (nreal + 15) // 16:
+        if pl.depth == DEPTH_MARCH and pl.nt == (nreal + 15) // 16:
             pl.pack_map = pack_map(pl, wshape)
             return pl
     return None
@@ -413,7 +426,7 @@ def residual_dgrad_pack_plan(wshape, q) -> "IgemmPlan":
     return pl
 
 
-# ---- fused output-parity classes on the streaming kernel ("pixel shuffle"): depth -4 ----------------------------------------
+# ---- fused output-parity classes on the streaming kernel ("pixel shuffle"): DEPTH_STREAM_SHUFFLE ----------------------------------------
 def shuffle_plans(kind, wshape, kernel, stride, q, es, kc, nreal, kreal) -> Optional[List["IgemmPlan"]]:
     """The output-parity classes of a stride-(2,2,1) 3x3x1 transposed convolution / data gradient fused into streaming-kernel launches: a
     stride-1 convolution on the coarse lattice over the 2x2x1 neighbourhood (+0 / +1) whose 4 channel tiles are parity classes — channel tile
@@ -437,7 +450,7 @@ def shuffle_plans(kind, wshape, kernel, stride, q, es, kc, nreal, kreal) -> Opti
     plans = []
     for px in range(tpc):  # tpc == 1: all four classes in one launch; tpc == 2: classes (px, 0), (px, 1)
         cls = LatticeClass((2, 2, 1), (px, 0, 0), (1, 1, 1), taps)
-        pl = IgemmPlan(kind, cls, tuple(q), kc, nreal, kreal, (8, 8, 4), 4, 4, 1, kc, 1, g, stream_lds_bytes(kc, 4, 4), -4)
+        pl = IgemmPlan(kind, cls, tuple(q), kc, nreal, kreal, (8, 8, 4), 4, 4, 1, kc, 1, g, stream_lds_bytes(kc, 4, 4), DEPTH_STREAM_SHUFFLE)
         ks, t, lane, j = np.meshgrid(np.arange(g), np.arange(4), np.arange(64), np.arange(8), indexing="ij")
         p = ks * 4 + (lane >> 4)
         tap, cg = p // g, p % g
@@ -451,8 +464,8 @@ def shuffle_plans(kind, wshape, kernel, stride, q, es, kc, nreal, kreal) -> Opti
 
 
 def is_shuffle(pl) -> bool:
-    """A launch that computes fused output-parity classes (pixel shuffle): the streaming kernel's depth -4 plans and their marching variants."""
-    return pl.depth == -4 or (pl.depth in MARCH_DEPTHS and tuple(pl.cls.os) == (2, 2, 1))
+    """A launch that computes fused output-parity classes (pixel shuffle): the streaming kernel's DEPTH_STREAM_SHUFFLE plans and their marching variants."""
+    return pl.depth == DEPTH_STREAM_SHUFFLE or (is_march(pl) and tuple(pl.cls.os) == (2, 2, 1))
 
 
 def march_shuffle_all_plans(kind, wshape, kernel, stride, q, es, kc, nreal, kreal, n=1) -> List["IgemmPlan"]:
@@ -491,7 +504,7 @@ def march_shuffle_all_plans(kind, wshape, kernel, stride, q, es, kc, nreal, krea
         for target in (512, 1024):
             nxs = max(1, min(q[0] // 8, -(-target // cols)))
             lx = -(-q[0] // nxs)
-            pl = IgemmPlan(kind, cls, tuple(q), kc, nreal, kreal, (lx, tyb, tz), mt, nt, 1, kc, 1, ksteps, lds, -5)
+            pl = IgemmPlan(kind, cls, tuple(q), kc, nreal, kreal, (lx, tyb, tz), mt, nt, 1, kc, 1, ksteps, lds, DEPTH_MARCH)
             pl.pack_map = pm
             if not any(o.tile == pl.tile and o.mtw == pl.mtw for o in out):
                 out.append(pl)
@@ -502,7 +515,7 @@ def march_shuffle_plans(sp: "IgemmPlan", n=1) -> List["IgemmPlan"]:
     """Marching-kernel variants (csrc/mconv.hip PS) of a fused-parity-classes plan of shuffle_plans: 32 input channels -> four classes of 16 channels (the level-1 ->
     level-0 transposed convolution).  Same lattice class, taps and packed weights; tile = (coarse x steps per workgroup, coarse rows, z slices); every fine
     output row is written as tz consecutive 32-byte voxels instead of the streaming kernel's 8x8x4 tiles."""
-    if sp.depth != -4 or (sp.kind, sp.kc) not in (("convT_fwd", 32), ("conv_dgrad", 16)) or sp.nc != 16 or sp.nt != 4 or tuple(sp.cls.oo) != (0, 0, 0):
+    if sp.depth != DEPTH_STREAM_SHUFFLE or (sp.kind, sp.kc) not in (("convT_fwd", 32), ("conv_dgrad", 16)) or sp.nc != 16 or sp.nt != 4 or tuple(sp.cls.oo) != (0, 0, 0):
         return []  # (the level-1 -> level-0 transposed convolution; the data gradient of the level-0 -> level-1 strided convolution)
     q, out = sp.q, []
     if sp.kc == 16:  # entries that exist for pixel-shuffle launches only (MC_P of csrc/mconv.hip)
@@ -516,7 +529,7 @@ def march_shuffle_plans(sp: "IgemmPlan", n=1) -> List["IgemmPlan"]:
             cols = n * (q[1] // tyb) * (q[2] // tz)
             for target in (512, 1024):
                 nxs = max(1, min(q[0] // 8, -(-target // cols)))
-                pl = dataclasses.replace(sp, tile=(-(-q[0] // nxs), tyb, tz), mtw=mt, lds=lds, depth=-5)
+                pl = dataclasses.replace(sp, tile=(-(-q[0] // nxs), tyb, tz), mtw=mt, lds=lds, depth=DEPTH_MARCH)
                 if not any(o.tile == pl.tile and o.mtw == pl.mtw for o in out):
                     out.append(pl)
         return out
@@ -528,15 +541,15 @@ def march_shuffle_plans(sp: "IgemmPlan", n=1) -> List["IgemmPlan"]:
         for target in (512, 1024):
             nxs = max(1, min(q[0] // 8, -(-target // cols)))
             lx = -(-q[0] // nxs)
-            for depth in ((-5, -6) if (c, t, tz, mt) in MARCH_WREG_SHAPES else (-5,)):
-                lds = march_lds_bytes(32, 4, tz, mt, depth == -6) - (0 if depth == -6 else 5 * 4 * 1024)  # 4 of the 9 K-steps of weights are staged
+            for depth in (MARCH_DEPTHS if (c, t, tz, mt) in MARCH_WREG_SHAPES else MARCH_DEPTHS[:1]):
+                lds = march_lds_bytes(32, 4, tz, mt, depth == DEPTH_MARCH_WREG) - (0 if depth == DEPTH_MARCH_WREG else 5 * 4 * 1024)  # 4 of the 9 K-steps of weights are staged
                 pl = dataclasses.replace(sp, tile=(lx, tyb, tz), mtw=mt, lds=lds, depth=depth)
                 if not any(o.tile == pl.tile and o.mtw == pl.mtw and o.depth == pl.depth for o in out):
                     out.append(pl)
     return out
 
 
-# ---- compute-bound kernel (csrc/cconv.hip): depth -3 -----------------------------------------------------------------------
+# ---- compute-bound kernel (csrc/cconv.hip): DEPTH_COMPUTE -----------------------------------------------------------------------
 COMPUTE_TILE = (4, 8, 16)
 _TAPS_3x3x3 = [(t // 9 - 1, (t // 3) % 3 - 1, t % 3 - 1) for t in range(27)]
 
@@ -583,7 +596,7 @@ def compute_lds_bytes(nt):
 
 
 def compute_plan(kind, wshape, cls, q, es, kc, nreal, kreal, in_split=0) -> Optional["IgemmPlan"]:
-    """The depth -3 candidate: the compile-time-geometry kernel for the MFMA-bound launches (stride-1 3x3x3 bf16, input channels a multiple
+    """The DEPTH_COMPUTE candidate: the compile-time-geometry kernel for the MFMA-bound launches (stride-1 3x3x3 bf16, input channels a multiple
     of 16 processed in 16-channel chunks, 32 / 48 / 64 / 96 output channels, extents divisible by the 4x8x16 tile)."""
     offs = [tuple(t[0]) for t in cls.taps]
     if es != 2 or tuple(cls.is_) != (1, 1, 1) or tuple(cls.os) != (1, 1, 1) or tuple(cls.oo) != (0, 0, 0) or offs != _TAPS_3x3x3:
@@ -594,10 +607,10 @@ def compute_plan(kind, wshape, cls, q, es, kc, nreal, kreal, in_split=0) -> Opti
     if sp is None:
         return None
     nt, nsplit = sp
-    return IgemmPlan(kind, cls, tuple(q), kc, nreal, kreal, COMPUTE_TILE, 8, nt, nsplit, 16, kc // 16, 14, compute_lds_bytes(nt), -3)
+    return IgemmPlan(kind, cls, tuple(q), kc, nreal, kreal, COMPUTE_TILE, 8, nt, nsplit, 16, kc // 16, 14, compute_lds_bytes(nt), DEPTH_COMPUTE)
 
 
-# ---- deep-level kernel (csrc/dconv.hip): depth -7 -------------------------------------------------------------------------
+# ---- deep-level kernel (csrc/dconv.hip): DEPTH_DEEP -------------------------------------------------------------------------
 DEEP_MAX_VOXELS = 1 << 18  # lattice voxels x batch up to which the deep-level kernel is offered (level 3 at batch 4: 196 608)
 DEEP_WAVES = 4
 
@@ -624,7 +637,7 @@ def _deep_ok(tile, mt, nt):
 
 
 def deep_plans(kind, wshape, cls, q, es, kc, nreal, kreal, n=1, in_split=0, limit=12) -> List["IgemmPlan"]:
-    """The depth -7 candidates: the deep-level kernel (csrc/dconv.hip) on the small bf16 launches — workgroups of 16 * mt lattice voxels x nt channel tiles whose
+    """The DEPTH_DEEP candidates: the deep-level kernel (csrc/dconv.hip) on the small bf16 launches — workgroups of 16 * mt lattice voxels x nt channel tiles whose
     four waves split the K-steps, weight fragments straight from L2.  Any lattice class (stride-1, strided, one parity class of a transposed convolution)."""
     nvox = n * q[0] * q[1] * q[2]
     if es != 2 or nvox > DEEP_MAX_VOXELS or kc % 8 or (in_split and in_split % 8):
@@ -647,7 +660,7 @@ def deep_plans(kind, wshape, cls, q, es, kc, nreal, kreal, n=1, in_split=0, limi
                 lds = deep_lds_bytes(tile, cls.is_, cls.taps, ck, ksteps, mt, nt, 0)
                 if lds > LDS_LIMIT:
                     continue
-                pl = IgemmPlan(kind, cls, tuple(q), kc, nreal, kreal, tuple(tile), mt, nt, nsplit, ck, kc // ck, ksteps, lds, -7)
+                pl = IgemmPlan(kind, cls, tuple(q), kc, nreal, kreal, tuple(tile), mt, nt, nsplit, ck, kc // ck, ksteps, lds, DEPTH_DEEP)
                 pl.pack_map = pack_map(pl, wshape)
                 out.append((tiles * nsplit, pl))
                 got += 1
@@ -682,14 +695,14 @@ def deep_class_plans(kind, wshape, kernel, stride, q, es, kc, nreal, kreal, n=1,
         lds = deep_lds_bytes(tile, union.is_, union.taps, kc, ksteps, mt, nt, len(classes))
         if lds > LDS_LIMIT:
             continue
-        pl = IgemmPlan(kind, union, tuple(q), kc, nreal, kreal, tuple(tile), mt, nt, len(classes), kc, 1, ksteps, lds, -7)
+        pl = IgemmPlan(kind, union, tuple(q), kc, nreal, kreal, tuple(tile), mt, nt, len(classes), kc, 1, ksteps, lds, DEPTH_DEEP)
         pl.classes = classes
         pl.pack_map = pack_map(pl, wshape)
         out.append(pl)
     return out
 
 
-# ---- transition kernel (csrc/tconv.hip): depth -8 -----------------------------------------------------------------------
+# ---- transition kernel (csrc/tconv.hip): DEPTH_TRANSITION -----------------------------------------------------------------------
 TRANSITION_TILE = (4, 8, 8)
 
 
@@ -721,7 +734,7 @@ def transition_plans(kind, wshape, kernel, stride, q, es, kc, nreal, kreal, in_s
         if hi - lo != 1 or lo not in (0, -1):
             return []
     union = LatticeClass(classes[0].os, (0, 0, 0), classes[0].is_, [(off, (0, 0, 0)) for off in offs])
-    pl = IgemmPlan(kind, union, tuple(q), kc, nreal, kreal, TRANSITION_TILE, 16, 3, 8, kc, 1, (8 * (kc // 8) + 3) // 4, transition_lds_bytes(kc), -8)
+    pl = IgemmPlan(kind, union, tuple(q), kc, nreal, kreal, TRANSITION_TILE, 16, 3, 8, kc, 1, (8 * (kc // 8) + 3) // 4, transition_lds_bytes(kc), DEPTH_TRANSITION)
     pl.classes = classes
     pl.pack_map = pack_map(pl, wshape)
     return [pl]
@@ -850,15 +863,15 @@ def candidate_plans(kind, wshape, cls: LatticeClass, q, es, kc_pad=None, aux_es=
                 out.append(pl)
     # keep the default, then prefer few chunks / the default split; cap the list
     rest = sorted(out[1:], key=lambda p: (p.mtw != 8, p.nsplit != default.nsplit, p.nchunks, -p.mtw))[: limit - 1]  # the 512-voxel variants are always measured
-    # no-prefetch twins (depth -1: one LDS buffer, about half the footprint) where registers allow more than one resident
+    # no-prefetch twins (DEPTH_NOPREFETCH: one LDS buffer, about half the footprint) where registers allow more than one resident
     # workgroup: 32->16 full-res 0.85 -> 0.78 ms, 64->32 half-res 0.86 -> 0.61 ms (tools/sweep_depth0.sh)
     twins = []
     for pl in [default] + rest:
-        if pl.depth == -1 or pl.nt >= 3:  # nt >= 3 runs producer / consumer waves: always at least double-buffered
+        if pl.depth == DEPTH_NOPREFETCH or pl.nt >= 3:  # nt >= 3 runs producer / consumer waves: always at least double-buffered
             continue
         if pl.nt <= 2 or pl.mtw <= 2 or pl.mtw == 8:  # register budget allows a second resident workgroup (512-voxel tiles: one buffer is all that fits)
-            lds = igemm_lds_bytes(pl.tile, cls.is_, cls.taps, pl.ck, pl.ksteps, pl.nt, pl.mtw, es, pl.nchunks, aux_es, -1)
-            twins.append(dataclasses.replace(pl, depth=-1, lds=lds))
+            lds = igemm_lds_bytes(pl.tile, cls.is_, cls.taps, pl.ck, pl.ksteps, pl.nt, pl.mtw, es, pl.nchunks, aux_es, DEPTH_NOPREFETCH)
+            twins.append(dataclasses.replace(pl, depth=DEPTH_NOPREFETCH, lds=lds))
     rest = rest + twins
     sp = stream_plan(kind, wshape, cls, q, es, kc, nreal, kreal)
     if sp is not None and not in_split_unsupported(in_split, kc):
