@@ -84,6 +84,43 @@ def test_plans_lower_on_cpu(att, dt):
         assert eng.lib.vsseg_igemm_lds_bytes(ctypes.byref(d)) > 0
 
 
+@pytest.mark.parametrize("att", [True, False])
+def test_program_queries_agree_with_the_spelled_out_scans(att):
+    """Program.producer / readers / residual_conv and Layer.stride1_3x3x1 against the scans and predicates the engine used to spell out."""
+    from vs_seg_amd.graph import AttGate, ConvBnAct, ConvPlain
+
+    prog = build_program(att)
+    convs = [o for o in prog.ops if isinstance(o, (ConvBnAct, ConvPlain))]
+    for Lr in prog.layers:
+        assert Lr.stride1_3x3x1 == (not Lr.transposed and tuple(Lr.stride) == (1, 1, 1) and Lr.kernel == (3, 3, 1)), Lr.prefix
+    assert any(Lr.stride1_3x3x1 for Lr in prog.layers) and not all(Lr.stride1_3x3x1 for Lr in prog.layers)
+    # producer: every ConvPlain output, and nothing else
+    plain = [o for o in prog.ops if isinstance(o, ConvPlain)]
+    assert plain and all(prog.producer(o.out) is o for o in plain)
+    assert all(prog.producer(o.out) is None for o in prog.ops if not isinstance(o, ConvPlain)) and prog.producer(prog.input) is None
+    # residual_conv: every `.residual` convolution is found from the first convolution of its unit (same input, `unit0`) and from no other op
+    residuals = [o for o in plain if o.layer.prefix.endswith(".residual")]
+    assert len(residuals) == 11 and len({id(o.x) for o in residuals}) == len(residuals)  # (five encoder units, the bottom unit, five decoder units: each changes the channel count)
+    found = {id(op): prog.residual_conv(op) for op in convs}
+    for rc in residuals:
+        unit = rc.layer.prefix[: -len(".residual")]
+        first = [op for op in convs if op.layer.prefix == unit + ".conv.unit0"]
+        assert len(first) == 1 and first[0].x is rc.x and found[id(first[0])] is rc
+        assert [op for op in convs if found[id(op)] is rc] == first
+    assert sum(1 for v in found.values() if v is not None) == len(residuals)
+    # readers: of every attention-gate output, the two scans of the lowering (with and without the readers as an attention map, which a gated tensor never has)
+    gates = [g for g in prog.ops if isinstance(g, AttGate)]
+    assert bool(gates) == att
+    for g in gates:
+        scan1 = [o for o in prog.ops if isinstance(o, (ConvBnAct, ConvPlain)) and (o.x is g.out or (o.x.parts is not None and g.out in o.x.parts) or o.res is g.out)]
+        scan1 += [o for o in prog.ops if isinstance(o, AttGate) and (o.x is g.out or (o.x.parts is not None and g.out in o.x.parts))]
+        scan2 = [o for o in prog.ops if ((getattr(o, "x", None) is g.out) or (getattr(getattr(o, "x", None), "parts", None) is not None and g.out in o.x.parts)
+                                         or getattr(o, "res", None) is g.out or getattr(o, "att", None) is g.out)]
+        got = prog.readers(g.out)
+        assert got and sorted(map(id, got)) == sorted(map(id, scan1)) == sorted(map(id, scan2))
+        assert [o for o in prog.readers(g.att) if isinstance(o, AttGate)] == [g]  # the gate reads its attention map
+
+
 def test_bad_spatial_size_raises():
     lay = ParamLayout(state_manifest(True))
     flat = torch.zeros(lay.n_param)

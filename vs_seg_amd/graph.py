@@ -64,6 +64,10 @@ class Layer:
         return level_dims(patch, hp)[self.level]
 
     @property
+    def stride1_3x3x1(self):  # not transposed, stride (1,1,1), kernel (3,3,1): the domain of the marching kernels
+        return not self.transposed and tuple(self.stride) == (1, 1, 1) and self.kernel == (3, 3, 1)
+
+    @property
     def out_level(self):
         if all(s == 1 for s in self.stride):
             return self.level
@@ -126,6 +130,20 @@ class Program:
     input: TensorSpec
     logits: TensorSpec
     att_maps: List[TensorSpec]  # coarsest -> finest (hook order, ref:.../unet2d5_spvPA.py:101-104)
+
+    def __post_init__(self):
+        self._producer = {op.out.name: op for op in self.ops if isinstance(op, ConvPlain)}
+
+    def producer(self, t: TensorSpec) -> Optional[ConvPlain]:  # the ConvPlain (residual / attention / final convolution) that writes a tensor, or None
+        return self._producer.get(t.name)
+
+    def readers(self, t: TensorSpec) -> list:  # every op that reads a tensor: as its input, as one operand of its two-part input, as its residual or as its attention map
+        return [o for o in self.ops if o.x is t or (o.x.parts is not None and t in o.x.parts) or getattr(o, "res", None) is t or getattr(o, "att", None) is t]
+
+    def residual_conv(self, op) -> Optional[ConvPlain]:
+        """The 1x1x1 `.residual` convolution of the ResidualUnit whose first convolution `op` is: same input, same output channels."""
+        return next((o for o in self.ops if isinstance(o, ConvPlain) and o.x is op.x and o.layer.kernel == (1, 1, 1) and o.layer.prefix.endswith(".residual")
+                     and o.layer.cout == op.layer.cout and o.act == "none" and o.res is None and o is not op), None)
 
 
 def build_program(attention: bool = True, hp: dict = HP) -> Program:
