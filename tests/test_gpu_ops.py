@@ -2,7 +2,10 @@
 
 Tolerances: fp32 path = exact-fp32 MFMA, differences are summation-order only (<= 1e-4 relative to the output scale,
 well inside the 1e-3 bar of BASELINE.json's north_star).  bf16 path = bf16 operands, fp32 accumulate: inputs are
-pre-rounded to bf16 on both sides so the only difference left is the output rounding (2^-8 relative).
+pre-rounded to bf16 on both sides so the only difference left is the output rounding, and the comparison holds the kernels to it: every
+element of a bf16 output lies between the bf16 roundings of ref -+ 2e-5 max|ref| (tests/rounding.py; the 2e-5 is the fp32 path's bar, the
+accumulators are fp32 in both).  Where a kernel rounds an intermediate tensor to bf16 by design, the reference is built from that stored
+tensor (never from a rounding of its own), so no slack is left for a second rounding.
 """
 import ctypes as C
 import dataclasses
@@ -17,6 +20,7 @@ pytestmark = pytest.mark.gpu
 from oracle import vsseg_oracle as O  # noqa: E402
 from tests import gpu_harness as H  # noqa: E402
 from tests.helpers import load, synth_input, synth_label  # noqa: E402
+from tests.rounding import assert_one_rounding  # noqa: E402
 from vs_seg_amd import _lib as L  # noqa: E402
 from vs_seg_amd import planner as P  # noqa: E402
 
@@ -43,6 +47,14 @@ def _tol(dt, ref):
     return (2e-5 if dt == "fp32" else 1.2e-2) * scale
 
 
+def _check(dt, got, ref, what=""):
+    """An output (float image, NCDHW) against its fp64 definition: fp32 within the accumulator bar of `_tol`, bf16 within ONE correct rounding of it."""
+    if dt == "bf16":
+        assert_one_rounding(got, ref, what=what)
+    else:
+        np.testing.assert_allclose(got.numpy(), ref.detach().float().numpy(), atol=_tol(dt, ref), err_msg=what)
+
+
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])
 @pytest.mark.parametrize("k,s,cin,cout,dims", CONVS)
 def test_conv_forward_and_dgrad(k, s, cin, cout, dims, dt):
@@ -55,12 +67,12 @@ def test_conv_forward_and_dgrad(k, s, cin, cout, dims, dt):
     out = torch.zeros(2, *y.shape[2:], cout, dtype=H.DT[dt], device="cuda")
     bias = b.cuda()
     H.run_lattice_op("conv_fwd", w, H.to_cl(x, H.DT[dt], P.round_up(cin, 8)), out, s, bias=bias.data_ptr())
-    np.testing.assert_allclose(H.from_cl(out).numpy(), y.detach().float().numpy(), atol=_tol(dt, y))
+    _check(dt, H.from_cl(out), y.detach(), "conv_fwd")
     gy = _round(torch.randn(*y.shape), dt)
     y.backward(gy.double())
     dx = torch.zeros(2, *dims, cin, dtype=H.DT[dt], device="cuda")
     H.run_lattice_op("conv_dgrad", w, H.to_cl(gy, H.DT[dt], P.round_up(cout, 8)), dx, s)
-    np.testing.assert_allclose(H.from_cl(dx).numpy(), x.grad.float().numpy(), atol=_tol(dt, x.grad))
+    _check(dt, H.from_cl(dx), x.grad, "conv_dgrad")
 
 
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])
@@ -74,12 +86,12 @@ def test_conv_transpose_forward_and_dgrad(k, s, cin, cout, dims, dt):
     y = F.conv_transpose3d(x.double(), w.double(), stride=s, padding=pad, output_padding=opad)
     out = torch.zeros(2, *y.shape[2:], cout, dtype=H.DT[dt], device="cuda")
     H.run_lattice_op("convT_fwd", w, H.to_cl(x, H.DT[dt]), out, s)
-    np.testing.assert_allclose(H.from_cl(out).numpy(), y.detach().float().numpy(), atol=_tol(dt, y))
+    _check(dt, H.from_cl(out), y.detach(), "convT_fwd")
     gy = _round(torch.randn(*y.shape), dt)
     y.backward(gy.double())
     dx = torch.zeros(2, *dims, cin, dtype=H.DT[dt], device="cuda")
     H.run_lattice_op("convT_dgrad", w, H.to_cl(gy, H.DT[dt]), dx, s)
-    np.testing.assert_allclose(H.from_cl(dx).numpy(), x.grad.float().numpy(), atol=_tol(dt, x.grad))
+    _check(dt, H.from_cl(dx), x.grad, "convT_dgrad")
 
 
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])
@@ -99,10 +111,85 @@ def test_igemm_epilogue_and_channel_chunks(dt):
     rcl = H.to_cl(r, H.DT[dt])
     H.run_lattice_op("conv_fwd", w, H.to_cl(x, H.DT[dt]), out, s, bias=dev[0].data_ptr(), scale=dev[1].data_ptr(), shift=dev[2].data_ptr(), alpha=dev[3].data_ptr(), act=L.ACT_PRELU,
                      res_mode=L.RES_ADD, res=H.tdesc(rcl), stats=stats.data_ptr(), stats_stride=32, lds_budget=24 * 1024)
-    np.testing.assert_allclose(H.from_cl(out).numpy(), y.float().numpy(), atol=_tol(dt, y))
+    _check(dt, H.from_cl(out), y, "PReLU + RES_ADD + statistics, several chunks")
     st = H.stat_decode(stats).cpu().view(L.STAT_SHARDS, 2, 32).sum(0)
     np.testing.assert_allclose(st[0].numpy(), pre.sum((0, 2, 3, 4)).numpy(), rtol=1e-4, atol=1e-2)
     np.testing.assert_allclose(st[1].numpy(), (pre * pre).sum((0, 2, 3, 4)).numpy(), rtol=1e-4)
+
+
+EPILOGUE_MODES = ["plain", "bias", "eval_prelu", "relu", "sigmoid", "res_add", "relu_mask", "gate", "in1", "accumulate"]
+EPILOGUE_SHAPES = [
+    # kernel, cin, cout, dims, input split, LDS budget
+    ((3, 3, 1), 16, 16, (16, 16, 8), 0, None),
+    ((3, 3, 3), 96, 48, (8, 8, 8), 48, 40 * 1024),  # the concat read as a two-part 48 + 48 tensor; the tight budget makes the kernel sum several channel chunks
+]
+_epilogue_operands = {}
+
+
+def _epilogue_case(k, cin, cout, dims):
+    """Operands and the fp64 convolution of an EPILOGUE_SHAPES row: computed once, shared by the modes, never modified."""
+    key = (k, cin, cout, dims)
+    if key not in _epilogue_operands:
+        g = torch.Generator().manual_seed(41)
+        r = lambda *shape: torch.randn(*shape, generator=g)
+        x, w = _round(r(2, cin, *dims), "bf16"), _round(r(cout, cin, *k) / (cin * np.prod(k)) ** 0.5, "bf16")
+        vec = dict(b=r(cout), sc=torch.rand(cout, generator=g) + 0.5, sh=r(cout), w1=r(cout), b1=r(cout))
+        side, x1 = _round(r(2, cout, *dims), "bf16"), _round(r(2, 1, *dims), "bf16")
+        gate = torch.rand(2, *dims, generator=g)
+        conv = F.conv3d(x.double(), w.double(), padding=P.same_pad(k))
+        _epilogue_operands[key] = (x, w, vec, side, x1, gate, conv)
+    return _epilogue_operands[key]
+
+
+@pytest.mark.parametrize("mode", EPILOGUE_MODES)
+@pytest.mark.parametrize("k,cin,cout,dims,split,budget", EPILOGUE_SHAPES)
+def test_general_kernel_epilogue_modes_match_definition(k, cin, cout, dims, split, budget, mode):
+    """Every epilogue mode of the GENERAL bf16 kernel (depth >= 0: the kernel the specialised ones are tested bit-identical to) against the fp64 definition of that
+    mode, within one bf16 rounding: plain, bias, eval affine + PReLU, ReLU, sigmoid, residual add, ReLU mask, gated add, accumulate (definition = the stored bf16
+    value + the convolution).  VSSEG_RES_IN1 exists in the marching kernel only: the general kernel must refuse it (an error, not another epilogue); it meets its
+    definition in test_chained_marching_convolution_equals_the_two_launches."""
+    x, w, vec, side, x1, gate, conv = _epilogue_case(k, cin, cout, dims)
+    col = lambda v: v.double().view(1, -1, 1, 1, 1)
+    dev = {n_: v.cuda() for n_, v in vec.items()}
+    xcl = H.to_cl(x, torch.bfloat16)
+    xin = H._split_cl(xcl, split) if split else xcl
+    side_cl, gate_d, alpha = H.to_cl(side, torch.bfloat16), gate.cuda(), torch.tensor([0.2], device="cuda")
+    out = torch.full((2, *dims, cout), float("nan"), dtype=torch.bfloat16, device="cuda")
+    kw, ref = {}, conv
+    if mode != "plain":
+        kw["bias"], ref = dev["b"].data_ptr(), conv + col(vec["b"])
+    if mode == "eval_prelu":
+        kw.update(scale=dev["sc"].data_ptr(), shift=dev["sh"].data_ptr(), alpha=alpha.data_ptr(), act=L.ACT_PRELU)
+        ref = ref * col(vec["sc"]) + col(vec["sh"])
+        ref = torch.where(ref > 0, ref, 0.2 * ref)
+    elif mode == "relu":
+        kw["act"], ref = L.ACT_RELU, ref.clamp(min=0)
+    elif mode == "sigmoid":
+        kw["act"], ref = L.ACT_SIGMOID, torch.sigmoid(ref)
+    elif mode == "res_add":
+        kw.update(res=H.tdesc(side_cl), res_mode=L.RES_ADD)
+        ref = ref + side.double()
+    elif mode == "relu_mask":
+        kw.update(res=H.tdesc(side_cl), res_mode=L.RES_RELUMASK)
+        ref = ref * (side.double() > 0)
+    elif mode == "gate":
+        kw.update(res=H.tdesc(side_cl), res_mode=L.RES_GATE, gate=gate_d.data_ptr())
+        ref = ref + side.double() * (1.0 + gate.double()).unsqueeze(1)
+    elif mode == "accumulate":
+        out = side_cl.clone()
+        kw["accumulate"], ref = 1, ref + side.double()
+    elif mode == "in1":
+        x1_cl = H.to_cl(x1, torch.bfloat16)
+        kw.update(res_mode=L.RES_IN1, in1=x1_cl.data_ptr(), in1_w=dev["w1"].data_ptr(), in1_b=dev["b1"].data_ptr())
+    if budget:
+        kw["lds_budget"] = budget
+    if mode == "in1":
+        with pytest.raises(L.VssegError, match="VSSEG_RES_IN1 needs a marching-kernel plan"):
+            H.run_lattice_op("conv_fwd", w, xin, out, (1, 1, 1), **kw)
+        return
+    keep = H.run_lattice_op("conv_fwd", w, xin, out, (1, 1, 1), **kw)
+    assert len(keep) == 1 and keep[0][1].depth >= 0 and (not budget or keep[0][1].nchunks > 1)
+    assert_one_rounding(H.from_cl(out), ref, what=f"general kernel, {mode}")
 
 
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])
@@ -204,7 +291,10 @@ def test_narrow_output_convolution_matches_definition(c, dims, batch, lx, act, o
     torch.cuda.synchronize()
     got = out.float().cpu().permute(0, 4, 1, 2, 3)
     assert not torch.isnan(got).any()
-    np.testing.assert_allclose(got.numpy(), y.float().numpy(), atol=(2e-5 if odt == "fp32" else 8e-3) * max(1.0, float(y.abs().max())))
+    if odt == "bf16":
+        assert_one_rounding(got, y, what="conv_to1")
+    else:
+        np.testing.assert_allclose(got.numpy(), y.float().numpy(), atol=2e-5 * max(1.0, float(y.abs().max())))
     if odt == "fp32" and act == "none":  # the general kernel on the same operands
         o2 = torch.zeros(batch, *dims, 8, device="cuda", dtype=torch.float32)
         H.run_lattice_op("conv_fwd", w, xcl, o2, (1, 1, 1), bias=bd.data_ptr())
@@ -391,7 +481,7 @@ def test_igemm_512_voxel_tiles(dims, dt):
     bias = b.cuda()
     keep = H.run_lattice_op("conv_fwd", w, H.to_cl(x, H.DT[dt]), out, s, bias=bias.data_ptr(), stats=stats.data_ptr(), stats_stride=48, mtw=8)
     assert keep[0][1].mtw == 8 and keep[0][1].nt == 3
-    np.testing.assert_allclose(H.from_cl(out).numpy(), y.detach().float().numpy(), atol=_tol(dt, y))
+    _check(dt, H.from_cl(out), y.detach(), "mtw 8 forward")
     st = H.stat_decode(stats).cpu().view(L.STAT_SHARDS, 2, 48).sum(0)
     np.testing.assert_allclose(st[0].numpy(), y.detach().sum((0, 2, 3, 4)).numpy(), rtol=1e-4, atol=2e-2)
     # data gradient (48 output channels, NT 3) with the same tile, no auxiliary operand
@@ -402,7 +492,10 @@ def test_igemm_512_voxel_tiles(dims, dt):
     dx48 = torch.zeros(2, *dims, 48, dtype=H.DT[dt], device="cuda")
     keep = H.run_lattice_op("conv_dgrad", w48, H.to_cl(gy, H.DT[dt]), dx48, s, mtw=8)
     assert keep[0][1].mtw == 8
-    np.testing.assert_allclose(H.from_cl(dx48).numpy(), x48.grad.float().numpy(), atol=_tol(dt, x48.grad) * 1.5)
+    if dt == "bf16":
+        assert_one_rounding(H.from_cl(dx48), x48.grad, what="mtw 8 data gradient")
+    else:
+        np.testing.assert_allclose(H.from_cl(dx48).numpy(), x48.grad.float().numpy(), atol=_tol(dt, x48.grad) * 1.5)
 
 
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])
@@ -461,7 +554,7 @@ def test_bn_dropout_prelu_forward_backward(dt, p_drop, stored, centre):
     if p_drop > 0:
         z = z * ctx.masks["b"] / (1 - p_drop)
     ref = F.prelu(z, sd64["b.act.weight"]) + H.from_cl(rcl).double()
-    np.testing.assert_allclose(H.from_cl(out).numpy(), ref.detach().float().numpy(), atol=_tol(dt, ref))
+    _check(dt, H.from_cl(out), ref.detach(), "bn_act_fwd")
     np.testing.assert_allclose(rm.cpu().numpy(), (0.9 * sd["b.norm.running_mean"] + 0.1 * mean.detach().float()).numpy(), atol=1e-5)
     np.testing.assert_allclose(rv.cpu().numpy(), (0.9 * sd["b.norm.running_var"] + 0.1 * (var.detach() * nvox / (nvox - 1)).float()).numpy(), atol=1e-5)
     assert int(nb) == 1
@@ -475,7 +568,7 @@ def test_bn_dropout_prelu_forward_backward(dt, p_drop, stored, centre):
     dy = torch.zeros_like(ycl)
     L.check(lib.vsseg_bn_act_bwd_apply(H.tdesc(ycl), H.tdesc(gcl), vec[0].data_ptr(), vec[1].data_ptr(), g.data_ptr(), be.data_ptr(), vec[2].data_ptr(), vec[3].data_ptr(), al.data_ptr(), p_drop, seed, salt, vec[4].data_ptr(), vec[5].data_ptr(), H.tdesc(dy), kptr, S))
     torch.cuda.synchronize()
-    np.testing.assert_allclose(H.from_cl(dy).numpy(), yy.grad.float().numpy(), atol=_tol(dt, yy.grad))
+    _check(dt, H.from_cl(dy), yy.grad, "bn_act_bwd_apply")
     np.testing.assert_allclose(dg.cpu().numpy(), sd64["b.norm.weight"].grad.float().numpy(), rtol=1e-4, atol=1e-3)
     np.testing.assert_allclose(db.cpu().numpy(), sd64["b.norm.bias"].grad.float().numpy(), rtol=1e-4, atol=1e-3)
     np.testing.assert_allclose(da.cpu().numpy(), sd64["b.act.weight"].grad.float().numpy(), rtol=1e-4, atol=1e-3)
@@ -579,9 +672,9 @@ def test_attention_gate_forward_backward(dt, c):
     dpre1 = torch.zeros(n, *dims, dtype=H.DT[dt], device="cuda")
     L.check(lib.vsseg_att_apply_bwd(H.tdesc(xcl), attd.data_ptr(), H.tdesc(gcl), ge.data_ptr(), H.tdesc(dx), 0, H.tdesc(dpre), dbias.data_ptr(), dpre1.data_ptr(), S))
     torch.cuda.synchronize()
-    np.testing.assert_allclose(H.from_cl(o).numpy(), out.detach().float().numpy(), atol=_tol(dt, out))
-    np.testing.assert_allclose(H.from_cl(dx).numpy(), x.grad.float().numpy(), atol=_tol(dt, x.grad))
-    np.testing.assert_allclose(H.from_cl(dpre, 1).numpy(), pre.grad.float().numpy(), atol=_tol(dt, pre.grad))
+    _check(dt, H.from_cl(o), out.detach(), "att_apply_fwd")
+    _check(dt, H.from_cl(dx), x.grad, "att_apply_bwd dx")
+    _check(dt, H.from_cl(dpre, 1), pre.grad, "att_apply_bwd dpre")
     assert float(dpre[..., 1:].float().abs().max()) == 0.0
     assert torch.equal(dpre1, dpre[..., 0])  # the compact copy feeds the z-folded data gradient of the sigmoid convolution
     assert abs(float(dbias) - float(pre.grad.sum())) < 2e-2 * float(pre.grad.abs().sum()) ** 0.5 + 1e-3
@@ -632,7 +725,7 @@ def test_every_candidate_plan_gives_the_same_convolution(kind, k, cin, cout, dim
             L.check(lib.vsseg_igemm(C.byref(d), H.stream()), f"igemm {pl.tile} ck={pl.ck} ns={pl.nsplit} D={pl.depth}")
             torch.cuda.synchronize()
             tag = f"{mode} tile={pl.tile} mtw={pl.mtw} ck={pl.ck} ns={pl.nsplit} D={pl.depth}"
-            np.testing.assert_allclose(H.from_cl(out).numpy(), ref.float().numpy(), atol=_tol(dt, ref), err_msg=tag)
+            _check(dt, H.from_cl(out), ref.detach(), tag)
             if stats is not None:
                 st = H.stat_decode(stats).cpu().view(L.STAT_SHARDS, 2, -1).sum(0)[:, :nout]
                 np.testing.assert_allclose(st[0].numpy(), want.sum((0, 2, 3, 4)).numpy(), rtol=2e-4, atol=2e-2, err_msg=tag)
@@ -718,7 +811,7 @@ def test_streaming_kernel_equals_general_kernel(kind, k, cin, cout, dims, split)
         (og, sg), (os_, ss) = outs
         assert torch.equal(og, os_), f"{mode}: streaming kernel differs from the general kernel (max {float((og.float() - os_.float()).abs().max())})"
         if mode == "plain":
-            np.testing.assert_allclose(H.from_cl(os_).numpy(), want.float().numpy(), atol=_tol(dt, want))
+            _check("fp32" if odt == torch.float32 else dt, H.from_cl(os_), want, "streaming kernel")
         if mode == "stats":
             a, bb = H.stat_decode(sg).view(L.STAT_SHARDS, 2, -1).sum(0), H.stat_decode(ss).view(L.STAT_SHARDS, 2, -1).sum(0)
             np.testing.assert_allclose(bb.cpu().numpy(), a.cpu().numpy(), rtol=1e-5, atol=1e-3)
@@ -815,7 +908,7 @@ def test_marching_kernel_equals_general_kernel(kind, cin, cout, dims, split, sha
         for pl, (om, sm) in zip(mps, outs[1:]):
             assert torch.equal(og, om), f"{mode}: marching kernel (depth {pl.depth}) differs from the general kernel (max {float((og.float() - om.float()).abs().max())})"
             if mode == "plain":
-                np.testing.assert_allclose(H.from_cl(om).numpy(), want.float().numpy(), atol=_tol(dt, want))
+                _check("fp32" if odt == torch.float32 else dt, H.from_cl(om), want, f"marching kernel depth {pl.depth}")
             if mode == "stats":
                 a, bb = H.stat_decode(sg).view(L.STAT_SHARDS, 2, -1).sum(0), H.stat_decode(sm).view(L.STAT_SHARDS, 2, -1).sum(0)
                 np.testing.assert_allclose(bb.cpu().numpy(), a.cpu().numpy(), rtol=1e-5, atol=1e-3)
@@ -862,8 +955,8 @@ def test_gathering_marching_kernel_equals_general_kernel(kind, cin, cout, dims, 
     """depth -9 selects the gathering marching kernel (csrc/gconv.hip: the stride-(2,2,1) 3x3x1 launches that read the fine level and write the coarse one — a workgroup walks
     along x with a ring of FINE planes, stored as odd-row / even-row half planes).  Same packed weights, K order and fp32 accumulation as the general kernel with the whole
     input in one chunk: outputs must be IDENTICAL bit for bit in every epilogue it has (plain, statistics, eval affine + PReLU, accumulate), across x segments, row blocks and
-    the image borders (16 input channels; with 32 the general kernel sums two 16-channel chunks one after the other: equal to a bf16 rounding in < 5 % of the values); and equal
-    torch's fp64 result."""
+    the image borders (16 input channels; with 32 the general kernel sums two 16-channel chunks one after the other, another fp32 summation order: there both kernels meet
+    torch's fp64 definition within one bf16 rounding in EVERY mode instead); and equal torch's fp64 result."""
     lib = L.lib()
     dt, k, st = "bf16", (3, 3, 1), (2, 2, 1)
     torch.manual_seed(11)
@@ -899,6 +992,9 @@ def test_gathering_marching_kernel_equals_general_kernel(kind, cin, cout, dims, 
     bias = torch.randn(nout, device="cuda")
     res_t = H.to_cl(_round(torch.randn(n, nout, *dims), dt), H.DT[dt])
     sc, sh, alpha = torch.rand(nout, device="cuda") + 0.5, torch.randn(nout, device="cuda"), torch.tensor([0.25], device="cuda")
+    pre = want + bias.cpu().double().view(1, -1, 1, 1, 1)
+    ev = pre * sc.cpu().double().view(1, -1, 1, 1, 1) + sh.cpu().double().view(1, -1, 1, 1, 1)
+    defs = {"plain": pre, "stats": pre, "eval": torch.where(ev > 0, ev, 0.25 * ev), "accumulate": pre + H.from_cl(res_t).double()}
     for mode in ("plain", "stats", "eval", "accumulate"):
         outs = []
         for pl in (gen, gpl):
@@ -921,11 +1017,10 @@ def test_gathering_marching_kernel_equals_general_kernel(kind, cin, cout, dims, 
         assert not torch.isnan(om.float()).any()
         if same_order:
             assert torch.equal(og, om), f"{mode}: gathering kernel differs from the general kernel (max {float((og.float() - om.float()).abs().max())})"
-        else:
-            np.testing.assert_allclose(om.float().cpu().numpy(), og.float().cpu().numpy(), atol=1.6e-2 * float(og.float().abs().max()), err_msg=mode)
-            assert float((om.float() != og.float()).float().mean()) < 0.05, f"{mode}: more than 5 % of the values differ from the general kernel's by a rounding"
-        if mode == "plain":
-            np.testing.assert_allclose(H.from_cl(om).numpy(), (want + bias.cpu().double().view(1, -1, 1, 1, 1)).float().numpy(), atol=_tol(dt, want))
+        else:  # another K order: the two are compared through the definition, in every mode
+            assert_one_rounding(H.from_cl(og), defs[mode], what=f"general kernel, {mode}")
+        if mode == "plain" or not same_order:
+            assert_one_rounding(H.from_cl(om), defs[mode], what=f"gathering kernel, {mode}")
         if mode == "stats":
             a, bb = H.stat_decode(sg).view(L.STAT_SHARDS, 2, -1).sum(0), H.stat_decode(sm).view(L.STAT_SHARDS, 2, -1).sum(0)
             np.testing.assert_allclose(bb.cpu().numpy(), a.cpu().numpy(), rtol=1e-5, atol=1e-3)
@@ -1039,7 +1134,7 @@ def test_fused_conv_backward_equals_separate_launches(cin, cout, dims, tile, p_d
     xd = x.double().requires_grad_(True)
     wd = w.double().requires_grad_(True)
     F.conv3d(xd, wd, None, padding=P.same_pad(k)).backward(H.from_cl(dy).double())
-    np.testing.assert_allclose(H.from_cl(dx).numpy(), xd.grad.float().numpy(), atol=_tol("bf16", xd.grad))
+    assert_one_rounding(H.from_cl(dx), xd.grad, what="fused backward dx")
     np.testing.assert_allclose(dwf.numpy(), wd.grad.float().numpy(), rtol=1e-3, atol=1e-3 * float(wd.grad.abs().max()))
     # the second call accumulates into dw (+=), and a shape outside the table is refused loudly
     L.check(lib.vsseg_conv_bwd_fused(C.byref(fd), S), "conv_bwd_fused")
@@ -1054,7 +1149,8 @@ def test_fused_conv_backward_equals_separate_launches(cin, cout, dims, tile, p_d
 def test_fused_conv_backward_with_residual_convolution(cin, cout, dims, tile, same):
     """vsseg_conv_bwd_fused with the ResidualUnit's 1x1x1 residual convolution riding along (ref:params/networks/blocks/convolutions.py:241-255): dx = conv3x3'(dy) + conv1x1'(dres)
     in one store, dw_res = sum dres x.  `same`: dres is the tensor dout itself (single-subunit decoder units) or another tensor (encoder units).  Against the
-    fp64 definition (the separate launches round dx to bf16 between the two terms, the fused one does not) and against the separate weight-gradient launches."""
+    fp64 definition on the bf16 dy the separate pass stored (the separate launches round dx to bf16 between the two terms, the fused one does not: ONE rounding of the
+    sum) and against the separate weight-gradient launches."""
     lib = L.lib()
     k, n, p_drop = (3, 3, 1), 2, 0.1
     torch.manual_seed(23)
@@ -1105,7 +1201,7 @@ def test_fused_conv_backward_with_residual_convolution(cin, cout, dims, tile, sa
     xd.grad = None
     F.conv3d(xd, wrd, None).backward(H.from_cl(rcl).double())
     want = g3 + xd.grad
-    np.testing.assert_allclose(H.from_cl(dx).numpy(), want.float().numpy(), atol=_tol("bf16", want))
+    assert_one_rounding(H.from_cl(dx), want, what="fused backward dx + residual convolution")
     np.testing.assert_allclose(dw.cpu().reshape(w.shape).numpy(), dw_ref.numpy(), rtol=2e-4, atol=2e-4 * float(dw_ref.abs().max()))
     np.testing.assert_allclose(dwr.cpu().reshape(wr.shape).numpy(), dwr_ref.numpy(), rtol=2e-4, atol=2e-4 * float(dwr_ref.abs().max()))
     np.testing.assert_allclose(dwr.cpu().reshape(wr.shape).numpy(), wrd.grad.float().numpy(), rtol=1e-3, atol=1e-3 * float(wrd.grad.abs().max()))
@@ -1182,7 +1278,7 @@ def test_marching_kernel_with_residual_tiles(cin, cout, dims, shape, lx):
         torch.cuda.synchronize()
         yy = F.conv3d(x.double(), w.double(), b.double().cpu(), padding=P.same_pad(k)) * sc.double().cpu().view(1, -1, 1, 1, 1) + sh.double().cpu().view(1, -1, 1, 1, 1)
         want = F.prelu(yy, al.double().cpu()) + F.conv3d(x.double(), wr.double(), br.double().cpu())
-        np.testing.assert_allclose(H.from_cl(out).numpy(), want.float().numpy(), atol=_tol("bf16", want))
+        assert_one_rounding(H.from_cl(out), want, what=f"residual tiles, eval, depth {depth}")
         if cin == 64:  # + the attention gate applied on load to the two-part concat (the level-1 decoder unit): bit-identical to the launch on the materialised gated tensor
             att = torch.rand(n, *dims, device="cuda")
             gated = torch.empty_like(xcl)
@@ -1209,7 +1305,8 @@ def test_marching_kernel_with_residual_tiles(cin, cout, dims, shape, lx):
 def test_attention_gate_on_load_equals_materialised_gate(dims, split, shape, lx):
     """in_gate / h_gate: the marching convolution and the marching weight gradient multiply the input voxels by (1 + att) in LDS (AttentionBlock2,
     ref:params/networks/blocks/attentionblock.py:43-47) instead of reading a gated tensor written by vsseg_att_apply_fwd.  The forward must be
-    BIT-IDENTICAL to the same marching launch on the materialised tensor (same fp32 product, same bf16 rounding), the weight gradient too."""
+    BIT-IDENTICAL to the same marching launch on the materialised tensor (same fp32 product, same bf16 rounding), the weight gradient too; and equal
+    the fp64 convolution of that materialised bf16 tensor (the reference rounds where the kernel does: it reads the stored tensor)."""
     lib = L.lib()
     cin, cout, k = 32, 2, (3, 3, 1)
     torch.manual_seed(13)
@@ -1235,6 +1332,9 @@ def test_attention_gate_on_load_equals_materialised_gate(dims, split, shape, lx)
         torch.cuda.synchronize()
         outs.append(out)
     assert torch.equal(outs[0], outs[1]), float((outs[0] - outs[1]).abs().max())
+    # the definition on the bf16 gated tensor vsseg_att_apply_fwd stored (the marching launch rounds x * (1 + att) to bf16 at the same place); the logits are fp32
+    y = F.conv3d(H.from_cl(gated).double(), w.double(), b.cpu().double(), padding=P.same_pad(k))
+    _check("fp32", H.from_cl(outs[1]), y, "gate on load")
     # the general kernel refuses the field loudly
     gen = P.plan_igemm("conv_fwd", tuple(w.shape), cls, dims, 2, kc_pad=cin, in_split=split)
     gen.pack_map = P.pack_map(gen, tuple(w.shape))
@@ -1276,7 +1376,10 @@ CHAIN_CASES = [
 def test_chained_marching_convolution_equals_the_two_launches(cin, cout, dims, split, shape, lx, waves, lead):
     """vsseg_conv_chain (csrc/chain.hip): conv + folded BatchNorm + PReLU -> conv + epilogue as ONE launch with the 16-channel tensor between them in LDS.  Same packed
     weights, K order, MFMA order and epilogue arithmetic as the two marching launches (depth -5) it replaces: the output must be IDENTICAL bit for bit — across x segments
-    (the halo planes of h are recomputed), z blocks, the image borders (h is zero outside the image, not conv_a of a padded x) — and equal the torch fp64 definition."""
+    (the halo planes of h are recomputed), z blocks, the image borders (h is zero outside the image, not conv_a of a padded x) — and equal the torch fp64 definition.
+    The 16-channel tensor between the two convolutions is bf16 by design: the first launch's stored output meets ITS definition within one rounding, and the
+    definition of the second convolution is built from that stored tensor (the chain is bit-identical to the two launches), so neither check leaves room for a
+    second rounding.  The second marching launch is also where the VSSEG_RES_IN1 epilogue (first ResidualUnit) meets its definition."""
     lib = L.lib()
     dt, k, cm = "bf16", (3, 3, 1), 16
     tz, mtw = shape
@@ -1297,17 +1400,11 @@ def test_chained_marching_convolution_equals_the_two_launches(cin, cout, dims, s
     ptr = lambda t: t.data_ptr() if t is not None else None
     act_b = L.ACT_PRELU if res1 else L.ACT_SIGMOID
 
-    # torch fp64 definition (h rounded to bf16 like the stored tensor)
+    # torch fp64 definition of the first convolution
     h = F.conv3d(x.double(), wa.double(), ba.double(), padding=P.same_pad(k))
     if res1:
         h = h * sca.double().view(1, -1, 1, 1, 1) + sha.double().view(1, -1, 1, 1, 1)
-    h = torch.where(h > 0, h, (0.25 if res1 else 0.0) * h).float().to(torch.bfloat16).double()
-    y = F.conv3d(h, wb.double(), bb.double(), padding=P.same_pad(k))
-    if res1:
-        y = y * scb.double().view(1, -1, 1, 1, 1) + shb.double().view(1, -1, 1, 1, 1)
-        y = torch.where(y > 0, y, 0.1 * y) + x.double() * w1.double().view(1, -1, 1, 1, 1) + b1.double().view(1, -1, 1, 1, 1)
-    else:
-        y = torch.sigmoid(y)
+    h = torch.where(h > 0, h, (0.25 if res1 else 0.0) * h)
 
     # the two marching launches
     cls = P.lattice_classes("conv_fwd", k, (1, 1, 1))[0]
@@ -1336,6 +1433,14 @@ def test_chained_marching_convolution_equals_the_two_launches(cin, cout, dims, s
         kw.update(scale=ptr(scb_d), shift=ptr(shb_d), res_mode=L.RES_IN1, in1=compact.data_ptr(), in1_w=ptr(w1_d), in1_b=ptr(b1_d))
     d2 = H.igemm_desc(pb, wpb, H.tdesc(h_cl), H.tdesc(want), **kw)
     L.check(lib.vsseg_igemm(C.byref(d2), H.stream()), "igemm B")
+    assert_one_rounding(H.from_cl(h_cl), h, what="first launch")
+    # torch fp64 definition of the second convolution on the bf16 tensor the first launch stored
+    y = F.conv3d(H.from_cl(h_cl).double(), wb.double(), bb.double(), padding=P.same_pad(k))
+    if res1:
+        y = y * scb.double().view(1, -1, 1, 1, 1) + shb.double().view(1, -1, 1, 1, 1)
+        y = torch.where(y > 0, y, 0.1 * y) + x.double() * w1.double().view(1, -1, 1, 1, 1) + b1.double().view(1, -1, 1, 1, 1)
+    else:
+        y = torch.sigmoid(y)
 
     # ... and the chain
     got = torch.full((2, *dims, cout), float("nan"), dtype=odt, device="cuda")
@@ -1351,7 +1456,7 @@ def test_chained_marching_convolution_equals_the_two_launches(cin, cout, dims, s
     torch.cuda.synchronize()
     assert not torch.isnan(got.float()).any()
     assert torch.equal(got, want), f"chain differs from the two launches (max {float((got.float() - want.float()).abs().max())})"
-    np.testing.assert_allclose(H.from_cl(got).numpy(), y.float().numpy(), atol=_tol(dt, y) if res1 else 2e-3)
+    _check(dt if res1 else "fp32", H.from_cl(got), y, "chain")  # (the attention map is an fp32 tensor)
     got2 = torch.full_like(got, float("nan"))
     d.out = H.tdesc(got2)
     L.check(lib.vsseg_conv_chain(C.byref(d), H.stream()), "conv_chain")
@@ -1409,13 +1514,15 @@ def test_chained_marching_convolution_with_residual_tiles(dims, shape, lx):
     L.check(lib.vsseg_conv_chain(C.byref(d), H.stream()), "conv_chain")
     torch.cuda.synchronize()
     assert torch.equal(got, want), f"chain differs from the three launches (max {float((got.float() - want.float()).abs().max())})"
-    # the definition in fp64 (h and the residual rounded to bf16 like the stored tensors)
+    # the definition in fp64.  h and the residual are bf16 tensors by design: each stored tensor meets its own definition within one rounding, and the
+    # definition of the output is built from the stored tensors (the chain is bit-identical to the three launches that store them)
     pre = lambda v: v.double().cpu().view(1, -1, 1, 1, 1)
     h = F.conv3d(x.double(), wa.double(), ba.double().cpu(), padding=P.same_pad(k)) * pre(sca) + pre(sha)
-    h = torch.where(h > 0, h, 0.25 * h).float().to(torch.bfloat16).double()
-    y = F.conv3d(h, wb.double(), bb.double().cpu(), padding=P.same_pad(k)) * pre(scb) + pre(shb)
-    y = torch.where(y > 0, y, 0.1 * y) + F.conv3d(x.double(), wr.double(), br.double().cpu()).float().to(torch.bfloat16).double()
-    np.testing.assert_allclose(H.from_cl(got).numpy(), y.float().numpy(), atol=_tol(dt, y))
+    assert_one_rounding(H.from_cl(h_cl), torch.where(h > 0, h, 0.25 * h), what="first launch")
+    assert_one_rounding(H.from_cl(r_cl), F.conv3d(x.double(), wr.double(), br.double().cpu()), what="residual convolution")
+    y = F.conv3d(H.from_cl(h_cl).double(), wb.double(), bb.double().cpu(), padding=P.same_pad(k)) * pre(scb) + pre(shb)
+    y = torch.where(y > 0, y, 0.1 * y) + H.from_cl(r_cl).double()
+    assert_one_rounding(H.from_cl(got), y, what="chain with residual tiles")
 
 
 def test_chained_marching_convolution_rejects_what_it_does_not_cover():
@@ -1508,7 +1615,7 @@ def test_compute_kernel_equals_general_kernel(kind, cin, cout, dims, split):
         (og, sg), (oc, sc) = outs
         assert torch.equal(og, oc), f"{mode}: compute kernel differs from the general kernel (max {float((og.float() - oc.float()).abs().max())})"
         if mode == "plain":
-            np.testing.assert_allclose(H.from_cl(oc).numpy(), want.float().numpy(), atol=_tol(dt, want))
+            assert_one_rounding(H.from_cl(oc), want, what="compute kernel")
         if mode == "stats":
             a, bb = H.stat_decode(sg).view(L.STAT_SHARDS, 2, -1).sum(0), H.stat_decode(sc).view(L.STAT_SHARDS, 2, -1).sum(0)
             np.testing.assert_allclose(bb.cpu().numpy(), a.cpu().numpy(), rtol=1e-5, atol=1e-3)
@@ -1566,8 +1673,8 @@ def test_fused_parity_classes_equal_per_class_launches(kind, cin, cout, dims, mo
         d = H.igemm_desc(pl, H.pack(pl, w, inp_cl.dtype), H.tdesc(inp_cl), H.tdesc(out_b), **(dict(stats=sb.data_ptr(), stats_stride=nout) if mode == "stats" else kw))
         L.check(lib.vsseg_igemm(C.byref(d), H.stream()), "fused classes")
     torch.cuda.synchronize()
-    np.testing.assert_allclose(H.from_cl(out_b).numpy(), want.float().numpy(), atol=_tol(dt, want))
-    assert float((out_a.float() - out_b.float()).abs().max()) <= 2 * _tol(dt, want)  # same products, different fp32 summation order of the taps
+    assert_one_rounding(H.from_cl(out_b), want, what=f"fused parity classes, {mode}")
+    assert_one_rounding(H.from_cl(out_a), want, what=f"per-class launches, {mode}")  # same products, different fp32 summation order of the taps: compared through the definition
     if mode == "stats":
         a, bb = H.stat_decode(sa).view(L.STAT_SHARDS, 2, -1).sum(0), H.stat_decode(sb).view(L.STAT_SHARDS, 2, -1).sum(0)
         np.testing.assert_allclose(bb.cpu().numpy(), a.cpu().numpy(), rtol=1e-4, atol=1e-2)
@@ -1653,7 +1760,7 @@ def test_class_split_launch_equals_per_class_launches(kind, cin, cout, fine, mod
     out_a = prev.clone() if mode == "accumulate" else torch.zeros(n, *fine, nout, dtype=tdt, device="cuda")
     sa = stats_buf()
     H.run_lattice_op(kind, w, inp_cl, out_a, st, **epi(sa))
-    np.testing.assert_allclose(H.from_cl(out_a).numpy(), want.float().numpy(), atol=_tol(dt, want))
+    _check(dt, H.from_cl(out_a), want, f"per-class launches, {mode}")
     kreal, nreal = P.gemm_dims(kind, tuple(w.shape))
     aux_es = 0 if mode in ("plain", "stats") else inp_cl.element_size()
     pls = P.class_split_plans(kind, tuple(w.shape), k, st, q, inp_cl.element_size(), inp_cl.shape[-1], nreal, kreal, aux_es=aux_es)
@@ -1664,8 +1771,8 @@ def test_class_split_launch_equals_per_class_launches(kind, cin, cout, fine, mod
         d = H.igemm_desc(pl, H.pack(pl, w, inp_cl.dtype), H.tdesc(inp_cl), H.tdesc(out_b), **epi(sb))
         L.check(lib.vsseg_igemm(C.byref(d), H.stream()), "class split")
         torch.cuda.synchronize()
-        np.testing.assert_allclose(H.from_cl(out_b).numpy(), want.float().numpy(), atol=_tol(dt, want), err_msg=f"{pl.tile} ck={pl.ck}")
-        assert float((out_a.float() - out_b.float()).abs().max()) <= 2 * _tol(dt, want)
+        _check(dt, H.from_cl(out_b), want, f"class split, {mode}, {pl.tile} ck={pl.ck}")
+        assert dt == "bf16" or float((out_a.float() - out_b.float()).abs().max()) <= 2 * _tol(dt, want)  # (bf16: both are within one rounding of the definition)
         if mode == "stats":
             a, bb = H.stat_decode(sa).view(L.STAT_SHARDS, 2, -1).sum(0), H.stat_decode(sb).view(L.STAT_SHARDS, 2, -1).sum(0)
             np.testing.assert_allclose(bb.cpu().numpy(), a.cpu().numpy(), rtol=1e-4, atol=1e-2)
@@ -1734,7 +1841,7 @@ def test_transition_kernel_equals_class_split_launch_and_definition(kind, cin, c
     torch.cuda.synchronize()
     got = H.from_cl(out_t)
     assert not torch.isnan(got).any()
-    np.testing.assert_allclose(got.numpy(), want.float().numpy(), atol=_tol("bf16", want))
+    assert_one_rounding(got, want, what=f"transition kernel, {mode}")
     # the class-split launch of the general kernel with the whole input in one channel chunk: the same accumulator chain per output value
     csp = [pl for pl in P.class_split_plans(kind, tuple(w.shape), k, st, coarse, 2, inp_cl.shape[-1], nreal, kreal, aux_es=2 if mode == "accumulate" else 0) if pl.nchunks == 1]
     assert csp
@@ -1800,8 +1907,9 @@ DEEP_CASES = [
 def test_deep_kernel_matches_definition_and_general_kernel(kind, k, st, cin, cout, fine, mode, split):
     """csrc/dconv.hip (launch plans with depth -7: the small launches of levels 3-5, ref:params/networks/nets/unet2d5_spvPA.py:56-89): every plan `planner.deep_plans` /
     `deep_class_plans` offers computes the convolution of torch's fp64 definition with each epilogue the network uses (bias, BatchNorm statistics, activations, residual /
-    accumulate / ReLU mask / gated add, fp32 one-channel output, two-part input), on ragged lattices, with all parity classes in one launch — within the bf16 output
-    rounding, and within fp32 rounding of the general kernel (the four waves split the K sum: not bit-identical by construction); twice in a row gives identical bits."""
+    accumulate / ReLU mask / gated add, fp32 one-channel output, two-part input), on ragged lattices, with all parity classes in one launch — within ONE bf16
+    rounding of the definition in every mode, as the general kernel is (the four waves split the K sum: not bit-identical to it by construction, so the two are
+    compared through the definition); twice in a row gives identical bits."""
     lib = L.lib()
     dt, tdt, n = "bf16", torch.bfloat16, 2
     torch.manual_seed(29)
@@ -1882,8 +1990,15 @@ def test_deep_kernel_matches_definition_and_general_kernel(kind, k, st, cin, cou
 
     classes = P.lattice_classes(kind, k, st)
     general, gstat = launch([P.plan_igemm(kind, tuple(w.shape), c_, q, 2, kc_pad=inp_cl.shape[-1], aux_es=aux_es, in_split=split) for c_ in classes])
-    tol = (1e-4 if f32out else 1.2e-2) * (float(ref.abs().max()) + 1e-12)
-    np.testing.assert_allclose(H.from_cl(general).numpy(), ref.float().numpy(), atol=tol)
+    tol = 1e-4 * (float(ref.abs().max()) + 1e-12)  # of the fp32 one-channel output; the bf16 outputs are held to one rounding of the definition
+
+    def meets_definition(out, what):
+        if f32out:
+            np.testing.assert_allclose(H.from_cl(out).numpy(), ref.float().numpy(), atol=tol, err_msg=what)
+        else:
+            assert_one_rounding(H.from_cl(out), ref, what=what)
+
+    meets_definition(general, f"general kernel, {mode}")
     variants = []
     per_class = [P.deep_plans(kind, tuple(w.shape), c_, q, 2, inp_cl.shape[-1], nreal, kreal, n, split) for c_ in classes]
     assert all(per_class), "the deep-level kernel is offered for every lattice class of these shapes"
@@ -1897,8 +2012,8 @@ def test_deep_kernel_matches_definition_and_general_kernel(kind, k, st, cin, cou
     for v in variants:
         tag = " | ".join(f"tile={pl.tile} mt={pl.mtw} nt={pl.nt} ns={pl.nsplit} ck={pl.ck} cls={len(pl.classes or [])}" for pl in v[:1])
         out, st_ = launch(v)
-        np.testing.assert_allclose(H.from_cl(out).numpy(), ref.float().numpy(), atol=tol, err_msg=tag)
-        assert float((out.float() - general.float()).abs().max()) <= 2 * tol, tag
+        meets_definition(out, f"deep kernel, {mode}, {tag}")
+        assert not f32out or float((out.float() - general.float()).abs().max()) <= 2 * tol, tag  # (bf16: both are within one rounding of the definition)
         if mode == "stats":
             np.testing.assert_allclose(st_.cpu().numpy(), gstat.cpu().numpy(), rtol=2e-4, atol=2e-2, err_msg=tag)
             np.testing.assert_allclose(st_[0, :nout].cpu().numpy(), (want + bias.double().view(1, -1, 1, 1, 1)).sum((0, 2, 3, 4)).numpy(), rtol=2e-4, atol=5e-2, err_msg=tag)
@@ -1985,7 +2100,7 @@ def test_two_part_input_forward_and_wgrad(k, c0, c1, cout, dims, budget, dt):
     keep = H.run_lattice_op("conv_fwd", w.detach().float(), (xa, xb), out, (1, 1, 1), **kw)
     if budget:
         assert keep[0][1].nchunks > 1 and c0 % keep[0][1].ck == 0  # several chunks, none straddling the split
-    np.testing.assert_allclose(H.from_cl(out).numpy(), y.detach().float().numpy(), atol=_tol(dt, y))
+    _check(dt, H.from_cl(out), y.detach(), "two-part input")
     gy = _round(torch.randn(*y.shape), dt)
     y.backward(gy.double())
     dw = H.run_wgrad(False, tuple(w.shape), k, (1, 1, 1), H.to_cl(gy, H.DT[dt]), (xa, xb), cout, cin)
@@ -2010,7 +2125,7 @@ def test_two_part_output_dgrad_fresh_accumulate_and_relu_mask(k, c0, c1, cout, d
     da, db = torch.zeros(2, *dims, c0, dtype=H.DT[dt], device="cuda"), torch.zeros(2, *dims, c1, dtype=H.DT[dt], device="cuda")
     H.run_lattice_op("conv_dgrad", w, gcl, (da, db), (1, 1, 1))
     got = torch.cat([H.from_cl(da), H.from_cl(db)], 1)
-    np.testing.assert_allclose(got.numpy(), want.float().numpy(), atol=_tol(dt, want))
+    _check(dt, got, want, "two-part output, fresh")
     # accumulate + mask: operands pre-filled, result = old + dgrad * (mask > 0)
     old = _round(torch.randn(2, cin, *dims), dt)
     mask = _round(torch.randn(2, cin, *dims), dt)
@@ -2019,12 +2134,15 @@ def test_two_part_output_dgrad_fresh_accumulate_and_relu_mask(k, c0, c1, cout, d
     H.run_lattice_op("conv_dgrad", w, gcl, (oa, ob), (1, 1, 1), accumulate=1)
     got = torch.cat([H.from_cl(oa), H.from_cl(ob)], 1)
     ref = old.double() + want
-    np.testing.assert_allclose(got.numpy(), ref.float().numpy(), atol=_tol(dt, ref))
+    _check(dt, got, ref, "two-part output, accumulate")  # ref = the stored bf16 value + the convolution: one rounding of the sum
     fa, fb = torch.zeros_like(da), torch.zeros_like(db)
     H.run_lattice_op("conv_dgrad", w, gcl, (fa, fb), (1, 1, 1), res_mode=L.RES_RELUMASK, res=H.two_part(ma, mb))
     got = torch.cat([H.from_cl(fa), H.from_cl(fb)], 1)
     ref = want * (mask.double() > 0)
-    np.testing.assert_allclose(got.numpy(), ref.float().numpy(), atol=_tol(dt, want))
+    if dt == "bf16":
+        assert_one_rounding(got, ref, what="two-part output, ReLU mask")
+    else:
+        np.testing.assert_allclose(got.numpy(), ref.float().numpy(), atol=_tol(dt, want))
 
 
 @pytest.mark.parametrize("c0", [16, 48, 80])
@@ -2050,10 +2168,10 @@ def test_two_part_attention_gate(dt, c0):
     dpre = torch.zeros(n, *dims, 8, dtype=H.DT[dt], device="cuda")
     L.check(lib.vsseg_att_apply_bwd(H.two_part(xa, xb), attd.data_ptr(), H.tdesc(gcl), None, H.two_part(da, db), 1, H.tdesc(dpre), None, None, S))
     torch.cuda.synchronize()
-    np.testing.assert_allclose(H.from_cl(o).numpy(), out.detach().float().numpy(), atol=_tol(dt, out))
+    _check(dt, H.from_cl(o), out.detach(), "two-part att_apply_fwd")
     ref = old.double() + x.grad
-    np.testing.assert_allclose(torch.cat([H.from_cl(da), H.from_cl(db)], 1).numpy(), ref.float().numpy(), atol=_tol(dt, ref))
-    np.testing.assert_allclose(H.from_cl(dpre, 1).numpy(), pre.grad.float().numpy(), atol=_tol(dt, pre.grad))
+    _check(dt, torch.cat([H.from_cl(da), H.from_cl(db)], 1), ref, "two-part att_apply_bwd dx (accumulated)")
+    _check(dt, H.from_cl(dpre, 1), pre.grad, "two-part att_apply_bwd dpre")
 
 
 def test_logits_gradient_staging_copy_fast_path_equals_the_generic_copy():
