@@ -235,7 +235,7 @@ int vsseg_fork_event_destroy(void* ev);
 int vsseg_fork_arm(void* ev);
 int vsseg_fork_disarm(void);
 int vsseg_stream_wait_event(void* stream, void* ev);
-int vsseg_version(void); /* 9: + vsseg_components_scratch_bytes, vsseg_components_label, vsseg_keep_largest_component; 8: + vsseg_surface_distances, vsseg_surface_scratch_bytes; 7: + vsseg_dice_pred_bwd_to, vsseg_dice_level_sums, vsseg_dice_tail_sums, vsseg_dice_att_bwd_levels, vsseg_fork_*, vsseg_stream_wait_event; 6: + launch plans with depth -8 (transition kernel) and -9 (gathering marching kernel); 5: vsseg_wgrad march = 2 (compute weight-gradient kernel), + vsseg_conv_to1, vsseg_conv_chain_desc without h_out (the training variant measured no gain and was deleted); 4: + vsseg_conv_chain; 3: the BatchNorm-block-on-load fields (in_bn_*, keep_*, x_bn_*: round-4 experiment, measured a loss, deleted) left the descriptors, depth -7 plans;
+int vsseg_version(void); /* 10: + vsseg_swi_finalize_mirrored, vsseg_crop_job.flip is a three-axis mirror mask (was flip_x); 9: + vsseg_components_scratch_bytes, vsseg_components_label, vsseg_keep_largest_component; 8: + vsseg_surface_distances, vsseg_surface_scratch_bytes; 7: + vsseg_dice_pred_bwd_to, vsseg_dice_level_sums, vsseg_dice_tail_sums, vsseg_dice_att_bwd_levels, vsseg_fork_*, vsseg_stream_wait_event; 6: + launch plans with depth -8 (transition kernel) and -9 (gathering marching kernel); 5: vsseg_wgrad march = 2 (compute weight-gradient kernel), + vsseg_conv_to1, vsseg_conv_chain_desc without h_out (the training variant measured no gain and was deleted); 4: + vsseg_conv_chain; 3: the BatchNorm-block-on-load fields (in_bn_*, keep_*, x_bn_*: round-4 experiment, measured a loss, deleted) left the descriptors, depth -7 plans;
                             * 2: fixed-point accumulators documented + vsseg_fx_status; 1: the buffers below were described as plain doubles */
 
 /* ---- Accumulator buffers are 64-bit FIXED-POINT integers, not doubles ------------------------------------------------------------------
@@ -398,12 +398,13 @@ int vsseg_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr
 
 /* ---- data side: the reference's MONAI transform chain on volumes cached in HBM -------------------- */
 /* One crop of one cached volume: RandFlipd(spatial_axis=0) then RandSpatialCropd / SpatialPadd's zero padding
- * (ref:params/VSparams.py:208-222).  origin is in flipped + padded coordinates and may be negative. */
+ * (ref:params/VSparams.py:208-222).  origin is in flipped + padded coordinates and may be negative.  Since ABI version 10 the last field is a mirror MASK (bit 0 = x,
+ * bit 1 = y, bit 2 = z; 0 and 1 mean what flip_x = 0 / 1 meant): the source coordinate of a mirrored axis is sdims-1-g, taken before the zero-padding test. */
 typedef struct {
   const float* src;     /* [sx][sy][sz] fp32, z contiguous (the reference's X,Y,Z array order) */
   int32_t sdims[3];
   int32_t origin[3];
-  int32_t flip_x;
+  int32_t flip;
 } vsseg_crop_job;
 /* dst[j][rx][ry][rz] for j < njobs; `jobs` is a DEVICE array of vsseg_crop_job structs, image and label of every batch element. */
 int vsseg_crop_flip(const void* jobs, int32_t njobs, float* dst, const int32_t roi[3], void* stream);
@@ -416,6 +417,12 @@ int vsseg_normalize_intensity(const float* x, float* y, int64_t n, double* acc2,
 int vsseg_swi_accumulate(const float* seg /* [rx][ry][rz][c] */, const float* imap /* [rx][ry][rz] */, const int32_t roi[3], const int32_t start[3], int32_t c,
                          float* out /* [PX][PY][PZ][c] */, float* cnt /* [PX][PY][PZ] */, const int32_t pdims[3], void* stream);
 int vsseg_swi_finalize(const float* out, const float* cnt, const int32_t pdims[3], const int32_t pad_before[3], const int32_t dims[3], int32_t c, float* dst /* [X][Y][Z][c] */, void* stream);
+/* One pass of mirrored test-time augmentation (ABI version 10): `out` / `cnt` are the blend of SWI(flip_m(volume)) in the padded frame of the MIRRORED volume, `mirror` is m as in
+   vsseg_crop_job.flip.  For every image voxel g: v[k] = out[o*c+k] / cnt[o] (the quotient of vsseg_swi_finalize, bit for bit) at o = pad_before + g', g' = dims-1-g on the mirrored
+   axes; softmax != 0: v = softmax of v over the c channels; then dst[g*c+k] = (first ? v[k] : dst[g*c+k] + v[k]) * scale.  The caller passes scale = 1 on every pass but the
+   last, where it is 1 / number of passes (a power of two: exact). */
+int vsseg_swi_finalize_mirrored(const float* out, const float* cnt, const int32_t pdims[3], const int32_t pad_before[3], const int32_t dims[3], int32_t c, int32_t mirror, int32_t softmax,
+                                int32_t first, float scale, float* dst /* [X][Y][Z][c] */, void* stream);
 /* hard Dice of argmax vs label (ref:params/VSparams.py:393-408): counts[0]=|P∩G|, [1]=|P|, [2]=|G| */
 int vsseg_hard_dice_counts(const float* logits, int32_t pitch, const float* label, int64_t nvox, double* counts, void* stream);
 int vsseg_argmax2(const float* logits, int32_t pitch, int64_t nvox, uint8_t* dst, void* stream);

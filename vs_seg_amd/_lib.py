@@ -35,7 +35,8 @@ class Tensor(C.Structure):
 
 
 class CropJob(C.Structure):  # vsseg_crop_job
-    _fields_ = [("src", C.c_void_p), ("sdims", C.c_int32 * 3), ("origin", C.c_int32 * 3), ("flip_x", C.c_int32)]
+    _fields_ = [("src", C.c_void_p), ("sdims", C.c_int32 * 3), ("origin", C.c_int32 * 3), ("flip", C.c_int32)]  # flip: mirror mask, bit 0 = x, bit 1 = y, bit 2 = z
+    flip_x = property(lambda self: self.flip & 1, lambda self, on: setattr(self, "flip", 1 if on else 0))  # the training crop mirrors x or nothing
 
 
 class IgemmDesc(C.Structure):
@@ -205,7 +206,7 @@ SYMBOLS = [
     "vsseg_bn_finalize", "vsseg_bn_fold_eval", "vsseg_bn_act_fwd", "vsseg_bn_act_fwd_res1", "vsseg_bn_act_bwd_reduce", "vsseg_bn_act_bwd_finalize", "vsseg_bn_act_bwd_apply",
     "vsseg_dropout_mask", "vsseg_att_apply_fwd", "vsseg_att_apply_bwd", "vsseg_channel_sum", "vsseg_add_inplace", "vsseg_copy_cast",
     "vsseg_maxpool_label", "vsseg_dice_pred_sums", "vsseg_dice_att_sums", "vsseg_dice_finalize", "vsseg_dice_pred_bwd", "vsseg_dice_pred_bwd_to", "vsseg_dice_att_bwd", "vsseg_dice_level_sums", "vsseg_dice_tail_sums", "vsseg_dice_att_bwd_levels", "vsseg_fork_event_create", "vsseg_fork_event_destroy", "vsseg_fork_arm", "vsseg_fork_disarm", "vsseg_stream_wait_event",
-    "vsseg_adam", "vsseg_swi_accumulate", "vsseg_swi_finalize", "vsseg_hard_dice_counts", "vsseg_argmax2",
+    "vsseg_adam", "vsseg_swi_accumulate", "vsseg_swi_finalize", "vsseg_swi_finalize_mirrored", "vsseg_hard_dice_counts", "vsseg_argmax2",
     "vsseg_surface_scratch_bytes", "vsseg_surface_distances",
     "vsseg_components_scratch_bytes", "vsseg_components_label", "vsseg_keep_largest_component",
 ]  # fmt: skip
@@ -276,6 +277,7 @@ def lib():
         L.vsseg_adam.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, f32, vp]
         L.vsseg_swi_accumulate.argtypes = [vp, vp, I3, I3, i32, vp, vp, I3, vp]
         L.vsseg_swi_finalize.argtypes = [vp, vp, I3, I3, I3, i32, vp, vp]
+        L.vsseg_swi_finalize_mirrored.argtypes = [vp, vp, I3, I3, I3, i32, i32, i32, i32, f32, vp, vp]
         L.vsseg_hard_dice_counts.argtypes = [vp, i32, vp, i64, vp, vp]
         L.vsseg_argmax2.argtypes = [vp, i32, i64, vp, vp]
         L.vsseg_surface_scratch_bytes.argtypes, L.vsseg_surface_scratch_bytes.restype = [I3], i64

@@ -3,7 +3,8 @@
 // (ref:params/VSparams.py:205-245: NormalizeIntensityd, SpatialPadd, RandFlipd(spatial_axis=0), RandSpatialCropd).
 #include "common.h"
 
-// dst[b][x][y][z] = vol_b[flip ? X-1-(sx+x) : sx+x][sy+y][sz+z], 0 outside the volume (= SpatialPadd's constant padding).
+// dst[b][x][y][z] = vol_b[m(sx+x)][m(sy+y)][m(sz+z)], m(g) = dim-1-g on the axes whose bit is set in the job's mirror mask (bit 0 = x, 1 = y, 2 = z) and g on the others,
+// 0 outside the volume (= SpatialPadd's constant padding).  Training mirrors x only (RandFlipd); the mirrored passes of sliding-window inference use all three bits.
 // One launch crops image and label of a whole batch: `srcs` holds 2*n device pointers (image_0, label_0, image_1, ...).
 __global__ void crop_flip_kernel(const vsseg_crop_job* __restrict__ jobs, float* __restrict__ dst, int rx, int ry, int rz) {
   const vsseg_crop_job j = jobs[blockIdx.y];
@@ -14,9 +15,10 @@ __global__ void crop_flip_kernel(const vsseg_crop_job* __restrict__ jobs, float*
     const int z = (int)(r % rz); r /= rz;
     const int y = (int)(r % ry);
     const int x = (int)(r / ry);
-    int gx = x + j.origin[0];
-    const int gy = y + j.origin[1], gz = z + j.origin[2];
-    if (j.flip_x) gx = j.sdims[0] - 1 - gx;  // RandFlipd acts on the padded volume, before the crop
+    int gx = x + j.origin[0], gy = y + j.origin[1], gz = z + j.origin[2];
+    if (j.flip & 1) gx = j.sdims[0] - 1 - gx;  // the mirror acts on the volume, before the padding and the crop (RandFlipd; flip_m of a mirrored inference pass)
+    if (j.flip & 2) gy = j.sdims[1] - 1 - gy;
+    if (j.flip & 4) gz = j.sdims[2] - 1 - gz;
     float v = 0.f;
     if ((unsigned)gx < (unsigned)j.sdims[0] && (unsigned)gy < (unsigned)j.sdims[1] && (unsigned)gz < (unsigned)j.sdims[2]) v = j.src[((int64_t)gx * j.sdims[1] + gy) * j.sdims[2] + gz];
     out[i] = v;

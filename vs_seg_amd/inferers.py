@@ -94,17 +94,18 @@ def crop_windows(vol: torch.Tensor, b_and_starts, roi, pad_before) -> torch.Tens
     return out
 
 
-def crop_all_windows(vol: torch.Tensor, b_and_starts, roi, pad_before) -> torch.Tensor:
-    """Every window of the (virtually zero-padded) volumes in ONE launch (`vsseg_crop_flip` with one job per window, no flip):
-    [n_windows,1,rx,ry,rz] fp32.  The per-group predictor inputs are then views of this buffer."""
+def crop_all_windows(vol: torch.Tensor, b_and_starts, roi, pad_before, masks=(0,)) -> torch.Tensor:
+    """Every window of the (virtually zero-padded) volumes in ONE launch (`vsseg_crop_flip` with one job per window):
+    [len(masks)*n_windows,1,rx,ry,rz] fp32, pass after pass — the windows of the volume mirrored along the axes of masks[0] (bit 0 = x, 1 = y, 2 = z; 0 = as it is), then
+    those of masks[1], ...  The per-group predictor inputs are then views of this buffer."""
     lib = L.lib()
     stream = torch.cuda.current_stream().cuda_stream
     B, _, X, Y, Z = vol.shape
-    n = len(b_and_starts)
+    n = len(masks) * len(b_and_starts)
     jobs = (L.CropJob * n)()
-    for i, (b, s) in enumerate(b_and_starts):
+    for i, (mask, (b, s)) in enumerate((m, bs) for m in masks for bs in b_and_starts):
         j = jobs[i]
-        j.src, j.sdims, j.origin, j.flip_x = vol.data_ptr() + 4 * b * X * Y * Z, L.i3((X, Y, Z)), L.i3(tuple(si - pb for si, pb in zip(s, pad_before))), 0
+        j.src, j.sdims, j.origin, j.flip = vol.data_ptr() + 4 * b * X * Y * Z, L.i3((X, Y, Z)), L.i3(tuple(si - pb for si, pb in zip(s, pad_before))), mask
     jbuf = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(vol.device)
     out = torch.empty((n, 1, *roi), dtype=torch.float32, device=vol.device)
     L.check(lib.vsseg_crop_flip(jbuf.data_ptr(), n, out.data_ptr(), L.i3(roi), stream), "crop_flip")
@@ -138,8 +139,40 @@ def _side_stream(device, i: int) -> "torch.cuda.Stream":
     return side_stream(device, i)
 
 
+def tta_masks(tta_flips, tta_average: str = "logits") -> List[int]:
+    """The mirror masks (bit 0 = x, 1 = y, 2 = z) of the 2^len(tta_flips) passes of test-time mirror augmentation, in pass order: pass m mirrors tta_flips[i] where bit i of m is set,
+    so the identity comes first.  [0] without flips.  Raises ValueError for arguments that name no such schedule."""
+    axes = tuple(tta_flips) if tta_flips is not None else ()
+    if any(isinstance(a, bool) or not isinstance(a, (int, np.integer)) or not 0 <= a <= 2 for a in axes):
+        raise ValueError(f"tta_flips {axes!r}: the spatial axes are 0, 1, 2 (X, Y, Z of [B,1,X,Y,Z])")
+    if len(set(axes)) != len(axes):
+        raise ValueError(f"tta_flips {axes!r} repeats an axis")
+    if tta_average not in ("logits", "probabilities"):
+        raise ValueError(f"unsupported tta_average {tta_average!r} (logits | probabilities)")
+    if not axes and tta_average != "logits":
+        raise ValueError("tta_average='probabilities' averages the mirrored passes of tta_flips; without flips there is nothing to average")
+    return [sum(1 << int(a) for i, a in enumerate(axes) if m >> i & 1) for m in range(1 << len(axes))]
+
+
+def finish_pass(lib, out: torch.Tensor, cnt: torch.Tensor, cnt_batch_stride: int, pad_before, final: torch.Tensor, p: int, masks, softmax: bool, stream):
+    """Normalises the blend `out` [B,*padded,C] of pass p into `final` [B,*img,C].  A single pass is today's `vsseg_swi_finalize`.  With mirrored passes `out` is in the frame of
+    the mirrored volume: `vsseg_swi_finalize_mirrored` un-mirrors it, stores (first pass) or adds (later ones, so the sum is in pass order), the last pass scales the sum by
+    1/passes, and `out` is cleared for the next pass — no flipped copy and no second logits volume."""
+    B, padded, C, img = out.shape[0], tuple(out.shape[1:4]), out.shape[-1], tuple(final.shape[1:4])
+    pvox, ivox = padded[0] * padded[1] * padded[2], img[0] * img[1] * img[2]
+    last = p == len(masks) - 1
+    for b in range(B):
+        o, c, f = out.data_ptr() + 4 * b * pvox * C, cnt.data_ptr() + 4 * b * cnt_batch_stride, final.data_ptr() + 4 * b * ivox * C
+        if len(masks) == 1:
+            L.check(lib.vsseg_swi_finalize(o, c, L.i3(padded), L.i3(pad_before), L.i3(img), C, f, stream), "swi_finalize")
+        else:
+            L.check(lib.vsseg_swi_finalize_mirrored(o, c, L.i3(padded), L.i3(pad_before), L.i3(img), C, masks[p], int(softmax), int(p == 0), 1.0 / len(masks) if last else 1.0, f, stream), "swi_finalize_mirrored")
+    if not last:
+        L.check(lib.vsseg_memset_zero(out.data_ptr(), out.numel() * 4, stream), "memset_zero")
+
+
 def sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_size: int, predictor: Callable, overlap: float = 0.25, mode: str = "constant", padding_mode: str = "constant",
-                             cval: float = 0.0, device=None, concurrent_groups: Optional[int] = None) -> torch.Tensor:
+                             cval: float = 0.0, device=None, concurrent_groups: Optional[int] = None, tta_flips: Optional[Sequence[int]] = None, tta_average: str = "logits") -> torch.Tensor:
     """`concurrent_groups` (not a MONAI argument; 1 = strictly serial, the reference's schedule): consecutive window groups run their predictor on that
     many HIP streams, so the latency-bound deep levels of one window's forward overlap the bandwidth-bound outer levels of the next; the blend
     (`out += map*seg`) stays on the caller's stream in window order, so the result is bit-identical to the serial schedule.
@@ -148,7 +181,14 @@ def sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_size: int,
     streams — and 2 for a predictor that declares itself `stream_safe` (`UNet2d5_spvPA.segmentation_predictor()`: one set of eval activation
     buffers, packed weights and hipGraph per stream, i.e. twice the eval memory and lowering time of the serial schedule).  Three groups (round 5, with the shorter launch
     list): 42.7 against 41.8 volumes/s in an inference-only process, 38.6-41.0 against 40.8-42.9 in a process that has also trained (bench.py); round 6: 44.3-44.8 against 42.1-42.2
-    in an inference-only process, 44.3-44.5 against 44.1-44.9 inside bench.py's (four groups: 42.1) — not the default."""
+    in an inference-only process, 44.3-44.5 against 44.1-44.9 inside bench.py's (four groups: 42.1) — not the default.
+
+    `tta_flips` (not a MONAI argument; None or () = off): test-time mirror augmentation over the given spatial axes (0, 1, 2 = X, Y, Z) —
+    result = (sum over the 2^len passes m of unflip_m(SWI(flip_m(inputs)))) / 2^len, an fp32 sum in pass order (`tta_masks`), bit-identical to composing it by hand from
+    `torch.flip` and this function.  Every pass crops, predicts and blends in the frame of the mirrored volume (its own padding and window starts) and is un-mirrored once,
+    when it is normalised (`finish_pass`); the window groups of all passes share the lanes, so the pipeline does not drain between passes.
+    `tta_average="probabilities"` averages the softmax over the class channel of every pass's normalised logits instead of the logits (nnU-Net's semantics)."""
+    masks = tta_masks(tta_flips, tta_average)  # (before the device check: the arguments are wrong on any device)
     if concurrent_groups is None:
         concurrent_groups = 2 if getattr(predictor, "stream_safe", False) else 1
     if not inputs.is_cuda:
@@ -172,39 +212,45 @@ def sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_size: int,
     stream = main.cuda_stream
     cnt = _weight_sum(lib, inputs.device, padded, roi, starts, imap, stream, mode_key=str(mode))  # [padded]: the same for every batch element
     per_win = roi[0] * roi[1] * roi[2] * 4
-    windows = crop_all_windows(vol, slices, roi, pad_before) if len(slices) * per_win <= (8 << 30) else None  # one crop launch per call (<= 8 GB of windows), else per group
-    ngroups = -(-len(slices) // sw_batch_size)
+    n = len(slices)  # windows of one pass
+    windows = crop_all_windows(vol, slices, roi, pad_before, masks) if len(masks) * n * per_win <= (8 << 30) else None  # one crop launch per call (<= 8 GB of windows), else per group
+    per_pass = -(-n // sw_batch_size)  # a window group never straddles two passes
+    ngroups = len(masks) * per_pass
     lanes = [_side_stream(inputs.device, i) for i in range(min(int(concurrent_groups), ngroups))] if concurrent_groups > 1 and ngroups > 1 else []
     ready = main.record_event() if lanes else None  # the windows (and the volume) are complete on the caller's stream
     blended: Dict[int, "torch.cuda.Event"] = {}  # lane -> its previous group's segmentation has been blended (the predictor may reuse its output buffers)
-    for gi, g in enumerate(range(0, len(slices), sw_batch_size)):
+    per = roi[0] * roi[1] * roi[2]
+    pvox = padded[0] * padded[1] * padded[2]
+    final = None
+    for gi, (p, g) in enumerate((p, g) for p in range(len(masks)) for g in range(0, n, sw_batch_size)):  # the groups of all passes go round the same lanes
         grp = slices[g : g + sw_batch_size]
+
+        def group_windows():
+            if windows is not None:
+                return windows[p * n + g : p * n + g + len(grp)]
+            return crop_windows(vol, grp, roi, pad_before) if masks[p] == 0 else crop_all_windows(vol, grp, roi, pad_before, masks[p : p + 1])
+
         if lanes:
             lane = lanes[gi % len(lanes)]
             lane.wait_event(blended.get(gi % len(lanes), ready))
             with torch.cuda.stream(lane):
-                win = windows[g : g + len(grp)] if windows is not None else crop_windows(vol, grp, roi, pad_before)
-                seg = _as_cl(predictor(win))  # [n,rx,ry,rz,C]
+                seg = _as_cl(predictor(group_windows()))  # [n,rx,ry,rz,C]
                 done = lane.record_event()
             seg.record_stream(main)
             main.wait_event(done)
         else:
-            win = windows[g : g + len(grp)] if windows is not None else crop_windows(vol, grp, roi, pad_before)
-            seg = _as_cl(predictor(win))  # [n,rx,ry,rz,C]
+            seg = _as_cl(predictor(group_windows()))  # [n,rx,ry,rz,C]
         C = seg.shape[-1]
         if out is None:
             out = torch.zeros((B, *padded, C), dtype=torch.float32, device=inputs.device)
-        per = roi[0] * roi[1] * roi[2]
-        pvox = padded[0] * padded[1] * padded[2]
         for i, (b, s) in enumerate(grp):
             L.check(lib.vsseg_swi_accumulate(seg.data_ptr() + 4 * i * per * C, imap.data_ptr(), L.i3(roi), L.i3(s), C, out.data_ptr() + 4 * b * pvox * C, None, L.i3(padded), stream), "swi_accumulate")
         if lanes:
             blended[gi % len(lanes)] = main.record_event()
-    C = out.shape[-1]
-    final = torch.empty((B, *img, C), dtype=torch.float32, device=inputs.device)
-    pvox, ivox = padded[0] * padded[1] * padded[2], img[0] * img[1] * img[2]
-    for b in range(B):
-        L.check(lib.vsseg_swi_finalize(out.data_ptr() + 4 * b * pvox * C, cnt.data_ptr(), L.i3(padded), L.i3(pad_before), L.i3(img), C, final.data_ptr() + 4 * b * ivox * C, stream), "swi_finalize")
+        if g + sw_batch_size >= n:  # the pass's last window is blended
+            if final is None:
+                final = torch.empty((B, *img, C), dtype=torch.float32, device=inputs.device)
+            finish_pass(lib, out, cnt, 0, pad_before, final, p, masks, tta_average == "probabilities", stream)
     return final.permute(0, 4, 1, 2, 3)
 
 

@@ -205,27 +205,34 @@ def sharded_window_logits(inputs: torch.Tensor, roi_size, predictor: Callable, o
     return windows, out, (roi, padded, pad_before)
 
 
-def sharded_sliding_window_inference(inputs: torch.Tensor, roi_size, predictor: Callable, overlap: float = 0.25, mode: str = "constant") -> torch.Tensor:
-    """`sliding_window_inference` with the windows of each volume spread over the ranks (latency mode)."""
-    from . import _lib as L
-    from .inferers import _as_cl, crop_windows, importance_map
+def sharded_sliding_window_inference(inputs: torch.Tensor, roi_size, predictor: Callable, overlap: float = 0.25, mode: str = "constant", tta_flips=None, tta_average: str = "logits") -> torch.Tensor:
+    """`sliding_window_inference` with the windows of each volume spread over the ranks (latency mode).  `tta_flips` / `tta_average` as there: every mirrored pass
+    shards, gathers and blends its own windows, and is folded into the result when it is normalised."""
+    from functools import partial
 
-    windows, logits, (roi, padded, pad_before) = sharded_window_logits(inputs, roi_size, predictor, overlap, crop_windows)
+    from . import _lib as L
+    from .inferers import _as_cl, crop_all_windows, crop_windows, finish_pass, importance_map, tta_masks
+
+    masks = tta_masks(tta_flips, tta_average)
     lib = L.lib()
     stream = torch.cuda.current_stream().cuda_stream
     B = inputs.shape[0]
     img = tuple(int(v) for v in inputs.shape[2:])
-    seg = _as_cl(logits)
-    C = seg.shape[-1]
-    imap = importance_map(roi, mode, inputs.device)
-    out = torch.zeros((B, *padded, C), dtype=torch.float32, device=inputs.device)
-    cnt = torch.zeros((B, *padded), dtype=torch.float32, device=inputs.device)
-    per, pvox, ivox = roi[0] * roi[1] * roi[2], padded[0] * padded[1] * padded[2], img[0] * img[1] * img[2]
-    for i, (b, s) in enumerate(windows):  # reference window order on every rank
-        L.check(lib.vsseg_swi_accumulate(seg.data_ptr() + 4 * i * per * C, imap.data_ptr(), L.i3(roi), L.i3(s), C, out.data_ptr() + 4 * b * pvox * C, cnt.data_ptr() + 4 * b * pvox, L.i3(padded), stream), "swi_accumulate")
-    final = torch.empty((B, *img, C), dtype=torch.float32, device=inputs.device)
-    for b in range(B):
-        L.check(lib.vsseg_swi_finalize(out.data_ptr() + 4 * b * pvox * C, cnt.data_ptr() + 4 * b * pvox, L.i3(padded), L.i3(pad_before), L.i3(img), C, final.data_ptr() + 4 * b * ivox * C, stream), "swi_finalize")
+    out = cnt = final = None
+    for p, mask in enumerate(masks):
+        crop = crop_windows if mask == 0 else partial(crop_all_windows, masks=(mask,))  # the crop mirrors: the windows are those of the mirrored volume
+        windows, logits, (roi, padded, pad_before) = sharded_window_logits(inputs, roi_size, predictor, overlap, crop)
+        seg = _as_cl(logits)
+        C = seg.shape[-1]
+        imap = importance_map(roi, mode, inputs.device)
+        if out is None:
+            out = torch.zeros((B, *padded, C), dtype=torch.float32, device=inputs.device)
+            cnt = torch.zeros((B, *padded), dtype=torch.float32, device=inputs.device)
+            final = torch.empty((B, *img, C), dtype=torch.float32, device=inputs.device)
+        per, pvox = roi[0] * roi[1] * roi[2], padded[0] * padded[1] * padded[2]
+        for i, (b, s) in enumerate(windows):  # reference window order on every rank; the weight sum depends on the geometry only: the first pass accumulates it for all
+            L.check(lib.vsseg_swi_accumulate(seg.data_ptr() + 4 * i * per * C, imap.data_ptr(), L.i3(roi), L.i3(s), C, out.data_ptr() + 4 * b * pvox * C, cnt.data_ptr() + 4 * b * pvox if p == 0 else None, L.i3(padded), stream), "swi_accumulate")
+        finish_pass(lib, out, cnt, pvox, pad_before, final, p, masks, tta_average == "probabilities", stream)
     return final.permute(0, 4, 1, 2, 3)
 
 

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import Adam, Dice_spvPA, UNet2d5_spvPA, compute_dice_score, sliding_window_inference
-from .inferers import argmax_segmentation
+from .inferers import argmax_segmentation, tta_masks
 from .metrics import compute_surface_distances, voxel_spacing
 from .postprocess import keep_largest_component
 from . import parallel as DP
@@ -95,7 +95,13 @@ class VSparams:
         parser.add_argument("--surface_metrics", action="store_true", help="run_inference also reports HD95 and ASSD per test case (mm, on the GPU) and writes figures/test_surface_metrics.csv")
         parser.add_argument("--keep_largest_component", action="store_true", help="run_inference keeps only the largest connected component of each predicted segmentation (on the GPU) before the Dice, the surface metrics and the NIfTI export, and writes figures/test_postprocessing.csv")
         parser.add_argument("--component_connectivity", type=int, default=26, choices=[6, 18, 26], help="voxel connectivity of --keep_largest_component (26: MONAI's KeepLargestConnectedComponent)")
+        parser.add_argument("--tta_flips", type=int, nargs="*", choices=[0, 1, 2], default=None, metavar="AXIS", help="run_inference predicts every case on mirrored copies as well (spatial axes 0 1 2 = X Y Z: one pass per subset of the given axes) and averages the un-mirrored predictions; training mirrors axis 0")
+        parser.add_argument("--tta_average", type=str, default="logits", choices=["logits", "probabilities"], help="what --tta_flips averages: the blended logits, or their softmax over the classes (nnU-Net)")
         args = parser.parse_args(argv)
+        try:
+            tta_masks(args.tta_flips, args.tta_average)
+        except ValueError as e:
+            parser.error(str(e))
 
         self.debug, self.dataset, self.data_root = args.debug, args.dataset, args.data_root
         self.split_csv = "./params/split_debug.csv" if self.debug else args.split
@@ -117,6 +123,7 @@ class VSparams:
         self.compute_dtype = args.compute_dtype
         self.surface_metrics = args.surface_metrics
         self.keep_largest_component, self.component_connectivity = args.keep_largest_component, args.component_connectivity
+        self.tta_flips, self.tta_average = tuple(args.tta_flips or ()), args.tta_average
         self.results_folder_path = os.path.join(self.data_root, "results", "debug" if self.debug else args.results_folder_name)
         self.logs_path = os.path.join(self.results_folder_path, "logs")
         self.model_path = os.path.join(self.results_folder_path, "model")
@@ -151,7 +158,7 @@ class VSparams:
         for k in ("dataset", "data_root", "split_csv", "pad_crop_shape", "pad_crop_shape_test", "num_workers", "torch_device_arg", "train_batch_size", "initial_learning_rate",
                   "epochs_with_const_lr", "lr_divisor", "weight_decay", "num_epochs", "val_interval", "model", "sliding_window_inferer_roi_size", "attention", "hardness",
                   "results_folder_path", "export_inferred_segmentations", "compute_dtype") + (("surface_metrics",) if self.surface_metrics else ()) + (
-                      ("keep_largest_component", "component_connectivity") if self.keep_largest_component else ()):
+                      ("keep_largest_component", "component_connectivity") if self.keep_largest_component else ()) + (("tta_flips", "tta_average") if self.tta_flips else ()):
             log("{:<34s} {}".format(k + " =", getattr(self, k)))
         log("-" * 10)
 
@@ -356,7 +363,8 @@ class VSparams:
             for i, data in enumerate(data_loader):
                 assert i < len(mine), "the test loader yielded more cases than this rank's shard (a padded loader would double-count them)"
                 logger.info("starting image {}".format(mine[i]))
-                outputs = sliding_window_inference(inputs=data["image"], roi_size=self.sliding_window_inferer_roi_size, sw_batch_size=1, predictor=predictor, mode="gaussian")
+                outputs = sliding_window_inference(inputs=data["image"], roi_size=self.sliding_window_inferer_roi_size, sw_batch_size=1, predictor=predictor, mode="gaussian",
+                                                   tta_flips=self.tta_flips, tta_average=self.tta_average)
                 gi = mine[i]
                 if post_dev is not None:  # everything below describes the filtered prediction; the raw Dice is kept beside it
                     post_dev[0, gi] = self.compute_dice_score(outputs, data["label"]).reshape(())
