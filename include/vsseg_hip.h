@@ -235,7 +235,7 @@ int vsseg_fork_event_destroy(void* ev);
 int vsseg_fork_arm(void* ev);
 int vsseg_fork_disarm(void);
 int vsseg_stream_wait_event(void* stream, void* ev);
-int vsseg_version(void); /* 10: + vsseg_swi_finalize_mirrored, vsseg_crop_job.flip is a three-axis mirror mask (was flip_x); 9: + vsseg_components_scratch_bytes, vsseg_components_label, vsseg_keep_largest_component; 8: + vsseg_surface_distances, vsseg_surface_scratch_bytes; 7: + vsseg_dice_pred_bwd_to, vsseg_dice_level_sums, vsseg_dice_tail_sums, vsseg_dice_att_bwd_levels, vsseg_fork_*, vsseg_stream_wait_event; 6: + launch plans with depth -8 (transition kernel) and -9 (gathering marching kernel); 5: vsseg_wgrad march = 2 (compute weight-gradient kernel), + vsseg_conv_to1, vsseg_conv_chain_desc without h_out (the training variant measured no gain and was deleted); 4: + vsseg_conv_chain; 3: the BatchNorm-block-on-load fields (in_bn_*, keep_*, x_bn_*: round-4 experiment, measured a loss, deleted) left the descriptors, depth -7 plans;
+int vsseg_version(void); /* 11: + vsseg_crop_affine, vsseg_affine_job; 10: + vsseg_swi_finalize_mirrored, vsseg_crop_job.flip is a three-axis mirror mask (was flip_x); 9: + vsseg_components_scratch_bytes, vsseg_components_label, vsseg_keep_largest_component; 8: + vsseg_surface_distances, vsseg_surface_scratch_bytes; 7: + vsseg_dice_pred_bwd_to, vsseg_dice_level_sums, vsseg_dice_tail_sums, vsseg_dice_att_bwd_levels, vsseg_fork_*, vsseg_stream_wait_event; 6: + launch plans with depth -8 (transition kernel) and -9 (gathering marching kernel); 5: vsseg_wgrad march = 2 (compute weight-gradient kernel), + vsseg_conv_to1, vsseg_conv_chain_desc without h_out (the training variant measured no gain and was deleted); 4: + vsseg_conv_chain; 3: the BatchNorm-block-on-load fields (in_bn_*, keep_*, x_bn_*: round-4 experiment, measured a loss, deleted) left the descriptors, depth -7 plans;
                             * 2: fixed-point accumulators documented + vsseg_fx_status; 1: the buffers below were described as plain doubles */
 
 /* ---- Accumulator buffers are 64-bit FIXED-POINT integers, not doubles ------------------------------------------------------------------
@@ -408,6 +408,32 @@ typedef struct {
 } vsseg_crop_job;
 /* dst[j][rx][ry][rz] for j < njobs; `jobs` is a DEVICE array of vsseg_crop_job structs, image and label of every batch element. */
 int vsseg_crop_flip(const void* jobs, int32_t njobs, float* dst, const int32_t roi[3], void* stream);
+/* Random rotation / scaling / intensity / noise augmentation of a crop (ABI version 11): what MONAI users know as RandAffined + RandScaleIntensityd + RandShiftIntensityd +
+ * RandGaussianNoised, as ONE resampling gather per batch.  The kernel knows a 3x4 matrix and an intensity map per job, nothing about angles, mirrors or labels.
+ *   coordinates  for the output voxel p = (x, y, z) of dst[j][x][y][z] the source coordinate, in voxel units of the cached volume, is evaluated in fp32 as
+ *                  s_i = fmaf(m[4i+2], z, fmaf(m[4i+1], y, fmaf(m[4i], x, m[4i+3])))            (explicit fused operations: no dependence on the compiler's contraction)
+ *   interp 0     trilinear: i0 = floorf(s), f = s - i0 per axis; the eight taps (i0 + a, a in {0,1}^3) carry the products of f (a = 1) and 1 - f (a = 0).  A tap outside the
+ *                volume contributes exactly 0 (SpatialPadd's constant padding, continuous across the border): the VALUE is selected, the address of an outside tap is
+ *                never formed or read, so neighbouring memory (NaN or not) cannot leak in.
+ *   interp 1     nearest: index floorf(s + 0.5f) per axis, 0 outside the volume.
+ *   intensity    v = fmaf(v, gain, bias); then, when noise_std != 0, v = fmaf(noise_std, n, v).
+ *   noise        for the flattened patch index i = (x*ry + y)*rz + z of a job: g = i >> 2, k = i & 3,
+ *                  r = philox4x32_10(counter = (lo32 g, hi32 g, noise_stream, 0), key = (lo32 seed, hi32 seed)),   u(w) = ((w >> 8) + 0.5f) * 2^-24   (fp32 arithmetic),
+ *                  (n0, n1) = sqrtf(-2 logf(u(r.x))) * (cosf, sinf)(6.2831853f * u(r.y)),   (n2, n3) likewise from r.z, r.w;   n = n_k   (accurate logf / sincosf).
+ *   labels       are jobs with interp = 1, gain = 1, bias = 0, noise_std = 0.
+ * `jobs_dev` is the DEVICE array the kernel reads, `jobs_host` the caller's host copy of the same njobs records: the argument checks read the host copy (the entry point never
+ * reads device memory, synchronises or allocates), so that null pointers, njobs < 1, a non-positive roi or sdims, an interp outside {0, 1} and a non-finite m / gain / bias /
+ * noise_std are VSSEG_EINVAL before anything is launched.  A coordinate that is not finite or far outside the volume (a finite but absurd m) reads nothing and gives bias. */
+typedef struct {
+  const float* src;     /* [sx][sy][sz] fp32, z contiguous */
+  int32_t sdims[3];
+  int32_t interp;       /* 0 trilinear, 1 nearest */
+  float m[12];          /* row-major 3x4: output index (x, y, z, 1) -> source coordinate */
+  float gain, bias, noise_std;
+  uint32_t noise_stream;
+} vsseg_affine_job;
+/* dst[j][rx][ry][rz] for j < njobs (16-byte aligned), one launch for image and label jobs of a whole batch. */
+int vsseg_crop_affine(const vsseg_affine_job* jobs_host, const void* jobs_dev, int32_t njobs, float* dst, const int32_t roi[3], uint64_t seed, void* stream);
 /* NormalizeIntensityd (ref:params/VSparams.py:213): y = (x - mean) / std over all n voxels (population std; std == 0: no
  * division).  acc2 = 2 doubles of device scratch (sum, sum of squares; left filled for inspection). */
 int vsseg_normalize_intensity(const float* x, float* y, int64_t n, double* acc2, void* stream);

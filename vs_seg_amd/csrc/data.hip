@@ -33,6 +33,98 @@ extern "C" int vsseg_crop_flip(const void* jobs, int32_t njobs, float* dst, cons
   return VSSEG_OK;
 }
 
+// ---- vsseg_crop_affine: the resampling gather of the training augmentation (semantics: include/vsseg_hip.h) ----
+// blockIdx.y = job (the record and its matrix are wave-uniform: scalar loads), blockIdx.z = x, lanes run along (y, z / 4): a thread owns four consecutive z of one output row
+// and, when rz % 4 == 0, stores them as 16 bytes.  The shipped augmentation rotates about z, so the taps of a wave fall on contiguous source runs.
+// One 32-bit division per thread (row index from the quad index), none per voxel.
+__device__ __forceinline__ float affine_coord(const float* __restrict__ r, float x, float y, float z) { return __builtin_fmaf(r[2], z, __builtin_fmaf(r[1], y, __builtin_fmaf(r[0], x, r[3]))); }
+// a coordinate with every tap outside stays outside when it is clamped to [-2, dim + 1]; NaN becomes -2.  The conversions to int below are then always in range.
+__device__ __forceinline__ float affine_clamp(float s, int dim) { return fminf(fmaxf(s, -2.f), (float)dim + 1.f); }
+__device__ __forceinline__ float affine_tap(const float* __restrict__ src, int ix, int iy, int iz, int sx, int sy, int sz) {
+  const bool in = (unsigned)ix < (unsigned)sx && (unsigned)iy < (unsigned)sy && (unsigned)iz < (unsigned)sz;
+  return in ? src[((int64_t)ix * sy + iy) * sz + iz] : 0.f;  // an outside tap is never addressed
+}
+__device__ __forceinline__ float affine_u01(unsigned w) { return ((float)(w >> 8) + 0.5f) * 5.9604644775390625e-8f; }
+__device__ __forceinline__ void affine_normals(uint64_t g, uint32_t stream, uint2 key, float n[4]) {
+  const uint4 r = philox4x32_10(make_uint4((unsigned)g, (unsigned)(g >> 32), stream, 0u), key);
+  const float a0 = sqrtf(-2.f * logf(affine_u01(r.x))), a1 = sqrtf(-2.f * logf(affine_u01(r.z)));
+  float s0, c0, s1, c1;
+  sincosf(6.2831853f * affine_u01(r.y), &s0, &c0);
+  sincosf(6.2831853f * affine_u01(r.w), &s1, &c1);
+  n[0] = a0 * c0; n[1] = a0 * s0; n[2] = a1 * c1; n[3] = a1 * s1;
+}
+__global__ __launch_bounds__(256) void crop_affine_kernel(const vsseg_affine_job* __restrict__ jobs, float* __restrict__ dst, int rx, int ry, int rz, int nzq, uint64_t seed) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= ry * nzq) return;
+  const vsseg_affine_job j = jobs[blockIdx.y];
+  const int x = blockIdx.z, y = t / nzq, z0 = (t - y * nzq) * 4;
+  const int sx = j.sdims[0], sy = j.sdims[1], sz = j.sdims[2];
+  const int64_t row = ((int64_t)x * ry + y) * rz;  // flattened patch index of (x, y, 0)
+  const uint2 key = make_uint2((unsigned)seed, (unsigned)(seed >> 32));
+  uint64_t have = ~0ull;  // the Philox group whose four normals are in nrm
+  float nrm[4] = {0.f, 0.f, 0.f, 0.f};
+  float v[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int z = z0 + e;  // z >= rz (the tail of a row with rz % 4 != 0) is computed like any other voxel and not stored
+    const float fx = (float)x, fy = (float)y, fz = (float)z;
+    const float cx = affine_clamp(affine_coord(j.m + 0, fx, fy, fz), sx), cy = affine_clamp(affine_coord(j.m + 4, fx, fy, fz), sy), cz = affine_clamp(affine_coord(j.m + 8, fx, fy, fz), sz);
+    float r;
+    if (j.interp == 0) {
+      const float bx = floorf(cx), by = floorf(cy), bz = floorf(cz);
+      const float tx = cx - bx, ty = cy - by, tz = cz - bz, ux = 1.f - tx, uy = 1.f - ty, uz = 1.f - tz;
+      const int ix = (int)bx, iy = (int)by, iz = (int)bz;
+      const float v000 = affine_tap(j.src, ix, iy, iz, sx, sy, sz), v001 = affine_tap(j.src, ix, iy, iz + 1, sx, sy, sz);
+      const float v010 = affine_tap(j.src, ix, iy + 1, iz, sx, sy, sz), v011 = affine_tap(j.src, ix, iy + 1, iz + 1, sx, sy, sz);
+      const float v100 = affine_tap(j.src, ix + 1, iy, iz, sx, sy, sz), v101 = affine_tap(j.src, ix + 1, iy, iz + 1, sx, sy, sz);
+      const float v110 = affine_tap(j.src, ix + 1, iy + 1, iz, sx, sy, sz), v111 = affine_tap(j.src, ix + 1, iy + 1, iz + 1, sx, sy, sz);
+      r = (ux * uy) * (uz * v000 + tz * v001) + (ux * ty) * (uz * v010 + tz * v011) + (tx * uy) * (uz * v100 + tz * v101) + (tx * ty) * (uz * v110 + tz * v111);
+    } else {
+      r = affine_tap(j.src, (int)floorf(cx + 0.5f), (int)floorf(cy + 0.5f), (int)floorf(cz + 0.5f), sx, sy, sz);
+    }
+    r = __builtin_fmaf(r, j.gain, j.bias);
+    if (j.noise_std != 0.f) {
+      const uint64_t i = (uint64_t)(row + z), g = i >> 2;
+      if (g != have) {  // rz % 4 == 0: one Philox call for the four voxels of the thread
+        affine_normals(g, j.noise_stream, key, nrm);
+        have = g;
+      }
+      const int k = (int)(i & 3);
+      r = __builtin_fmaf(j.noise_std, k == 0 ? nrm[0] : k == 1 ? nrm[1] : k == 2 ? nrm[2] : nrm[3], r);
+    }
+    v[e] = r;
+  }
+  float* out = dst + (int64_t)blockIdx.y * ((int64_t)rx * ry * rz) + row + z0;
+  if ((rz & 3) == 0) {
+    *reinterpret_cast<float4*>(out) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (z0 + e < rz) out[e] = v[e];
+  }
+}
+static bool affine_finite(float f) { return f - f == 0.f; }
+extern "C" int vsseg_crop_affine(const vsseg_affine_job* jobs_host, const void* jobs_dev, int32_t njobs, float* dst, const int32_t roi[3], uint64_t seed, void* stream) {
+  VSSEG_CHECK(jobs_host && jobs_dev && dst && roi, "vsseg_crop_affine: null pointer");
+  VSSEG_CHECK(njobs >= 1 && njobs <= 65535, "vsseg_crop_affine: njobs = %d outside [1, 65535]", njobs);
+  VSSEG_CHECK(roi[0] > 0 && roi[1] > 0 && roi[2] > 0 && roi[0] <= 65535 && (int64_t)roi[1] * ((roi[2] + 3) / 4) < (1ll << 31) - 256, "vsseg_crop_affine: bad roi (%d, %d, %d)", roi[0], roi[1], roi[2]);
+  VSSEG_CHECK(((uintptr_t)dst & 15) == 0, "vsseg_crop_affine: misaligned dst (16 bytes)");
+  for (int32_t i = 0; i < njobs; ++i) {
+    const vsseg_affine_job& j = jobs_host[i];
+    VSSEG_CHECK(j.src, "vsseg_crop_affine: job %d: null src pointer", i);
+    VSSEG_CHECK(j.sdims[0] > 0 && j.sdims[1] > 0 && j.sdims[2] > 0, "vsseg_crop_affine: job %d: bad sdims (%d, %d, %d)", i, j.sdims[0], j.sdims[1], j.sdims[2]);
+    VSSEG_CHECK(j.interp == 0 || j.interp == 1, "vsseg_crop_affine: job %d: interp = %d (0 trilinear, 1 nearest)", i, j.interp);
+    bool fin = affine_finite(j.gain) && affine_finite(j.bias) && affine_finite(j.noise_std);
+    for (int k = 0; k < 12; ++k) fin = fin && affine_finite(j.m[k]);
+    VSSEG_CHECK(fin, "vsseg_crop_affine: job %d: non-finite m, gain, bias or noise_std", i);
+  }
+  const int nzq = (roi[2] + 3) / 4;
+  dim3 grid((roi[1] * nzq + 255) / 256, njobs, roi[0]);
+  hipLaunchKernelGGL(crop_affine_kernel, grid, dim3(256), 0, as_stream(stream), (const vsseg_affine_job*)jobs_dev, dst, roi[0], roi[1], roi[2], nzq, seed);
+  VSSEG_LAUNCH_CHECK("vsseg_crop_affine");
+  return VSSEG_OK;
+}
+
 // NormalizeIntensityd: (x - mean) / std over the whole image, population std, no division when std == 0.
 // Pass 1: fp64 sum / sum of squares (sharded atomics); pass 2 applies.  acc = 2 doubles, zeroed by the caller.
 __global__ void intensity_sums_kernel(const float* __restrict__ x, int64_t n, double* __restrict__ acc) {

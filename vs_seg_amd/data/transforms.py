@@ -5,6 +5,10 @@ Deterministic head (cached once per case, like `CacheDataset(cache_rate=1.0)`, r
 Random tail (per sample, per epoch):
     RandFlipd(prob=0.5, spatial_axis=0) → RandSpatialCropd(roi=pad_crop_shape, random_center=True, random_size=False)
 
+Optional training augmentation (off by default; this project's own conventions — MONAI's RandAffined / RandScaleIntensityd /
+RandShiftIntensityd / RandGaussianNoised are the transforms it corresponds to): an in-plane rotation and scaling about the centre
+of the crop window, a gain, a bias and Gaussian noise, all applied by ONE `vsseg_crop_affine` launch in place of the crop.
+
 The numpy restatement of MONAI 0.4.0's arithmetic that checks the HIP path (`vsseg_normalize_intensity`, `vsseg_crop_flip`) is test
 infrastructure and lives in `oracle/data_oracle.py` (parity unpinned — MONAI is not installed).  `PatchSampler`
 is the product path: cached volumes live in HBM, one launch crops/flips image and label of a whole batch.
@@ -35,27 +39,77 @@ def pad_widths(shape: Sequence[int], spatial_size: Sequence[int]) -> List[Tuple[
     return out
 
 
+AUGMENT_KEYS = ("rotate_deg", "scale", "intensity_scale", "intensity_shift", "noise_std")
+
+
+def check_augment(rotate_deg=0.0, scale=0.0, intensity_scale=0.0, intensity_shift=0.0, noise_std=0.0) -> Dict[str, float]:
+    """The five augmentation ranges as floats (0 = off); ValueError for a negative or non-finite range, rotate_deg > 180, scale or intensity_scale >= 1."""
+    a = dict(rotate_deg=float(rotate_deg), scale=float(scale), intensity_scale=float(intensity_scale), intensity_shift=float(intensity_shift), noise_std=float(noise_std))
+    for k, v in a.items():
+        if not (np.isfinite(v) and v >= 0.0):
+            raise ValueError(f"augmentation range {k} = {v}: must be finite and >= 0")
+    if a["rotate_deg"] > 180.0:
+        raise ValueError(f"rotate_deg = {a['rotate_deg']}: at most 180")
+    for k in ("scale", "intensity_scale"):
+        if a[k] >= 1.0:
+            raise ValueError(f"{k} = {a[k]}: must be < 1 (the factor 1 + u stays positive)")
+    return a
+
+
+def affine_matrix(roi: Sequence[int], start: Sequence[int], sdim_x: int, flip: bool, angle: float = 0.0, scale: float = 1.0) -> np.ndarray:
+    """fp32 3x4 matrix of `vsseg_affine_job.m`: output index p -> source voxel coordinate
+        s = c_src + R_z(angle) diag(1/scale, 1/scale, 1) (p - c_roi),   c_roi = (roi - 1) / 2,   c_src = start + c_roi
+    (the centre of the window the plain crop would take; rotation and scaling in-plane only: the voxels are 0.4 x 0.4 x 1.5 mm), then the x mirror
+    s_x -> sdim_x - 1 - s_x on row 0.  Composed in fp64, rounded once.  angle = 0, scale = 1 gives [I | start] (or its mirrored form) exactly."""
+    c_roi = (np.asarray(roi, np.float64) - 1.0) / 2.0
+    c_src = np.asarray(start, np.float64) + c_roi
+    c, s = np.cos(float(angle)), np.sin(float(angle))
+    A = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]]) @ np.diag([1.0 / scale, 1.0 / scale, 1.0])
+    m = np.concatenate([A, (c_src - A @ c_roi)[:, None]], 1)
+    if flip:
+        m[0] = -m[0]
+        m[0, 3] += sdim_x - 1.0
+    return (m + 0.0).astype(np.float32)  # + 0.0: no negative zeros
+
+
 class RandomTail:
     """The random decisions of RandFlipd + RandSpatialCropd with MONAI's per-transform RandomState layout:
     `Compose.set_random_state(seed)` seeds its own state and gives every Randomizable transform, in order, the seed
     `R.randint(MAX_SEED, dtype=uint32)`; RandFlipd draws `R.random_sample() < prob`, RandSpatialCropd draws
-    `R.randint(0, size - roi + 1)` per axis where size > roi."""
+    `R.randint(0, size - roi + 1)` per axis where size > roi.
 
-    def __init__(self, roi: Sequence[int], flip_prob: Optional[float] = 0.5, seed: Optional[int] = None):
+    With a non-zero augmentation range a THIRD state is seeded from `R` after those two, so the flip and crop draws are the same with
+    augmentation on or off.  `draw_augment()` draws per sample, in this order and only for the families whose range is non-zero:
+    angle ~ U(-rotate_deg, rotate_deg), scale factor 1 + U(-scale, scale), gain 1 + U(-intensity_scale, intensity_scale),
+    bias ~ U(-intensity_shift, intensity_shift); `draw_noise_seed()` draws one randint(2^32) per batch when noise_std != 0."""
+
+    def __init__(self, roi: Sequence[int], flip_prob: Optional[float] = 0.5, seed: Optional[int] = None, rotate_deg: float = 0.0, scale: float = 0.0,
+                 intensity_scale: float = 0.0, intensity_shift: float = 0.0, noise_std: float = 0.0):
         self.roi = tuple(int(r) for r in roi)
         self.flip_prob = flip_prob
+        self.augment = check_augment(rotate_deg, scale, intensity_scale, intensity_shift, noise_std)
+        self.augmenting = any(v != 0.0 for v in self.augment.values())
         self.set_random_state(seed)
 
     def set_random_state(self, seed: Optional[int] = None):
         R = np.random.RandomState(seed)
         self._flipR = np.random.RandomState(R.randint(MAX_SEED, dtype="uint32")) if self.flip_prob is not None else None
         self._cropR = np.random.RandomState(R.randint(MAX_SEED, dtype="uint32"))
+        self._augR = np.random.RandomState(R.randint(MAX_SEED, dtype="uint32")) if self.augmenting else None
         return self
 
     def draw(self, shape: Sequence[int]) -> Tuple[bool, Tuple[int, int, int]]:
         flip = bool(self._flipR.random_sample() < self.flip_prob) if self._flipR is not None else False
         start = tuple(int(self._cropR.randint(0, s - r + 1)) if s > r else 0 for s, r in zip(shape, self.roi))
         return flip, start
+
+    def draw_augment(self) -> Tuple[float, float, float, float]:
+        """(angle in radians, scale factor, gain, bias) of one sample."""
+        a, u = self.augment, (lambda r: float(self._augR.uniform(-r, r)) if r != 0.0 else 0.0)
+        return float(np.deg2rad(u(a["rotate_deg"]))), 1.0 + u(a["scale"]), 1.0 + u(a["intensity_scale"]), u(a["intensity_shift"])
+
+    def draw_noise_seed(self) -> int:
+        return int(self._augR.randint(MAX_SEED, dtype="uint32")) if self.augment["noise_std"] != 0.0 else 0
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -91,22 +145,30 @@ class PatchSampler:
 
     `sample(indices)` → (inputs [B,1,*roi], labels [B,1,*roi]) fp32 on the device, the tensors the reference's DataLoader
     yields as batch["image"], batch["label"] (ref:params/VSparams.py:455).  `flip_prob=None` = the validation chain
-    (no RandFlipd, ref:params/VSparams.py:224-236)."""
+    (no RandFlipd, ref:params/VSparams.py:224-236).
 
-    def __init__(self, cases: List[Dict], roi: Sequence[int], flip_prob: Optional[float] = 0.5, seed: Optional[int] = 0):
+    A non-zero `rotate_deg`, `scale`, `intensity_scale`, `intensity_shift` or `noise_std` (see RandomTail) replaces that launch by one
+    `vsseg_crop_affine` launch: the image is resampled trilinearly and gets gain, bias and noise, the label goes through the same matrix
+    with nearest-neighbour lookup.  `last_augment` then holds, per sample, what a test needs to replay the launch."""
+
+    def __init__(self, cases: List[Dict], roi: Sequence[int], flip_prob: Optional[float] = 0.5, seed: Optional[int] = 0, rotate_deg: float = 0.0, scale: float = 0.0,
+                 intensity_scale: float = 0.0, intensity_shift: float = 0.0, noise_std: float = 0.0):
         self.cases, self.roi = cases, tuple(int(r) for r in roi)
-        self.tail = RandomTail(self.roi, flip_prob, seed)
+        self.tail = RandomTail(self.roi, flip_prob, seed, rotate_deg, scale, intensity_scale, intensity_shift, noise_std)
         self.lib = L.lib()
         self.last_draws: List[Tuple[bool, Tuple[int, int, int]]] = []
+        self.last_augment: List[Dict] = []  # per sample: m (fp32 3x4), gain, bias, noise_std (fp32), noise_stream, seed
 
     def __len__(self):
         return len(self.cases)
 
     def sample(self, indices: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:
+        if self.tail.augmenting:
+            return self._sample_affine(indices)
         dev = self.cases[indices[0]]["image"].device
         B = len(indices)
         jobs = (L.CropJob * (2 * B))()
-        self.last_draws = []
+        self.last_draws, self.last_augment = [], []
         for b, i in enumerate(indices):
             case = self.cases[i]
             shape = tuple(case["image"].shape)
@@ -118,6 +180,34 @@ class PatchSampler:
         jbuf = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(dev)
         out = torch.empty((2, B, 1, *self.roi), dtype=torch.float32, device=dev)
         L.check(self.lib.vsseg_crop_flip(jbuf.data_ptr(), 2 * B, out.data_ptr(), L.i3(self.roi), torch.cuda.current_stream().cuda_stream), "crop_flip")
+        jbuf.record_stream(torch.cuda.current_stream())
+        return out[0], out[1]
+
+    def _sample_affine(self, indices: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:
+        dev = self.cases[indices[0]]["image"].device
+        B = len(indices)
+        jobs = (L.AffineJob * (2 * B))()
+        self.last_draws, self.last_augment = [], []
+        seed = self.tail.draw_noise_seed()
+        for b, i in enumerate(indices):
+            case = self.cases[i]
+            shape = tuple(case["image"].shape)
+            flip, start = self.tail.draw(shape)
+            angle, scale, gain, bias = self.tail.draw_augment()
+            m = affine_matrix(self.roi, start, shape[0], flip, angle, scale)
+            aug = dict(m=m, gain=np.float32(gain), bias=np.float32(bias), noise_std=np.float32(self.tail.augment["noise_std"]), noise_stream=b, seed=seed)
+            self.last_draws.append((flip, start))
+            self.last_augment.append(aug)
+            for k, key in enumerate(("image", "label")):
+                j = jobs[b + k * B]  # dst = [image_0..image_{B-1} | label_0..label_{B-1}]
+                j.src, j.sdims, j.m, j.noise_stream = case[key].data_ptr(), L.i3(shape), (C.c_float * 12)(*m.ravel().tolist()), b
+                if key == "image":
+                    j.interp, j.gain, j.bias, j.noise_std = L.INTERP_TRILINEAR, float(aug["gain"]), float(aug["bias"]), float(aug["noise_std"])
+                else:
+                    j.interp, j.gain, j.bias, j.noise_std = L.INTERP_NEAREST, 1.0, 0.0, 0.0
+        jbuf = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(dev)
+        out = torch.empty((2, B, 1, *self.roi), dtype=torch.float32, device=dev)
+        L.check(self.lib.vsseg_crop_affine(jobs, jbuf.data_ptr(), 2 * B, out.data_ptr(), L.i3(self.roi), seed, torch.cuda.current_stream().cuda_stream), "crop_affine")
         jbuf.record_stream(torch.cuda.current_stream())
         return out[0], out[1]
 
