@@ -4,6 +4,8 @@
     python VS_train.py --results_folder_name run1 [--dataset T2] [--no_attention] [--no_hardness] [--debug]
     python VS_train.py --results_folder_name run2 --aug_rotate_deg 15 --aug_scale 0.1 --aug_intensity_scale 0.1 --aug_intensity_shift 0.1 --aug_noise_std 0.05
         (random rotation about z / in-plane zoom / gain / bias / Gaussian noise on every TRAINING patch, on the GPU; all 0 = off by default)
+    python VS_train.py --results_folder_name run3 --aug_elastic_mag 8 --aug_bias_field 0.3 [--aug_field_spacing 64]
+        (in-plane elastic deformation and a smooth multiplicative MR bias field, one cubic B-spline random field per TRAINING patch, in the same launch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 VS_train.py ...   (data parallel)
 """
 import argparse

@@ -235,7 +235,7 @@ int vsseg_fork_event_destroy(void* ev);
 int vsseg_fork_arm(void* ev);
 int vsseg_fork_disarm(void);
 int vsseg_stream_wait_event(void* stream, void* ev);
-int vsseg_version(void); /* 11: + vsseg_crop_affine, vsseg_affine_job; 10: + vsseg_swi_finalize_mirrored, vsseg_crop_job.flip is a three-axis mirror mask (was flip_x); 9: + vsseg_components_scratch_bytes, vsseg_components_label, vsseg_keep_largest_component; 8: + vsseg_surface_distances, vsseg_surface_scratch_bytes; 7: + vsseg_dice_pred_bwd_to, vsseg_dice_level_sums, vsseg_dice_tail_sums, vsseg_dice_att_bwd_levels, vsseg_fork_*, vsseg_stream_wait_event; 6: + launch plans with depth -8 (transition kernel) and -9 (gathering marching kernel); 5: vsseg_wgrad march = 2 (compute weight-gradient kernel), + vsseg_conv_to1, vsseg_conv_chain_desc without h_out (the training variant measured no gain and was deleted); 4: + vsseg_conv_chain; 3: the BatchNorm-block-on-load fields (in_bn_*, keep_*, x_bn_*: round-4 experiment, measured a loss, deleted) left the descriptors, depth -7 plans;
+int vsseg_version(void); /* 12: + vsseg_crop_field, vsseg_field_job; 11: + vsseg_crop_affine, vsseg_affine_job; 10: + vsseg_swi_finalize_mirrored, vsseg_crop_job.flip is a three-axis mirror mask (was flip_x); 9: + vsseg_components_scratch_bytes, vsseg_components_label, vsseg_keep_largest_component; 8: + vsseg_surface_distances, vsseg_surface_scratch_bytes; 7: + vsseg_dice_pred_bwd_to, vsseg_dice_level_sums, vsseg_dice_tail_sums, vsseg_dice_att_bwd_levels, vsseg_fork_*, vsseg_stream_wait_event; 6: + launch plans with depth -8 (transition kernel) and -9 (gathering marching kernel); 5: vsseg_wgrad march = 2 (compute weight-gradient kernel), + vsseg_conv_to1, vsseg_conv_chain_desc without h_out (the training variant measured no gain and was deleted); 4: + vsseg_conv_chain; 3: the BatchNorm-block-on-load fields (in_bn_*, keep_*, x_bn_*: round-4 experiment, measured a loss, deleted) left the descriptors, depth -7 plans;
                             * 2: fixed-point accumulators documented + vsseg_fx_status; 1: the buffers below were described as plain doubles */
 
 /* ---- Accumulator buffers are 64-bit FIXED-POINT integers, not doubles ------------------------------------------------------------------
@@ -434,6 +434,39 @@ typedef struct {
 } vsseg_affine_job;
 /* dst[j][rx][ry][rz] for j < njobs (16-byte aligned), one launch for image and label jobs of a whole batch. */
 int vsseg_crop_affine(const vsseg_affine_job* jobs_host, const void* jobs_dev, int32_t njobs, float* dst, const int32_t roi[3], uint64_t seed, void* stream);
+/* Elastic deformation and MR bias field on top of vsseg_crop_affine (ABI version 12): what MONAI users know as Rand3DElastic (in-plane) and RandBiasField.  Both are one smooth
+ * random field over the PATCH, a 2-vector d for the deformation and a scalar b for the bias: a coarse lattice of random control values interpolated by uniform cubic
+ * B-splines, evaluated inside the same gather.
+ *   lattice      n_a = (roi_a - 1) / spacing_a + 4 nodes along axis a (integer division); node id n = (i*n_y + j)*n_z + k (64 bits);
+ *                  r = philox4x32_10(counter = (lo32 n, hi32 n, noise_stream, 1), key = (lo32 seed, hi32 seed))     (fourth counter word 1: the noise uses 0, no counter is shared)
+ *                  c_x, c_y, c_b = fmaf(2, u(r.x | r.y | r.z), -1) in [-1, 1), u as for the noise; r.w is unused.  noise_stream is the field stream too: the image job and the
+ *                label job of one sample carry the same stream and so get the same deformation.
+ *   field        at the output voxel p, per axis: i0 = p_a / spacing_a, f = (p_a mod spacing_a) / spacing_a; the weights
+ *                  B0 = (1-f)^3/6,  B1 = (3f^3 - 6f^2 + 4)/6,  B2 = (-3f^3 + 3f^2 + 3f + 1)/6,  B3 = f^3/6
+ *                apply to the nodes i0 .. i0+3, and F(c)(p) is the tensor-product sum over 4 x 4 x 4 nodes.  d_x = elastic_mag * F(c_x), d_y = elastic_mag * F(c_y), d_z = 0
+ *                (in-plane only, like the rotation: the voxels are 0.4 x 0.4 x 1.5 mm), b = bias_log * F(c_b).  |F| <= 1, so |d| <= elastic_mag (voxels) and |b| <= bias_log.
+ *                The fp32 evaluation order of F is not part of the contract; its error is: |F_fp32 - F_exact| <= 96 * 2^-24 (derived in tests/field_oracle.py).
+ *   coordinates  x' = x + d_x, y' = y + d_y in fp32, then exactly the three fmaf of vsseg_crop_affine on (x', y', z): the deformation acts in patch space, and the matrix
+ *                rotates, zooms and mirrors it with the patch.
+ *   intensity    on the interpolated value v = v * expf(b) (accurate expf), then gain, bias and noise exactly as in vsseg_crop_affine.  Label jobs carry elastic_mag and bias_log = 0.
+ *   zero ranges  with elastic_mag == 0 and bias_log == 0 in every job the launch is bit-identical to vsseg_crop_affine (x + 0, v * expf(0)).
+ *   no folding   elastic_mag <= min(spacing_x, spacing_y) / 4 is required: the derivative of a cubic B-spline expansion is a convex combination of neighbouring control
+ *                differences (each below 2 * elastic_mag) divided by the spacing, so every partial of d is below 2 * elastic_mag / spacing and the in-plane Jacobian
+ *                determinant is above 1 - 4 * elastic_mag / spacing > 0.
+ *   limit        the kernel holds one x-reduced plane of the lattice on chip: n_y * n_z <= 1024, otherwise VSSEG_EINVAL (choose a larger spacing).
+ * Argument checks, on the host copy and before anything is launched: everything vsseg_crop_affine checks, spacing_a >= 1, elastic_mag and bias_log finite and >= 0, the
+ * bound on elastic_mag and the lattice limit.  No atomics: a launch is bit-reproducible run to run. */
+typedef struct {
+  const float* src;     /* the fields of vsseg_affine_job, in its order ... */
+  int32_t sdims[3];
+  int32_t interp;
+  float m[12];
+  float gain, bias, noise_std;
+  uint32_t noise_stream;
+  float elastic_mag;    /* ... then the bound of the control-point displacement, in voxels of the patch */
+  float bias_log;       /* and the bound of the log of the multiplicative bias */
+} vsseg_field_job;
+int vsseg_crop_field(const vsseg_field_job* jobs_host, const void* jobs_dev, int32_t njobs, float* dst, const int32_t roi[3], const int32_t spacing[3], uint64_t seed, void* stream);
 /* NormalizeIntensityd (ref:params/VSparams.py:213): y = (x - mean) / std over all n voxels (population std; std == 0: no
  * division).  acc2 = 2 doubles of device scratch (sum, sum of squares; left filled for inspection). */
 int vsseg_normalize_intensity(const float* x, float* y, int64_t n, double* acc2, void* stream);

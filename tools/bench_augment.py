@@ -1,6 +1,7 @@
-"""Time the augmenting crop (vsseg_crop_affine) beside the plain one (vsseg_crop_flip) at the two training shapes, batch 2 of 384 x 384 x 64 and batch 4 of
-384 x 128 x 128, over cached synthetic 512 x 512 x 120 volumes: rotation 15 degrees and scale +-10 % drawn by PatchSampler's own RandomTail, with and without
-Gaussian noise.  The launches alternate in one process (crop, affine, affine + noise, crop, ...), each timed with its own pair of device events after warm-up.
+"""Time the augmenting crops (vsseg_crop_affine, vsseg_crop_field) beside the plain one (vsseg_crop_flip) at the two training shapes, batch 2 of 384 x 384 x 64 and
+batch 4 of 384 x 128 x 128, over cached synthetic 512 x 512 x 120 volumes: rotation 15 degrees and scale +-10 % drawn by PatchSampler's own RandomTail, with and without
+Gaussian noise; the field launch with the elastic deformation alone (magnitude drawn from [0, 16] voxels, spacing 64 / 64 / 16) and with elastic + bias field (log 0.3) + noise.
+The launches alternate in one process (crop, affine, affine + noise, field, field + bias + noise, crop, ...), each timed with its own pair of device events after warm-up.
 Prints microseconds per launch (median and mean) and GB/s = (bytes written + source bytes inside the footprint, counted once) / median time.
 
     python tools/bench_augment.py [--launches 200] [--warmup 20]
@@ -19,6 +20,7 @@ from vs_seg_amd.data import transforms as T  # noqa: E402
 
 VOLUME = (512, 512, 120)
 SHAPES = [(2, (384, 384, 64)), (4, (384, 128, 128))]
+FIELD = dict(elastic_mag=16.0, bias_field=0.3, field_spacing=64)
 
 
 def footprint_voxels(m, roi, sdims):
@@ -38,43 +40,50 @@ def main():
     lib, stream = L.lib(), torch.cuda.current_stream().cuda_stream
     gen = torch.Generator(device="cuda").manual_seed(0)
     cases = [{"image": torch.randn(VOLUME, device="cuda", generator=gen), "label": (torch.rand(VOLUME, device="cuda", generator=gen) > 0.9).float()} for _ in range(4)]
-    print(f"vsseg_crop_flip vs vsseg_crop_affine on {torch.cuda.get_device_name(0)}: {a.launches} launches each after {a.warmup} warm-up, volumes {VOLUME}, rotation +-15 deg, scale +-10 %")
+    print(f"vsseg_crop_flip vs vsseg_crop_affine vs vsseg_crop_field on {torch.cuda.get_device_name(0)}: {a.launches} launches each after {a.warmup} warm-up, volumes {VOLUME}, rotation +-15 deg, scale +-10 %, "
+          f"field {FIELD}")
+    spacing = T.field_launch_spacing(FIELD["field_spacing"])
     for B, roi in SHAPES:
         per = roi[0] * roi[1] * roi[2]
-        tail = T.RandomTail(roi, 0.5, 0, rotate_deg=15.0, scale=0.1)
+        tail = T.RandomTail(roi, 0.5, 0, rotate_deg=15.0, scale=0.1, **FIELD)
         out = torch.empty((2 * B, *roi), device="cuda")
         # a fixed set of job lists drawn up front, so that the timed loop holds launches only
         sets = []
         for _ in range(8):
-            cj, aj, an = (L.CropJob * (2 * B))(), (L.AffineJob * (2 * B))(), (L.AffineJob * (2 * B))()
+            cj, aj, an, fe, fa = (L.CropJob * (2 * B))(), (L.AffineJob * (2 * B))(), (L.AffineJob * (2 * B))(), (L.FieldJob * (2 * B))(), (L.FieldJob * (2 * B))()
             read_c = read_a = 0
             for b in range(B):
                 flip, start = tail.draw(VOLUME)
                 angle, scale, _, _ = tail.draw_augment()
+                mag, blog = tail.draw_field()
                 m = T.affine_matrix(roi, start, VOLUME[0], flip, angle, scale)
                 read_c += 2 * per
                 read_a += 2 * footprint_voxels(m, roi, VOLUME)
                 for k, key in enumerate(("image", "label")):
                     j = cj[b + k * B]
                     j.src, j.sdims, j.origin, j.flip = cases[b][key].data_ptr(), L.i3(VOLUME), L.i3(start), int(flip)
-                    for js, std in ((aj, 0.0), (an, 0.05)):
+                    for js, std, full in ((aj, 0.0, False), (an, 0.05, False), (fe, 0.0, False), (fa, 0.05, True)):
                         q = js[b + k * B]
                         q.src, q.sdims, q.m, q.interp, q.noise_stream = cases[b][key].data_ptr(), L.i3(VOLUME), (C.c_float * 12)(*m.ravel().tolist()), k, b
                         q.gain, q.bias, q.noise_std = 1.0, 0.0, (std if k == 0 else 0.0)
-            dev = [torch.frombuffer(bytearray(bytes(j)), dtype=torch.uint8).cuda() for j in (cj, aj, an)]
-            sets.append((cj, aj, an, dev, read_c, read_a))
-        kinds = ["crop_flip", "crop_affine", "crop_affine + noise"]
+                        if js is fe or js is fa:
+                            q.elastic_mag, q.bias_log = mag, (blog if full and k == 0 else 0.0)
+            dev = [torch.frombuffer(bytearray(bytes(j)), dtype=torch.uint8).cuda() for j in (cj, aj, an, fe, fa)]
+            sets.append(((cj, aj, an, fe, fa), dev, read_c, read_a))
+        kinds = ["crop_flip", "crop_affine", "crop_affine + noise", "crop_field elastic", "crop_field el+bias+noise"]
 
         def launch(kind, s):
-            cj, aj, an, dev, _, _ = s
+            host, dev, _, _ = s
             if kind == 0:
                 L.check(lib.vsseg_crop_flip(dev[0].data_ptr(), 2 * B, out.data_ptr(), L.i3(roi), stream))
+            elif kind < 3:
+                L.check(lib.vsseg_crop_affine(host[kind], dev[kind].data_ptr(), 2 * B, out.data_ptr(), L.i3(roi), 12345, stream))
             else:
-                L.check(lib.vsseg_crop_affine(aj if kind == 1 else an, dev[kind].data_ptr(), 2 * B, out.data_ptr(), L.i3(roi), 12345, stream))
+                L.check(lib.vsseg_crop_field(host[kind], dev[kind].data_ptr(), 2 * B, out.data_ptr(), L.i3(roi), L.i3(spacing), 12345, stream))
 
         ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.launches)] for _ in kinds]
         for i in range(a.warmup + a.launches):
-            for kind in range(3):
+            for kind in range(len(kinds)):
                 if i >= a.warmup:
                     ev[kind][i - a.warmup][0].record()
                 launch(kind, sets[i % len(sets)])
@@ -85,9 +94,9 @@ def main():
         print(f"batch {B} of {roi}: {written / 1e6:.1f} MB written per launch")
         for kind, name in enumerate(kinds):
             us = np.array([e0.elapsed_time(e1) * 1e3 for e0, e1 in ev[kind]])
-            read = 4 * np.mean([s[4 if kind == 0 else 5] for s in sets])
+            read = 4 * np.mean([s[2 if kind == 0 else 3] for s in sets])
             med = float(np.median(us))
-            print(f"  {name:<20s} median {med:8.1f} us   mean {us.mean():8.1f} us   min {us.min():8.1f} us   {(written + read) / med / 1e3:7.1f} GB/s  ({read / 1e6:.1f} MB source footprint)")
+            print(f"  {name:<24s} median {med:8.1f} us   mean {us.mean():8.1f} us   min {us.min():8.1f} us   {(written + read) / med / 1e3:7.1f} GB/s  ({read / 1e6:.1f} MB source footprint)")
 
 
 if __name__ == "__main__":

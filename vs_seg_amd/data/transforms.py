@@ -7,7 +7,9 @@ Random tail (per sample, per epoch):
 
 Optional training augmentation (off by default; this project's own conventions — MONAI's RandAffined / RandScaleIntensityd /
 RandShiftIntensityd / RandGaussianNoised are the transforms it corresponds to): an in-plane rotation and scaling about the centre
-of the crop window, a gain, a bias and Gaussian noise, all applied by ONE `vsseg_crop_affine` launch in place of the crop.
+of the crop window, a gain, a bias and Gaussian noise, all applied by ONE `vsseg_crop_affine` launch in place of the crop.  Two more families
+(MONAI's Rand3DElastic / RandBiasField, TorchIO's RandomElasticDeformation) are one smooth random B-spline field over the patch, a 2-vector for an
+in-plane elastic deformation and a scalar for a multiplicative MR bias field; with either on, the launch is `vsseg_crop_field`, the same gather with the field.
 
 The numpy restatement of MONAI 0.4.0's arithmetic that checks the HIP path (`vsseg_normalize_intensity`, `vsseg_crop_flip`) is test
 infrastructure and lives in `oracle/data_oracle.py` (parity unpinned — MONAI is not installed).  `PatchSampler`
@@ -56,6 +58,31 @@ def check_augment(rotate_deg=0.0, scale=0.0, intensity_scale=0.0, intensity_shif
     return a
 
 
+FIELD_KEYS = ("elastic_mag", "bias_field", "field_spacing")
+
+
+def check_field_augment(elastic_mag=0.0, bias_field=0.0, field_spacing=64) -> Dict[str, float]:
+    """The two field ranges as floats (0 = off) and the in-plane control-point spacing as an int; ValueError for a negative or non-finite range, a spacing that is no
+    integer >= 1, and elastic_mag > field_spacing / 4 (beyond it the deformation could fold: include/vsseg_hip.h)."""
+    f = dict(elastic_mag=float(elastic_mag), bias_field=float(bias_field))
+    for k, v in f.items():
+        if not (np.isfinite(v) and v >= 0.0):
+            raise ValueError(f"augmentation range {k} = {v}: must be finite and >= 0")
+    sp = float(field_spacing)
+    if not (np.isfinite(sp) and sp >= 1.0 and sp == int(sp)):
+        raise ValueError(f"field_spacing = {field_spacing}: must be an integer >= 1 (voxels)")
+    if f["elastic_mag"] > sp / 4.0:
+        raise ValueError(f"elastic_mag = {f['elastic_mag']}: at most field_spacing / 4 = {sp / 4.0} (the deformation must not fold)")
+    f["field_spacing"] = int(sp)
+    return f
+
+
+def field_launch_spacing(field_spacing: int) -> Tuple[int, int, int]:
+    """(S, S, max(1, (S + 2) // 4)): the lattice is roughly isotropic in millimetres over 0.4 x 0.4 x 1.5 mm voxels."""
+    s = int(field_spacing)
+    return s, s, max(1, (s + 2) // 4)
+
+
 def affine_matrix(roi: Sequence[int], start: Sequence[int], sdim_x: int, flip: bool, angle: float = 0.0, scale: float = 1.0) -> np.ndarray:
     """fp32 3x4 matrix of `vsseg_affine_job.m`: output index p -> source voxel coordinate
         s = c_src + R_z(angle) diag(1/scale, 1/scale, 1) (p - c_roi),   c_roi = (roi - 1) / 2,   c_src = start + c_roi
@@ -81,14 +108,20 @@ class RandomTail:
     With a non-zero augmentation range a THIRD state is seeded from `R` after those two, so the flip and crop draws are the same with
     augmentation on or off.  `draw_augment()` draws per sample, in this order and only for the families whose range is non-zero:
     angle ~ U(-rotate_deg, rotate_deg), scale factor 1 + U(-scale, scale), gain 1 + U(-intensity_scale, intensity_scale),
-    bias ~ U(-intensity_shift, intensity_shift); `draw_noise_seed()` draws one randint(2^32) per batch when noise_std != 0."""
+    bias ~ U(-intensity_shift, intensity_shift); `draw_noise_seed()` draws one randint(2^32) per batch when noise_std != 0.
+
+    With a non-zero field range (`elastic_mag`, `bias_field`) a FOURTH state is seeded from `R` after those, so the flip, crop and five-family draws are the same with
+    the fields on or off.  `draw_field_seed()` draws one randint(2^32) per batch (the high half of the launch seed: the lattice differs from batch to batch, noise or no
+    noise); `draw_field()` draws per sample, in this order and only for the families that are on: a ~ U(0, elastic_mag), beta ~ U(0, bias_field)."""
 
     def __init__(self, roi: Sequence[int], flip_prob: Optional[float] = 0.5, seed: Optional[int] = None, rotate_deg: float = 0.0, scale: float = 0.0,
-                 intensity_scale: float = 0.0, intensity_shift: float = 0.0, noise_std: float = 0.0):
+                 intensity_scale: float = 0.0, intensity_shift: float = 0.0, noise_std: float = 0.0, elastic_mag: float = 0.0, bias_field: float = 0.0, field_spacing: int = 64):
         self.roi = tuple(int(r) for r in roi)
         self.flip_prob = flip_prob
         self.augment = check_augment(rotate_deg, scale, intensity_scale, intensity_shift, noise_std)
         self.augmenting = any(v != 0.0 for v in self.augment.values())
+        self.field = check_field_augment(elastic_mag, bias_field, field_spacing)
+        self.fielding = self.field["elastic_mag"] != 0.0 or self.field["bias_field"] != 0.0
         self.set_random_state(seed)
 
     def set_random_state(self, seed: Optional[int] = None):
@@ -96,6 +129,7 @@ class RandomTail:
         self._flipR = np.random.RandomState(R.randint(MAX_SEED, dtype="uint32")) if self.flip_prob is not None else None
         self._cropR = np.random.RandomState(R.randint(MAX_SEED, dtype="uint32"))
         self._augR = np.random.RandomState(R.randint(MAX_SEED, dtype="uint32")) if self.augmenting else None
+        self._fieldR = np.random.RandomState(R.randint(MAX_SEED, dtype="uint32")) if self.fielding else None
         return self
 
     def draw(self, shape: Sequence[int]) -> Tuple[bool, Tuple[int, int, int]]:
@@ -110,6 +144,14 @@ class RandomTail:
 
     def draw_noise_seed(self) -> int:
         return int(self._augR.randint(MAX_SEED, dtype="uint32")) if self.augment["noise_std"] != 0.0 else 0
+
+    def draw_field_seed(self) -> int:
+        return int(self._fieldR.randint(MAX_SEED, dtype="uint32")) if self.fielding else 0
+
+    def draw_field(self) -> Tuple[float, float]:
+        """(elastic_mag in voxels, bias_log) of one sample."""
+        f, u = self.field, (lambda r: float(self._fieldR.uniform(0.0, r)) if r != 0.0 else 0.0)
+        return u(f["elastic_mag"]), u(f["bias_field"])
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -149,21 +191,25 @@ class PatchSampler:
 
     A non-zero `rotate_deg`, `scale`, `intensity_scale`, `intensity_shift` or `noise_std` (see RandomTail) replaces that launch by one
     `vsseg_crop_affine` launch: the image is resampled trilinearly and gets gain, bias and noise, the label goes through the same matrix
-    with nearest-neighbour lookup.  `last_augment` then holds, per sample, what a test needs to replay the launch."""
+    with nearest-neighbour lookup.  `last_augment` then holds, per sample, what a test needs to replay the launch.
+
+    A non-zero `elastic_mag` (voxels) or `bias_field` (log of the factor) makes that launch `vsseg_crop_field` with the lattice spacing
+    `field_launch_spacing(field_spacing)`: image and label of a sample share the deformation, the bias field multiplies the image only.  `last_augment` then
+    also holds `elastic_mag`, `bias_log` (fp32) and `spacing` per sample.  With both 0 the sampler takes the paths above, launch for launch."""
 
     def __init__(self, cases: List[Dict], roi: Sequence[int], flip_prob: Optional[float] = 0.5, seed: Optional[int] = 0, rotate_deg: float = 0.0, scale: float = 0.0,
-                 intensity_scale: float = 0.0, intensity_shift: float = 0.0, noise_std: float = 0.0):
+                 intensity_scale: float = 0.0, intensity_shift: float = 0.0, noise_std: float = 0.0, elastic_mag: float = 0.0, bias_field: float = 0.0, field_spacing: int = 64):
         self.cases, self.roi = cases, tuple(int(r) for r in roi)
-        self.tail = RandomTail(self.roi, flip_prob, seed, rotate_deg, scale, intensity_scale, intensity_shift, noise_std)
+        self.tail = RandomTail(self.roi, flip_prob, seed, rotate_deg, scale, intensity_scale, intensity_shift, noise_std, elastic_mag, bias_field, field_spacing)
         self.lib = L.lib()
         self.last_draws: List[Tuple[bool, Tuple[int, int, int]]] = []
-        self.last_augment: List[Dict] = []  # per sample: m (fp32 3x4), gain, bias, noise_std (fp32), noise_stream, seed
+        self.last_augment: List[Dict] = []  # per sample: m (fp32 3x4), gain, bias, noise_std (fp32), noise_stream, seed (+ elastic_mag, bias_log (fp32), spacing with a field)
 
     def __len__(self):
         return len(self.cases)
 
     def sample(self, indices: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:
-        if self.tail.augmenting:
+        if self.tail.augmenting or self.tail.fielding:
             return self._sample_affine(indices)
         dev = self.cases[indices[0]]["image"].device
         B = len(indices)
@@ -186,16 +232,21 @@ class PatchSampler:
     def _sample_affine(self, indices: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:
         dev = self.cases[indices[0]]["image"].device
         B = len(indices)
-        jobs = (L.AffineJob * (2 * B))()
+        fielding = self.tail.fielding  # one vsseg_crop_field launch instead of one vsseg_crop_affine launch
+        jobs = ((L.FieldJob if fielding else L.AffineJob) * (2 * B))()
+        spacing = field_launch_spacing(self.tail.field["field_spacing"])
         self.last_draws, self.last_augment = [], []
-        seed = self.tail.draw_noise_seed()
+        seed = self.tail.draw_noise_seed() + (self.tail.draw_field_seed() << 32)
         for b, i in enumerate(indices):
             case = self.cases[i]
             shape = tuple(case["image"].shape)
             flip, start = self.tail.draw(shape)
-            angle, scale, gain, bias = self.tail.draw_augment()
+            angle, scale, gain, bias = self.tail.draw_augment() if self.tail.augmenting else (0.0, 1.0, 1.0, 0.0)
             m = affine_matrix(self.roi, start, shape[0], flip, angle, scale)
             aug = dict(m=m, gain=np.float32(gain), bias=np.float32(bias), noise_std=np.float32(self.tail.augment["noise_std"]), noise_stream=b, seed=seed)
+            if fielding:
+                mag, blog = self.tail.draw_field()
+                aug.update(elastic_mag=np.float32(mag), bias_log=np.float32(blog), spacing=spacing)
             self.last_draws.append((flip, start))
             self.last_augment.append(aug)
             for k, key in enumerate(("image", "label")):
@@ -205,9 +256,15 @@ class PatchSampler:
                     j.interp, j.gain, j.bias, j.noise_std = L.INTERP_TRILINEAR, float(aug["gain"]), float(aug["bias"]), float(aug["noise_std"])
                 else:
                     j.interp, j.gain, j.bias, j.noise_std = L.INTERP_NEAREST, 1.0, 0.0, 0.0
+                if fielding:  # the label follows the deformation and knows no bias field
+                    j.elastic_mag, j.bias_log = float(aug["elastic_mag"]), float(aug["bias_log"]) if key == "image" else 0.0
         jbuf = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(dev)
         out = torch.empty((2, B, 1, *self.roi), dtype=torch.float32, device=dev)
-        L.check(self.lib.vsseg_crop_affine(jobs, jbuf.data_ptr(), 2 * B, out.data_ptr(), L.i3(self.roi), seed, torch.cuda.current_stream().cuda_stream), "crop_affine")
+        stream = torch.cuda.current_stream().cuda_stream
+        if fielding:
+            L.check(self.lib.vsseg_crop_field(jobs, jbuf.data_ptr(), 2 * B, out.data_ptr(), L.i3(self.roi), L.i3(spacing), seed, stream), "crop_field")
+        else:
+            L.check(self.lib.vsseg_crop_affine(jobs, jbuf.data_ptr(), 2 * B, out.data_ptr(), L.i3(self.roi), seed, stream), "crop_affine")
         jbuf.record_stream(torch.cuda.current_stream())
         return out[0], out[1]
 

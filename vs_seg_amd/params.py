@@ -32,7 +32,7 @@ from .metrics import compute_surface_distances, voxel_spacing
 from .postprocess import keep_largest_component
 from . import parallel as DP
 from .data import nifti
-from .data.transforms import AUGMENT_KEYS, PatchSampler, check_augment, epoch_batches, load_case
+from .data.transforms import AUGMENT_KEYS, FIELD_KEYS, PatchSampler, check_augment, check_field_augment, epoch_batches, load_case
 
 HP = dict(
     channels=(16, 32, 48, 64, 80, 96),
@@ -50,14 +50,14 @@ class CachedLoader:
     the reference's first-epoch log line divides one by the other (ref:params/VSparams.py:466)."""
 
     def __init__(self, cases: List[Dict], roi: Optional[Sequence[int]], batch_size: int, shuffle: bool, flip_prob: Optional[float], seed: int = 0, pad: Optional[bool] = None,
-                 augment: Optional[Dict[str, float]] = None):
+                 augment: Optional[Dict[str, float]] = None, field_augment: Optional[Dict[str, float]] = None):
         self.cases, self.batch_size, self.shuffle = cases, batch_size, shuffle
         # equal step counts on every rank (wrap-around padding) only where every step issues a collective: the shuffled training loader.
         # Validation / test loaders give rank r exactly shard_indices(n, r, world) — a padded case would be counted twice in their sums
         self.pad = shuffle if pad is None else pad
         self.rank, self.world = DP.get_rank(), DP.world_size()
         # every rank shuffles with the SAME stream (the shards must partition one permutation) but draws its own flips / crops
-        self.sampler = PatchSampler(cases, roi, flip_prob, seed + 7919 * self.rank, **(augment or {})) if roi is not None else None
+        self.sampler = PatchSampler(cases, roi, flip_prob, seed + 7919 * self.rank, **(augment or {}), **(field_augment or {})) if roi is not None else None
         self._order = np.random.RandomState(seed)
 
     def __len__(self):
@@ -103,10 +103,14 @@ class VSparams:
         parser.add_argument("--aug_intensity_scale", type=float, default=0.0, metavar="FRAC", help="training augmentation: multiply the image of every training patch by a gain drawn from [1 - FRAC, 1 + FRAC] (0: off)")
         parser.add_argument("--aug_intensity_shift", type=float, default=0.0, metavar="STD", help="training augmentation: add a bias drawn from [-STD, STD] to the image of every training patch, in standard deviations of the normalised image (0: off)")
         parser.add_argument("--aug_noise_std", type=float, default=0.0, metavar="STD", help="training augmentation: add Gaussian noise of this standard deviation to the image of every training patch (0: off)")
+        parser.add_argument("--aug_elastic_mag", type=float, default=0.0, metavar="VOX", help="training augmentation: deform every training patch in-plane by a smooth random B-spline field whose control points move by at most a length drawn from [0, VOX] voxels; the peak displacement of the field is typically about half of it; at most aug_field_spacing / 4 (0: off)")
+        parser.add_argument("--aug_bias_field", type=float, default=0.0, metavar="LOG", help="training augmentation: multiply the image of every training patch by exp of a smooth random B-spline field whose amplitude is drawn from [0, LOG] (the MR bias field; 0: off)")
+        parser.add_argument("--aug_field_spacing", type=int, default=64, metavar="VOX", help="in-plane control-point spacing of the two B-spline fields in voxels (64: about 26 mm; along z a quarter of it)")
         args = parser.parse_args(argv)
         try:
             tta_masks(args.tta_flips, args.tta_average)
             augment = check_augment(*(getattr(args, "aug_" + k) for k in AUGMENT_KEYS))
+            field = check_field_augment(args.aug_elastic_mag, args.aug_bias_field, args.aug_field_spacing)
         except ValueError as e:
             parser.error(str(e))
 
@@ -132,6 +136,7 @@ class VSparams:
         self.keep_largest_component, self.component_connectivity = args.keep_largest_component, args.component_connectivity
         self.tta_flips, self.tta_average = tuple(args.tta_flips or ()), args.tta_average
         self.aug_rotate_deg, self.aug_scale, self.aug_intensity_scale, self.aug_intensity_shift, self.aug_noise_std = (augment[k] for k in AUGMENT_KEYS)
+        self.aug_elastic_mag, self.aug_bias_field, self.aug_field_spacing = (field[k] for k in FIELD_KEYS)
         self.results_folder_path = os.path.join(self.data_root, "results", "debug" if self.debug else args.results_folder_name)
         self.logs_path = os.path.join(self.results_folder_path, "logs")
         self.model_path = os.path.join(self.results_folder_path, "model")
@@ -167,7 +172,8 @@ class VSparams:
                   "epochs_with_const_lr", "lr_divisor", "weight_decay", "num_epochs", "val_interval", "model", "sliding_window_inferer_roi_size", "attention", "hardness",
                   "results_folder_path", "export_inferred_segmentations", "compute_dtype") + (("surface_metrics",) if self.surface_metrics else ()) + (
                       ("keep_largest_component", "component_connectivity") if self.keep_largest_component else ()) + (("tta_flips", "tta_average") if self.tta_flips else ()) + (
-                          tuple("aug_" + k for k in AUGMENT_KEYS) if any(self.augment.values()) else ()):
+                          tuple("aug_" + k for k in AUGMENT_KEYS) if any(self.augment.values()) else ()) + (
+                              ("aug_elastic_mag", "aug_bias_field", "aug_field_spacing") if self.aug_elastic_mag or self.aug_bias_field else ()):
             log("{:<34s} {}".format(k + " =", getattr(self, k)))
         log("-" * 10)
 
@@ -193,16 +199,24 @@ class VSparams:
         """The training augmentation ranges under PatchSampler's argument names (all 0: off)."""
         return {k: getattr(self, "aug_" + k) for k in AUGMENT_KEYS}
 
+    @property
+    def field_augment(self) -> Dict[str, float]:
+        """The two B-spline field ranges and their spacing under PatchSampler's argument names (both ranges 0: off)."""
+        return dict(elastic_mag=self.aug_elastic_mag, bias_field=self.aug_bias_field, field_spacing=self.aug_field_spacing)
+
     def get_transforms(self):
         """The three chains as plain descriptions; `cache_transformed_*_data` executes them (deterministic head cached in
-        HBM, random tail per batch).  The augmentation flags reach the training chain only."""
+        HBM, random tail per batch).  The augmentation flags reach the training chain only: the five ranges under "augment", the field ranges under "field_augment"."""
         head = ["LoadNifti", "AddChannel", "Orientation(RAS)", "NormalizeIntensity(image)"]
-        a = self.augment
-        aug = ([f"RandAffine(aug_rotate_deg={a['rotate_deg']}, aug_scale={a['scale']}, axis=z, about the crop centre)"] if a["rotate_deg"] or a["scale"] else []) + (
+        a, f = self.augment, self.field_augment
+        # in the order the launch applies them: the deformation acts in patch space, the matrix after it; the bias field multiplies the interpolated value before the gain
+        aug = ([f"RandElastic(aug_elastic_mag={f['elastic_mag']}, aug_field_spacing={f['field_spacing']}, in-plane, cubic B-spline)"] if f["elastic_mag"] else []) + (
+            [f"RandAffine(aug_rotate_deg={a['rotate_deg']}, aug_scale={a['scale']}, axis=z, about the crop centre)"] if a["rotate_deg"] or a["scale"] else []) + (
+            [f"RandBiasField(aug_bias_field={f['bias_field']}, aug_field_spacing={f['field_spacing']})"] if f["bias_field"] else []) + (
             [f"RandScaleIntensity(aug_intensity_scale={a['intensity_scale']})"] if a["intensity_scale"] else []) + (
             [f"RandShiftIntensity(aug_intensity_shift={a['intensity_shift']})"] if a["intensity_shift"] else []) + (
             [f"RandGaussianNoise(aug_noise_std={a['noise_std']})"] if a["noise_std"] else [])
-        train = dict(chain=head + [f"SpatialPad({self.pad_crop_shape})", "RandFlip(p=0.5, axis=0)", f"RandSpatialCrop({self.pad_crop_shape})"] + aug, pad=self.pad_crop_shape, roi=self.pad_crop_shape, flip_prob=0.5, augment=a)
+        train = dict(chain=head + [f"SpatialPad({self.pad_crop_shape})", "RandFlip(p=0.5, axis=0)", f"RandSpatialCrop({self.pad_crop_shape})"] + aug, pad=self.pad_crop_shape, roi=self.pad_crop_shape, flip_prob=0.5, augment=a, field_augment=f)
         val = dict(chain=head + [f"SpatialPad({self.pad_crop_shape})", f"RandSpatialCrop({self.pad_crop_shape})"], pad=self.pad_crop_shape, roi=self.pad_crop_shape, flip_prob=None)
         test = dict(chain=head, pad=None, roi=None, flip_prob=None)
         return train, val, test
@@ -240,7 +254,7 @@ class VSparams:
     def _cache(self, files, tf, batch_size, shuffle, what):
         self.logger.info(f"Caching {what} data set...")
         cases = [load_case(fd, tf["pad"], self.device) for fd in files]
-        return CachedLoader(cases, tf["roi"], batch_size, shuffle, tf["flip_prob"], seed=0, augment=tf.get("augment"))  # the crop/flip stream is decorrelated per rank inside CachedLoader
+        return CachedLoader(cases, tf["roi"], batch_size, shuffle, tf["flip_prob"], seed=0, augment=tf.get("augment"), field_augment=tf.get("field_augment"))  # the crop/flip stream is decorrelated per rank inside CachedLoader
 
     def cache_transformed_train_data(self, train_files, train_transforms):
         return self._cache(train_files, train_transforms, self.train_batch_size, True, "training")
