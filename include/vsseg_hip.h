@@ -467,6 +467,56 @@ typedef struct {
   float bias_log;       /* and the bound of the log of the multiplicative bias */
 } vsseg_field_job;
 int vsseg_crop_field(const vsseg_field_job* jobs_host, const void* jobs_dev, int32_t njobs, float* dst, const int32_t roi[3], const int32_t spacing[3], uint64_t seed, void* stream);
+/* Appearance augmentation of the image patches of a training batch (ABI version 13), applied AFTER the crop launch (vsseg_crop_flip, _affine or _field) in the fixed order
+ * blur -> low resolution -> contrast -> gamma.  Blur and low resolution read in-plane neighbours of the resampled patch and contrast and gamma need statistics of the whole
+ * patch, so none of them fits into the gather.  Both filters act in-plane only (x and y), like the rotation, the zoom and the elastic field: the voxels are 0.4 x 0.4 x 1.5 mm.
+ *
+ * vsseg_patch_filter: random Gaussian blur and simulated low-resolution acquisition.  src, dst and scratch are [njobs][rx][ry][rz] fp32 with z contiguous, 16-byte aligned,
+ * src != dst; job j reads patch j of src (and of scratch) and writes patch j of dst, nothing else.
+ *   reflect      reflect(i, n) is the edge-repeating reflection (..., 1, 0 | 0, 1, ..., n-1 | n-1, n-2, ...) of period 2n: m = i mod 2n (0 <= m < 2n), m < n ? m : 2n-1-m.
+ *                It is defined for every i, because the roi may be shorter than the radius.  The halo of a job comes from the reflection alone: no address outside the
+ *                job's own patch is formed or read.
+ *   blur         radius R = `radius` (0: no blur), half-taps w_k = taps[k], k = 0..R, with w_0 + 2 sum_{k>=1} w_k = 1.  u = G_y(G_x(v)) with
+ *                  G_a(v)[p] = sum_{k=-R..R} w_|k| * v[reflect(p_a + k, roi_a)]                (the other two coordinates of p unchanged)
+ *                G_x(v) is rounded to fp32 before G_y reads it; each sum is accumulated in fp32, its order is not part of the contract (the error of a sum of 2R+1 terms
+ *                is derived in tests/appearance_oracle.py).  The caller makes the taps: R = ceil(3 sigma) <= 5, w_k proportional to exp(-k^2 / (2 sigma^2)).
+ *   low res      reads u (v when radius == 0).  n_a = coarse[a] samples along in-plane axis a (n_a == roi_a on both axes: no low resolution).  Coarse sample i sits at the
+ *                source index q_a(i) = floor((2i + 1) * roi_a / (2 n_a)) (integer arithmetic).  Output index p has the coarse coordinate, in fp32 with a correctly
+ *                rounded division,
+ *                  t = clamp(((p + 0.5) * n_a) / roi_a - 0.5, 0, n_a - 1),   i0 = floor(t), i1 = min(i0 + 1, n_a - 1), phi = t - i0
+ *                (an axis with n_a == roi_a takes i0 = i1 = p, phi = 0 without evaluating t).  With (i0, i1, phi_x) along x and (j0, j1, phi_y) along y the value is
+ *                  lo = fmaf(phi_y, u[q_x(i0)][q_y(j1)] - u[q_x(i0)][q_y(j0)], u[q_x(i0)][q_y(j0)]),   hi = the same at q_x(i1),   out = fmaf(phi_x, hi - lo, lo)
+ *                at the output's own z: nearest-neighbour down-sampling to n_x x n_y, bilinear up-sampling back.  n_a == roi_a returns u bit-exactly.
+ *   neither      a job with radius == 0 and coarse == roi in-plane is a plain copy, bit for bit.
+ *   launches     one kernel blurs (or copies); a second one, launched only when a job has low resolution, gathers.  A job with both families passes u through its patch of
+ *                `scratch`, which may be null when no job has both (VSSEG_EINVAL otherwise).  No atomics: a launch is bit-reproducible run to run.
+ * Argument checks, on the host copy and before anything is launched (the entry point never reads device memory, synchronises or allocates): no null pointers, src != dst,
+ * njobs >= 1, 1 <= roi_a <= 65535, 16-byte alignment, 0 <= radius <= 5, with radius > 0 finite taps with |w_0 + 2 sum w_k - 1| <= 1e-5, 1 <= coarse_a <= roi_a. */
+typedef struct {
+  int32_t radius;       /* 0: no blur */
+  float taps[6];        /* w_0 .. w_radius */
+  int32_t coarse[2];    /* n_x, n_y; == roi in-plane: no low resolution */
+} vsseg_filter_job;
+int vsseg_patch_filter(const vsseg_filter_job* jobs_host, const void* jobs_dev, int32_t njobs, const float* src, float* dst, float* scratch, const int32_t roi[3], void* stream);
+/* vsseg_patch_tone: contrast about the mean with the value range preserved (batchgenerators' ContrastAugmentation with preserve_range) and a gamma curve over the value range
+ * (MONAI's RandAdjustContrast), in place on x = [njobs][n] fp32.  A job with contrast == 1 and gamma == 1 is left untouched (its stats are set to 0); every other job:
+ *   pass 1       mn = min, mx = max, S = sum of its n values.  S is an fp64 sum over a FIXED assignment of elements to VSSEG_TONE_SHARDS shards: element i belongs to chunk
+ *                i / 1024, chunk c to shard c mod VSSEG_TONE_SHARDS; the shards are combined in a fixed order.  No floating-point atomics: a launch is bit-reproducible
+ *                run to run.  `work` is device scratch of njobs * VSSEG_TONE_SHARDS * 3 doubles (S, mn, mx of every shard); it needs no initialisation.
+ *   statistics   mu = (float)(S / n);  stats[4j .. 4j+3] = {mn, mx, mu, 0} is left filled for inspection, like acc2 of vsseg_normalize_intensity.
+ *   pass 2       with c = contrast, g = gamma and the contrast map
+ *                  T(x) = fminf(fmaxf(fmaf(x - mu, c, mu), mn), mx)   (x - mu rounded to fp32),        T(x) = x when c == 1
+ *                a = T(mn), b = T(mx), r = b - a, y = T(x);  out = y when g == 1, otherwise
+ *                  out = fmaf(powf((y - a) / (r + 1e-7f), g), r, a)             (accurate powf and division)
+ *                A constant patch (r = 0) comes out unchanged and finite.
+ * nnU-Net rescales the result of its gamma transform to the mean and standard deviation the patch had before (retain_stats); that is deliberately left out: it would add
+ * another reduction pass over the patch.  The inverted-image gamma variant is out of scope.
+ * Argument checks, on the host copy and before anything is launched: no null pointers, njobs >= 1, n >= 1, contrast and gamma finite and in (0, 2). */
+#define VSSEG_TONE_SHARDS 128
+typedef struct {
+  float contrast, gamma;  /* 1, 1: the job is left untouched */
+} vsseg_tone_job;
+int vsseg_patch_tone(const vsseg_tone_job* jobs_host, const void* jobs_dev, int32_t njobs, float* x, int64_t n, float* stats, double* work, void* stream);
 /* NormalizeIntensityd (ref:params/VSparams.py:213): y = (x - mean) / std over all n voxels (population std; std == 0: no
  * division).  acc2 = 2 doubles of device scratch (sum, sum of squares; left filled for inspection). */
 int vsseg_normalize_intensity(const float* x, float* y, int64_t n, double* acc2, void* stream);

@@ -3,6 +3,9 @@ batch 4 of 384 x 128 x 128, over cached synthetic 512 x 512 x 120 volumes: rotat
 Gaussian noise; the field launch with the elastic deformation alone (magnitude drawn from [0, 16] voxels, spacing 64 / 64 / 16) and with elastic + bias field (log 0.3) + noise.
 The launches alternate in one process (crop, affine, affine + noise, field, field + bias + noise, crop, ...), each timed with its own pair of device events after warm-up.
 Prints microseconds per launch (median and mean) and GB/s = (bytes written + source bytes inside the footprint, counted once) / median time.
+In the same loop, alternating with them: the appearance launches on the image half of the batch, every sample hit (sigma from [0.75, 1.5], resolution factor from [0.5, 1],
+contrast +-25 %, gamma +-30 %): vsseg_patch_filter with blur alone, low resolution alone and both (algorithmic bytes: one read and one write of the image batch), and
+vsseg_patch_tone with contrast alone and contrast + gamma (one read for the statistics, one read and one write for the map).
 
     python tools/bench_augment.py [--launches 200] [--warmup 20]
 """
@@ -21,6 +24,7 @@ from vs_seg_amd.data import transforms as T  # noqa: E402
 VOLUME = (512, 512, 120)
 SHAPES = [(2, (384, 384, 64)), (4, (384, 128, 128))]
 FIELD = dict(elastic_mag=16.0, bias_field=0.3, field_spacing=64)
+APPEARANCE = dict(blur_sigma=1.5, lowres=0.5, contrast=0.25, gamma=0.3, appearance_prob=1.0)
 
 
 def footprint_voxels(m, roi, sdims):
@@ -41,22 +45,30 @@ def main():
     gen = torch.Generator(device="cuda").manual_seed(0)
     cases = [{"image": torch.randn(VOLUME, device="cuda", generator=gen), "label": (torch.rand(VOLUME, device="cuda", generator=gen) > 0.9).float()} for _ in range(4)]
     print(f"vsseg_crop_flip vs vsseg_crop_affine vs vsseg_crop_field on {torch.cuda.get_device_name(0)}: {a.launches} launches each after {a.warmup} warm-up, volumes {VOLUME}, rotation +-15 deg, scale +-10 %, "
-          f"field {FIELD}")
+          f"field {FIELD}; vsseg_patch_filter and vsseg_patch_tone with {APPEARANCE}")
     spacing = T.field_launch_spacing(FIELD["field_spacing"])
     for B, roi in SHAPES:
         per = roi[0] * roi[1] * roi[2]
-        tail = T.RandomTail(roi, 0.5, 0, rotate_deg=15.0, scale=0.1, **FIELD)
+        tail = T.RandomTail(roi, 0.5, 0, rotate_deg=15.0, scale=0.1, **FIELD, **APPEARANCE)
         out = torch.empty((2 * B, *roi), device="cuda")
+        filtered, scratch = torch.empty((B, *roi), device="cuda"), torch.empty((B, *roi), device="cuda")  # the filter reads the image half of `out`; the tone maps `filtered`
+        stats, work = torch.empty((B, 4), device="cuda"), torch.empty((B, L.TONE_SHARDS, 3), dtype=torch.float64, device="cuda")
         # a fixed set of job lists drawn up front, so that the timed loop holds launches only
         sets = []
         for _ in range(8):
             cj, aj, an, fe, fa = (L.CropJob * (2 * B))(), (L.AffineJob * (2 * B))(), (L.AffineJob * (2 * B))(), (L.FieldJob * (2 * B))(), (L.FieldJob * (2 * B))()
+            pb, pl, pbl, tc, tcg = (L.FilterJob * B)(), (L.FilterJob * B)(), (L.FilterJob * B)(), (L.ToneJob * B)(), (L.ToneJob * B)()
             read_c = read_a = 0
             for b in range(B):
                 flip, start = tail.draw(VOLUME)
                 angle, scale, _, _ = tail.draw_augment()
                 mag, blog = tail.draw_field()
                 m = T.affine_matrix(roi, start, VOLUME[0], flip, angle, scale)
+                sigma, f, con, gam = tail.draw_appearance()
+                taps, coarse = T.blur_taps(sigma), T.coarse_size(roi, f)
+                for js, w, n in ((pb, taps, roi[:2]), (pl, taps[:0], coarse), (pbl, taps, coarse)):
+                    js[b].radius, js[b].taps, js[b].coarse = max(len(w) - 1, 0), (C.c_float * 6)(*w.tolist()), (C.c_int32 * 2)(*n)
+                tc[b].contrast, tc[b].gamma, tcg[b].contrast, tcg[b].gamma = con, 1.0, con, gam
                 read_c += 2 * per
                 read_a += 2 * footprint_voxels(m, roi, VOLUME)
                 for k, key in enumerate(("image", "label")):
@@ -68,9 +80,10 @@ def main():
                         q.gain, q.bias, q.noise_std = 1.0, 0.0, (std if k == 0 else 0.0)
                         if js is fe or js is fa:
                             q.elastic_mag, q.bias_log = mag, (blog if full and k == 0 else 0.0)
-            dev = [torch.frombuffer(bytearray(bytes(j)), dtype=torch.uint8).cuda() for j in (cj, aj, an, fe, fa)]
-            sets.append(((cj, aj, an, fe, fa), dev, read_c, read_a))
-        kinds = ["crop_flip", "crop_affine", "crop_affine + noise", "crop_field elastic", "crop_field el+bias+noise"]
+            dev = [torch.frombuffer(bytearray(bytes(j)), dtype=torch.uint8).cuda() for j in (cj, aj, an, fe, fa, pb, pl, pbl, tc, tcg)]
+            sets.append(((cj, aj, an, fe, fa, pb, pl, pbl, tc, tcg), dev, read_c, read_a))
+        kinds = ["crop_flip", "crop_affine", "crop_affine + noise", "crop_field elastic", "crop_field el+bias+noise",
+                 "patch_filter blur", "patch_filter low res", "patch_filter blur+low res", "patch_tone contrast", "patch_tone contrast+gamma"]
 
         def launch(kind, s):
             host, dev, _, _ = s
@@ -78,8 +91,12 @@ def main():
                 L.check(lib.vsseg_crop_flip(dev[0].data_ptr(), 2 * B, out.data_ptr(), L.i3(roi), stream))
             elif kind < 3:
                 L.check(lib.vsseg_crop_affine(host[kind], dev[kind].data_ptr(), 2 * B, out.data_ptr(), L.i3(roi), 12345, stream))
-            else:
+            elif kind < 5:
                 L.check(lib.vsseg_crop_field(host[kind], dev[kind].data_ptr(), 2 * B, out.data_ptr(), L.i3(roi), L.i3(spacing), 12345, stream))
+            elif kind < 8:
+                L.check(lib.vsseg_patch_filter(host[kind], dev[kind].data_ptr(), B, out.data_ptr(), filtered.data_ptr(), scratch.data_ptr(), L.i3(roi), stream))
+            else:  # in place on the patches the filter launches before it have just written
+                L.check(lib.vsseg_patch_tone(host[kind], dev[kind].data_ptr(), B, filtered.data_ptr(), per, stats.data_ptr(), work.data_ptr(), stream))
 
         ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.launches)] for _ in kinds]
         for i in range(a.warmup + a.launches):
@@ -94,9 +111,13 @@ def main():
         print(f"batch {B} of {roi}: {written / 1e6:.1f} MB written per launch")
         for kind, name in enumerate(kinds):
             us = np.array([e0.elapsed_time(e1) * 1e3 for e0, e1 in ev[kind]])
-            read = 4 * np.mean([s[2 if kind == 0 else 3] for s in sets])
             med = float(np.median(us))
-            print(f"  {name:<24s} median {med:8.1f} us   mean {us.mean():8.1f} us   min {us.min():8.1f} us   {(written + read) / med / 1e3:7.1f} GB/s  ({read / 1e6:.1f} MB source footprint)")
+            if kind >= 5:  # algorithmic bytes over the image half of the batch: filter 1 read + 1 write, tone 2 reads + 1 write
+                moved = (2 if kind < 8 else 3) * B * per * 4
+                print(f"  {name:<26s} median {med:8.1f} us   mean {us.mean():8.1f} us   min {us.min():8.1f} us   {moved / med / 1e3:7.1f} GB/s  ({moved / 1e6:.1f} MB algorithmic)")
+                continue
+            read = 4 * np.mean([s[2 if kind == 0 else 3] for s in sets])
+            print(f"  {name:<26s} median {med:8.1f} us   mean {us.mean():8.1f} us   min {us.min():8.1f} us   {(written + read) / med / 1e3:7.1f} GB/s  ({read / 1e6:.1f} MB source footprint)")
 
 
 if __name__ == "__main__":

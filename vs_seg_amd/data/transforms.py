@@ -10,6 +10,9 @@ RandShiftIntensityd / RandGaussianNoised are the transforms it corresponds to): 
 of the crop window, a gain, a bias and Gaussian noise, all applied by ONE `vsseg_crop_affine` launch in place of the crop.  Two more families
 (MONAI's Rand3DElastic / RandBiasField, TorchIO's RandomElasticDeformation) are one smooth random B-spline field over the patch, a 2-vector for an
 in-plane elastic deformation and a scalar for a multiplicative MR bias field; with either on, the launch is `vsseg_crop_field`, the same gather with the field.
+Four appearance families act on the image after the crop launch, each per sample with probability `appearance_prob`: an in-plane Gaussian blur and a simulated
+low-resolution acquisition (`vsseg_patch_filter`), then a contrast change and a gamma curve (`vsseg_patch_tone`; batchgenerators' ContrastAugmentation with
+preserve_range, MONAI's RandAdjustContrast).
 
 The numpy restatement of MONAI 0.4.0's arithmetic that checks the HIP path (`vsseg_normalize_intensity`, `vsseg_crop_flip`) is test
 infrastructure and lives in `oracle/data_oracle.py` (parity unpinned — MONAI is not installed).  `PatchSampler`
@@ -77,6 +80,43 @@ def check_field_augment(elastic_mag=0.0, bias_field=0.0, field_spacing=64) -> Di
     return f
 
 
+APPEARANCE_KEYS = ("blur_sigma", "lowres", "contrast", "gamma", "appearance_prob")
+
+
+def check_appearance_augment(blur_sigma=0.0, lowres=0.0, contrast=0.0, gamma=0.0, appearance_prob=0.25) -> Dict[str, float]:
+    """The four appearance ranges (0 = off) and the per-sample, per-family probability as floats; ValueError for a non-finite value, blur_sigma outside [0, 1.5]
+    (the radius ceil(3 sigma) stays <= 5), lowres that is neither 0 nor in [0.25, 1), contrast or gamma outside [0, 1) and appearance_prob outside [0, 1]."""
+    a = dict(blur_sigma=float(blur_sigma), lowres=float(lowres), contrast=float(contrast), gamma=float(gamma), appearance_prob=float(appearance_prob))
+    for k, v in a.items():
+        if not (np.isfinite(v) and v >= 0.0):
+            raise ValueError(f"augmentation range {k} = {v}: must be finite and >= 0")
+    if a["blur_sigma"] > 1.5:
+        raise ValueError(f"blur_sigma = {a['blur_sigma']}: at most 1.5 in-plane voxels (a radius of 5)")
+    if a["lowres"] != 0.0 and not 0.25 <= a["lowres"] < 1.0:
+        raise ValueError(f"lowres = {a['lowres']}: 0 (off) or a resolution factor in [0.25, 1)")
+    for k in ("contrast", "gamma"):
+        if a[k] >= 1.0:
+            raise ValueError(f"{k} = {a[k]}: must be < 1 (the factor 1 + u stays positive)")
+    if a["appearance_prob"] > 1.0:
+        raise ValueError(f"appearance_prob = {a['appearance_prob']}: a probability, at most 1")
+    return a
+
+
+def blur_taps(sigma: float) -> np.ndarray:
+    """The R + 1 half-taps of `vsseg_filter_job.taps` for R = ceil(3 sigma): w_k = exp(-k^2 / (2 sigma^2)), normalised in fp64 so that w_0 + 2 sum_{k>=1} w_k = 1,
+    rounded once to fp32.  sigma = 0: no taps (radius 0)."""
+    sigma = float(sigma)
+    if sigma == 0.0:
+        return np.zeros(0, np.float32)
+    w = np.exp(-np.arange(int(np.ceil(3.0 * sigma)) + 1, dtype=np.float64) ** 2 / (2.0 * sigma * sigma))
+    return (w / (w[0] + 2.0 * w[1:].sum())).astype(np.float32)
+
+
+def coarse_size(roi: Sequence[int], f: float) -> Tuple[int, int]:
+    """The in-plane sample counts of `vsseg_filter_job.coarse` at the resolution factor f: n_a = max(1, floor(roi_a * f + 0.5)); (roi_x, roi_y) means off."""
+    return tuple(max(1, int(np.floor(int(roi[a]) * float(f) + 0.5))) for a in range(2))
+
+
 def field_launch_spacing(field_spacing: int) -> Tuple[int, int, int]:
     """(S, S, max(1, (S + 2) // 4)): the lattice is roughly isotropic in millimetres over 0.4 x 0.4 x 1.5 mm voxels."""
     s = int(field_spacing)
@@ -112,16 +152,24 @@ class RandomTail:
 
     With a non-zero field range (`elastic_mag`, `bias_field`) a FOURTH state is seeded from `R` after those, so the flip, crop and five-family draws are the same with
     the fields on or off.  `draw_field_seed()` draws one randint(2^32) per batch (the high half of the launch seed: the lattice differs from batch to batch, noise or no
-    noise); `draw_field()` draws per sample, in this order and only for the families that are on: a ~ U(0, elastic_mag), beta ~ U(0, bias_field)."""
+    noise); `draw_field()` draws per sample, in this order and only for the families that are on: a ~ U(0, elastic_mag), beta ~ U(0, bias_field).
+
+    With a non-zero appearance range (`blur_sigma`, `lowres`, `contrast`, `gamma`) a FIFTH state is seeded from `R` after those, so all the draws above are the same with
+    the appearance families on or off.  `draw_appearance()` draws per sample, for each family whose range is non-zero, in the order blur, low resolution, contrast, gamma:
+    first `random_sample() < appearance_prob`, then the value (sigma ~ U(S/2, S), f ~ U(F, 1), c ~ U(1 - C, 1 + C), gamma ~ U(1 - G, 1 + G)).  Both numbers are always
+    drawn, so the position in the stream does not depend on the outcome; a family that is not hit gets its neutral value (sigma = 0, f = 1, c = 1, gamma = 1)."""
 
     def __init__(self, roi: Sequence[int], flip_prob: Optional[float] = 0.5, seed: Optional[int] = None, rotate_deg: float = 0.0, scale: float = 0.0,
-                 intensity_scale: float = 0.0, intensity_shift: float = 0.0, noise_std: float = 0.0, elastic_mag: float = 0.0, bias_field: float = 0.0, field_spacing: int = 64):
+                 intensity_scale: float = 0.0, intensity_shift: float = 0.0, noise_std: float = 0.0, elastic_mag: float = 0.0, bias_field: float = 0.0, field_spacing: int = 64,
+                 blur_sigma: float = 0.0, lowres: float = 0.0, contrast: float = 0.0, gamma: float = 0.0, appearance_prob: float = 0.25):
         self.roi = tuple(int(r) for r in roi)
         self.flip_prob = flip_prob
         self.augment = check_augment(rotate_deg, scale, intensity_scale, intensity_shift, noise_std)
         self.augmenting = any(v != 0.0 for v in self.augment.values())
         self.field = check_field_augment(elastic_mag, bias_field, field_spacing)
         self.fielding = self.field["elastic_mag"] != 0.0 or self.field["bias_field"] != 0.0
+        self.appearance = check_appearance_augment(blur_sigma, lowres, contrast, gamma, appearance_prob)
+        self.appearing = any(self.appearance[k] != 0.0 for k in APPEARANCE_KEYS[:4])
         self.set_random_state(seed)
 
     def set_random_state(self, seed: Optional[int] = None):
@@ -130,6 +178,7 @@ class RandomTail:
         self._cropR = np.random.RandomState(R.randint(MAX_SEED, dtype="uint32"))
         self._augR = np.random.RandomState(R.randint(MAX_SEED, dtype="uint32")) if self.augmenting else None
         self._fieldR = np.random.RandomState(R.randint(MAX_SEED, dtype="uint32")) if self.fielding else None
+        self._appR = np.random.RandomState(R.randint(MAX_SEED, dtype="uint32")) if self.appearing else None
         return self
 
     def draw(self, shape: Sequence[int]) -> Tuple[bool, Tuple[int, int, int]]:
@@ -152,6 +201,19 @@ class RandomTail:
         """(elastic_mag in voxels, bias_log) of one sample."""
         f, u = self.field, (lambda r: float(self._fieldR.uniform(0.0, r)) if r != 0.0 else 0.0)
         return u(f["elastic_mag"]), u(f["bias_field"])
+
+    def draw_appearance(self) -> Tuple[float, float, float, float]:
+        """(blur sigma in in-plane voxels, resolution factor, contrast factor, gamma) of one sample; (0, 1, 1, 1) is neutral."""
+        a, p = self.appearance, self.appearance["appearance_prob"]
+
+        def family(rng, lo, hi, neutral):
+            if rng == 0.0:
+                return neutral
+            hit, v = self._appR.random_sample() < p, float(self._appR.uniform(lo, hi))
+            return v if hit else neutral
+
+        return (family(a["blur_sigma"], a["blur_sigma"] / 2.0, a["blur_sigma"], 0.0), family(a["lowres"], a["lowres"], 1.0, 1.0),
+                family(a["contrast"], 1.0 - a["contrast"], 1.0 + a["contrast"], 1.0), family(a["gamma"], 1.0 - a["gamma"], 1.0 + a["gamma"], 1.0))
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -195,12 +257,25 @@ class PatchSampler:
 
     A non-zero `elastic_mag` (voxels) or `bias_field` (log of the factor) makes that launch `vsseg_crop_field` with the lattice spacing
     `field_launch_spacing(field_spacing)`: image and label of a sample share the deformation, the bias field multiplies the image only.  `last_augment` then
-    also holds `elastic_mag`, `bias_log` (fp32) and `spacing` per sample.  With both 0 the sampler takes the paths above, launch for launch."""
+    also holds `elastic_mag`, `bias_log` (fp32) and `spacing` per sample.  With both 0 the sampler takes the paths above, launch for launch.
+
+    A non-zero `blur_sigma`, `lowres`, `contrast` or `gamma` with `appearance_prob` > 0 adds, after whichever crop launch it is and on the image only, one
+    `vsseg_patch_filter` launch when a sample of the batch drew a blur or a low resolution and one `vsseg_patch_tone` launch when one drew a contrast or a gamma.
+    `last_augment[b]` then also holds `blur_sigma` (as drawn), `blur_taps` (fp32, R + 1 values), `coarse` (two ints), `contrast` and `gamma` (fp32), and `last_tone_stats` the
+    [B, 4] device tensor {min, max, mean, 0} of the tone launch (None when it was skipped).  The scratch of the filter and the workspace of the tone launch belong to
+    the sampler; the filtered image is a new tensor, because it is handed to the caller.  Nothing here reads device memory from the host or synchronises.  With the
+    four ranges 0, or `appearance_prob` 0, the sampler takes the paths above, launch for launch."""
 
     def __init__(self, cases: List[Dict], roi: Sequence[int], flip_prob: Optional[float] = 0.5, seed: Optional[int] = 0, rotate_deg: float = 0.0, scale: float = 0.0,
-                 intensity_scale: float = 0.0, intensity_shift: float = 0.0, noise_std: float = 0.0, elastic_mag: float = 0.0, bias_field: float = 0.0, field_spacing: int = 64):
+                 intensity_scale: float = 0.0, intensity_shift: float = 0.0, noise_std: float = 0.0, elastic_mag: float = 0.0, bias_field: float = 0.0, field_spacing: int = 64,
+                 blur_sigma: float = 0.0, lowres: float = 0.0, contrast: float = 0.0, gamma: float = 0.0, appearance_prob: float = 0.25):
         self.cases, self.roi = cases, tuple(int(r) for r in roi)
-        self.tail = RandomTail(self.roi, flip_prob, seed, rotate_deg, scale, intensity_scale, intensity_shift, noise_std, elastic_mag, bias_field, field_spacing)
+        self.tail = RandomTail(self.roi, flip_prob, seed, rotate_deg, scale, intensity_scale, intensity_shift, noise_std, elastic_mag, bias_field, field_spacing,
+                               blur_sigma, lowres, contrast, gamma, appearance_prob)
+        self.appearing = self.tail.appearing and self.tail.appearance["appearance_prob"] > 0.0
+        self.last_tone_stats: Optional[torch.Tensor] = None
+        self._filter_scratch: Optional[torch.Tensor] = None  # [B, *roi] of the largest batch so far: a job with blur and low resolution passes the blurred patch through it
+        self._tone_work: Optional[torch.Tensor] = None  # [B, TONE_SHARDS, 3] fp64
         self.lib = L.lib()
         self.last_draws: List[Tuple[bool, Tuple[int, int, int]]] = []
         self.last_augment: List[Dict] = []  # per sample: m (fp32 3x4), gain, bias, noise_std (fp32), noise_stream, seed (+ elastic_mag, bias_log (fp32), spacing with a field)
@@ -209,8 +284,44 @@ class PatchSampler:
         return len(self.cases)
 
     def sample(self, indices: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:
-        if self.tail.augmenting or self.tail.fielding:
-            return self._sample_affine(indices)
+        img, lab = self._sample_affine(indices) if self.tail.augmenting or self.tail.fielding else self._sample_crop(indices)
+        return (self._appearance(img), lab) if self.appearing else (img, lab)
+
+    def _appearance(self, img: torch.Tensor) -> torch.Tensor:
+        """blur -> low resolution -> contrast -> gamma on the image patches [B, 1, *roi] of the crop launch; draws one sample after the other."""
+        B, dev, stream = img.shape[0], img.device, torch.cuda.current_stream()
+        if not self.last_augment:  # the plain crop keeps no per-sample record of its own
+            self.last_augment = [dict() for _ in range(B)]
+        fjobs, tjobs = (L.FilterJob * B)(), (L.ToneJob * B)()
+        filtering = toning = both = False
+        for b in range(B):
+            sigma, f, c, g = self.tail.draw_appearance()
+            taps, coarse = blur_taps(sigma), coarse_size(self.roi, f)
+            self.last_augment[b].update(blur_sigma=float(sigma), blur_taps=taps, coarse=coarse, contrast=np.float32(c), gamma=np.float32(g))
+            fjobs[b].radius, fjobs[b].taps, fjobs[b].coarse = max(len(taps) - 1, 0), (C.c_float * 6)(*taps.tolist()), (C.c_int32 * 2)(*coarse)
+            tjobs[b].contrast, tjobs[b].gamma = float(np.float32(c)), float(np.float32(g))
+            low = coarse != self.roi[:2]
+            filtering, both = filtering or low or len(taps) > 0, both or (low and len(taps) > 0)
+            toning = toning or tjobs[b].contrast != 1.0 or tjobs[b].gamma != 1.0
+        if filtering:
+            if both and (self._filter_scratch is None or self._filter_scratch.shape[0] < B or self._filter_scratch.device != dev):
+                self._filter_scratch = torch.empty((B, *self.roi), dtype=torch.float32, device=dev)
+            jbuf = torch.frombuffer(bytearray(bytes(fjobs)), dtype=torch.uint8).to(dev)
+            out = torch.empty_like(img)
+            L.check(self.lib.vsseg_patch_filter(fjobs, jbuf.data_ptr(), B, img.data_ptr(), out.data_ptr(), self._filter_scratch.data_ptr() if both else None, L.i3(self.roi), stream.cuda_stream), "patch_filter")
+            jbuf.record_stream(stream)
+            img = out
+        self.last_tone_stats = None
+        if toning:
+            if self._tone_work is None or self._tone_work.shape[0] < B or self._tone_work.device != dev:
+                self._tone_work = torch.empty((B, L.TONE_SHARDS, 3), dtype=torch.float64, device=dev)
+            jbuf = torch.frombuffer(bytearray(bytes(tjobs)), dtype=torch.uint8).to(dev)
+            self.last_tone_stats = torch.empty((B, 4), dtype=torch.float32, device=dev)
+            L.check(self.lib.vsseg_patch_tone(tjobs, jbuf.data_ptr(), B, img.data_ptr(), img[0].numel(), self.last_tone_stats.data_ptr(), self._tone_work.data_ptr(), stream.cuda_stream), "patch_tone")
+            jbuf.record_stream(stream)
+        return img
+
+    def _sample_crop(self, indices: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:
         dev = self.cases[indices[0]]["image"].device
         B = len(indices)
         jobs = (L.CropJob * (2 * B))()

@@ -32,7 +32,7 @@ from .metrics import compute_surface_distances, voxel_spacing
 from .postprocess import keep_largest_component
 from . import parallel as DP
 from .data import nifti
-from .data.transforms import AUGMENT_KEYS, FIELD_KEYS, PatchSampler, check_augment, check_field_augment, epoch_batches, load_case
+from .data.transforms import APPEARANCE_KEYS, AUGMENT_KEYS, FIELD_KEYS, PatchSampler, check_appearance_augment, check_augment, check_field_augment, epoch_batches, load_case
 
 HP = dict(
     channels=(16, 32, 48, 64, 80, 96),
@@ -50,14 +50,14 @@ class CachedLoader:
     the reference's first-epoch log line divides one by the other (ref:params/VSparams.py:466)."""
 
     def __init__(self, cases: List[Dict], roi: Optional[Sequence[int]], batch_size: int, shuffle: bool, flip_prob: Optional[float], seed: int = 0, pad: Optional[bool] = None,
-                 augment: Optional[Dict[str, float]] = None, field_augment: Optional[Dict[str, float]] = None):
+                 augment: Optional[Dict[str, float]] = None, field_augment: Optional[Dict[str, float]] = None, appearance_augment: Optional[Dict[str, float]] = None):
         self.cases, self.batch_size, self.shuffle = cases, batch_size, shuffle
         # equal step counts on every rank (wrap-around padding) only where every step issues a collective: the shuffled training loader.
         # Validation / test loaders give rank r exactly shard_indices(n, r, world) — a padded case would be counted twice in their sums
         self.pad = shuffle if pad is None else pad
         self.rank, self.world = DP.get_rank(), DP.world_size()
         # every rank shuffles with the SAME stream (the shards must partition one permutation) but draws its own flips / crops
-        self.sampler = PatchSampler(cases, roi, flip_prob, seed + 7919 * self.rank, **(augment or {}), **(field_augment or {})) if roi is not None else None
+        self.sampler = PatchSampler(cases, roi, flip_prob, seed + 7919 * self.rank, **(augment or {}), **(field_augment or {}), **(appearance_augment or {})) if roi is not None else None
         self._order = np.random.RandomState(seed)
 
     def __len__(self):
@@ -106,11 +106,17 @@ class VSparams:
         parser.add_argument("--aug_elastic_mag", type=float, default=0.0, metavar="VOX", help="training augmentation: deform every training patch in-plane by a smooth random B-spline field whose control points move by at most a length drawn from [0, VOX] voxels; the peak displacement of the field is typically about half of it; at most aug_field_spacing / 4 (0: off)")
         parser.add_argument("--aug_bias_field", type=float, default=0.0, metavar="LOG", help="training augmentation: multiply the image of every training patch by exp of a smooth random B-spline field whose amplitude is drawn from [0, LOG] (the MR bias field; 0: off)")
         parser.add_argument("--aug_field_spacing", type=int, default=64, metavar="VOX", help="in-plane control-point spacing of the two B-spline fields in voxels (64: about 26 mm; along z a quarter of it)")
+        parser.add_argument("--aug_blur_sigma", type=float, default=0.0, metavar="VOX", help="training augmentation: blur the image of a training patch in-plane with a Gaussian whose sigma is drawn from [VOX / 2, VOX] in-plane voxels; at most 1.5 (0: off)")
+        parser.add_argument("--aug_lowres", type=float, default=0.0, metavar="FRAC", help="training augmentation: simulate a low-resolution acquisition of the image of a training patch: sample it in-plane at a resolution factor drawn from [FRAC, 1] and interpolate back; in [0.25, 1) (0: off)")
+        parser.add_argument("--aug_contrast", type=float, default=0.0, metavar="FRAC", help="training augmentation: scale the image of a training patch about its mean by a factor drawn from [1 - FRAC, 1 + FRAC], clipped to the range it had (0: off)")
+        parser.add_argument("--aug_gamma", type=float, default=0.0, metavar="FRAC", help="training augmentation: apply a gamma curve over the value range of the image of a training patch, with an exponent drawn from [1 - FRAC, 1 + FRAC] (0: off)")
+        parser.add_argument("--aug_appearance_prob", type=float, default=0.25, metavar="P", help="probability with which each of the blur, low-resolution, contrast and gamma augmentations is applied to a training sample, independently of the others")
         args = parser.parse_args(argv)
         try:
             tta_masks(args.tta_flips, args.tta_average)
             augment = check_augment(*(getattr(args, "aug_" + k) for k in AUGMENT_KEYS))
             field = check_field_augment(args.aug_elastic_mag, args.aug_bias_field, args.aug_field_spacing)
+            appearance = check_appearance_augment(*(getattr(args, "aug_" + k) for k in APPEARANCE_KEYS))
         except ValueError as e:
             parser.error(str(e))
 
@@ -137,6 +143,7 @@ class VSparams:
         self.tta_flips, self.tta_average = tuple(args.tta_flips or ()), args.tta_average
         self.aug_rotate_deg, self.aug_scale, self.aug_intensity_scale, self.aug_intensity_shift, self.aug_noise_std = (augment[k] for k in AUGMENT_KEYS)
         self.aug_elastic_mag, self.aug_bias_field, self.aug_field_spacing = (field[k] for k in FIELD_KEYS)
+        self.aug_blur_sigma, self.aug_lowres, self.aug_contrast, self.aug_gamma, self.aug_appearance_prob = (appearance[k] for k in APPEARANCE_KEYS)
         self.results_folder_path = os.path.join(self.data_root, "results", "debug" if self.debug else args.results_folder_name)
         self.logs_path = os.path.join(self.results_folder_path, "logs")
         self.model_path = os.path.join(self.results_folder_path, "model")
@@ -173,7 +180,8 @@ class VSparams:
                   "results_folder_path", "export_inferred_segmentations", "compute_dtype") + (("surface_metrics",) if self.surface_metrics else ()) + (
                       ("keep_largest_component", "component_connectivity") if self.keep_largest_component else ()) + (("tta_flips", "tta_average") if self.tta_flips else ()) + (
                           tuple("aug_" + k for k in AUGMENT_KEYS) if any(self.augment.values()) else ()) + (
-                              ("aug_elastic_mag", "aug_bias_field", "aug_field_spacing") if self.aug_elastic_mag or self.aug_bias_field else ()):
+                              ("aug_elastic_mag", "aug_bias_field", "aug_field_spacing") if self.aug_elastic_mag or self.aug_bias_field else ()) + (
+                                  tuple("aug_" + k for k in APPEARANCE_KEYS) if self._appearance_on else ()):
             log("{:<34s} {}".format(k + " =", getattr(self, k)))
         log("-" * 10)
 
@@ -204,19 +212,34 @@ class VSparams:
         """The two B-spline field ranges and their spacing under PatchSampler's argument names (both ranges 0: off)."""
         return dict(elastic_mag=self.aug_elastic_mag, bias_field=self.aug_bias_field, field_spacing=self.aug_field_spacing)
 
+    @property
+    def appearance_augment(self) -> Dict[str, float]:
+        """The four appearance ranges and their probability under PatchSampler's argument names (all four ranges 0: off)."""
+        return {k: getattr(self, "aug_" + k) for k in APPEARANCE_KEYS}
+
+    @property
+    def _appearance_on(self) -> bool:
+        return any(getattr(self, "aug_" + k) for k in APPEARANCE_KEYS[:4])
+
     def get_transforms(self):
         """The three chains as plain descriptions; `cache_transformed_*_data` executes them (deterministic head cached in
-        HBM, random tail per batch).  The augmentation flags reach the training chain only: the five ranges under "augment", the field ranges under "field_augment"."""
+        HBM, random tail per batch).  The augmentation flags reach the training chain only: the five ranges under "augment", the field ranges under "field_augment",
+        the appearance ranges under "appearance_augment"."""
         head = ["LoadNifti", "AddChannel", "Orientation(RAS)", "NormalizeIntensity(image)"]
-        a, f = self.augment, self.field_augment
+        a, f, ap = self.augment, self.field_augment, self.appearance_augment
+        p = f"p={ap['appearance_prob']}"
         # in the order the launch applies them: the deformation acts in patch space, the matrix after it; the bias field multiplies the interpolated value before the gain
         aug = ([f"RandElastic(aug_elastic_mag={f['elastic_mag']}, aug_field_spacing={f['field_spacing']}, in-plane, cubic B-spline)"] if f["elastic_mag"] else []) + (
             [f"RandAffine(aug_rotate_deg={a['rotate_deg']}, aug_scale={a['scale']}, axis=z, about the crop centre)"] if a["rotate_deg"] or a["scale"] else []) + (
             [f"RandBiasField(aug_bias_field={f['bias_field']}, aug_field_spacing={f['field_spacing']})"] if f["bias_field"] else []) + (
             [f"RandScaleIntensity(aug_intensity_scale={a['intensity_scale']})"] if a["intensity_scale"] else []) + (
             [f"RandShiftIntensity(aug_intensity_shift={a['intensity_shift']})"] if a["intensity_shift"] else []) + (
-            [f"RandGaussianNoise(aug_noise_std={a['noise_std']})"] if a["noise_std"] else [])
-        train = dict(chain=head + [f"SpatialPad({self.pad_crop_shape})", "RandFlip(p=0.5, axis=0)", f"RandSpatialCrop({self.pad_crop_shape})"] + aug, pad=self.pad_crop_shape, roi=self.pad_crop_shape, flip_prob=0.5, augment=a, field_augment=f)
+            [f"RandGaussianNoise(aug_noise_std={a['noise_std']})"] if a["noise_std"] else []) + (
+            [f"RandGaussianBlur(aug_blur_sigma={ap['blur_sigma']}, in-plane, {p})"] if ap["blur_sigma"] else []) + (
+            [f"RandLowResolution(aug_lowres={ap['lowres']}, in-plane, {p})"] if ap["lowres"] else []) + (
+            [f"RandContrast(aug_contrast={ap['contrast']}, preserve_range, {p})"] if ap["contrast"] else []) + (
+            [f"RandGamma(aug_gamma={ap['gamma']}, {p})"] if ap["gamma"] else [])
+        train = dict(chain=head + [f"SpatialPad({self.pad_crop_shape})", "RandFlip(p=0.5, axis=0)", f"RandSpatialCrop({self.pad_crop_shape})"] + aug, pad=self.pad_crop_shape, roi=self.pad_crop_shape, flip_prob=0.5, augment=a, field_augment=f, appearance_augment=ap)
         val = dict(chain=head + [f"SpatialPad({self.pad_crop_shape})", f"RandSpatialCrop({self.pad_crop_shape})"], pad=self.pad_crop_shape, roi=self.pad_crop_shape, flip_prob=None)
         test = dict(chain=head, pad=None, roi=None, flip_prob=None)
         return train, val, test
@@ -254,7 +277,7 @@ class VSparams:
     def _cache(self, files, tf, batch_size, shuffle, what):
         self.logger.info(f"Caching {what} data set...")
         cases = [load_case(fd, tf["pad"], self.device) for fd in files]
-        return CachedLoader(cases, tf["roi"], batch_size, shuffle, tf["flip_prob"], seed=0, augment=tf.get("augment"), field_augment=tf.get("field_augment"))  # the crop/flip stream is decorrelated per rank inside CachedLoader
+        return CachedLoader(cases, tf["roi"], batch_size, shuffle, tf["flip_prob"], seed=0, augment=tf.get("augment"), field_augment=tf.get("field_augment"), appearance_augment=tf.get("appearance_augment"))  # the crop/flip stream is decorrelated per rank inside CachedLoader
 
     def cache_transformed_train_data(self, train_files, train_transforms):
         return self._cache(train_files, train_transforms, self.train_batch_size, True, "training")
