@@ -235,7 +235,7 @@ int vsseg_fork_event_destroy(void* ev);
 int vsseg_fork_arm(void* ev);
 int vsseg_fork_disarm(void);
 int vsseg_stream_wait_event(void* stream, void* ev);
-int vsseg_version(void); /* 12: + vsseg_crop_field, vsseg_field_job; 11: + vsseg_crop_affine, vsseg_affine_job; 10: + vsseg_swi_finalize_mirrored, vsseg_crop_job.flip is a three-axis mirror mask (was flip_x); 9: + vsseg_components_scratch_bytes, vsseg_components_label, vsseg_keep_largest_component; 8: + vsseg_surface_distances, vsseg_surface_scratch_bytes; 7: + vsseg_dice_pred_bwd_to, vsseg_dice_level_sums, vsseg_dice_tail_sums, vsseg_dice_att_bwd_levels, vsseg_fork_*, vsseg_stream_wait_event; 6: + launch plans with depth -8 (transition kernel) and -9 (gathering marching kernel); 5: vsseg_wgrad march = 2 (compute weight-gradient kernel), + vsseg_conv_to1, vsseg_conv_chain_desc without h_out (the training variant measured no gain and was deleted); 4: + vsseg_conv_chain; 3: the BatchNorm-block-on-load fields (in_bn_*, keep_*, x_bn_*: round-4 experiment, measured a loss, deleted) left the descriptors, depth -7 plans;
+int vsseg_version(void); /* 14: + vsseg_ce_sums, vsseg_dice_ce_finalize, vsseg_dice_ce_pred_bwd, vsseg_dice_ce_pred_bwd_to; 13: + vsseg_patch_filter, vsseg_patch_tone; 12: + vsseg_crop_field, vsseg_field_job; 11: + vsseg_crop_affine, vsseg_affine_job; 10: + vsseg_swi_finalize_mirrored, vsseg_crop_job.flip is a three-axis mirror mask (was flip_x); 9: + vsseg_components_scratch_bytes, vsseg_components_label, vsseg_keep_largest_component; 8: + vsseg_surface_distances, vsseg_surface_scratch_bytes; 7: + vsseg_dice_pred_bwd_to, vsseg_dice_level_sums, vsseg_dice_tail_sums, vsseg_dice_att_bwd_levels, vsseg_fork_*, vsseg_stream_wait_event; 6: + launch plans with depth -8 (transition kernel) and -9 (gathering marching kernel); 5: vsseg_wgrad march = 2 (compute weight-gradient kernel), + vsseg_conv_to1, vsseg_conv_chain_desc without h_out (the training variant measured no gain and was deleted); 4: + vsseg_conv_chain; 3: the BatchNorm-block-on-load fields (in_bn_*, keep_*, x_bn_*: round-4 experiment, measured a loss, deleted) left the descriptors, depth -7 plans;
                             * 2: fixed-point accumulators documented + vsseg_fx_status; 1: the buffers below were described as plain doubles */
 
 /* ---- Accumulator buffers are 64-bit FIXED-POINT integers, not doubles ------------------------------------------------------------------
@@ -244,12 +244,13 @@ int vsseg_version(void); /* 12: + vsseg_crop_field, vsseg_field_job; 11: + vsseg
  * each 8-byte slot holds a two's-complement int64 = round(value * scale), added to with integer atomics so that the total does not depend on
  * the order in which workgroups finish (a training step is run-to-run bit-identical).  Zero bytes are the value 0, so callers keep zero-filling
  * the buffers (vsseg_memset_zero) exactly as before; callers that READ or PRE-FILL a slot must use the scale of its family:
- *     VSSEG_FX_STAT_SCALE  2^20  BatchNorm forward statistics (sum, sum of squares)         per-workgroup partial |v| < 4.3e9
+ *     VSSEG_FX_STAT_SCALE  2^20  BatchNorm forward statistics (sum, sum of squares);         per-workgroup partial |v| < 4.3e9
+ *                                cross-entropy sums (vsseg_ce_sums)
  *     VSSEG_FX_GRAD_SCALE  2^44  BatchNorm / PReLU backward sums (sums, alpha_acc)           per-workgroup partial |v| < 256
  *     VSSEG_FX_DICE_SCALE  2^32  Dice sums (pred_sums, att_sums)                              per-workgroup partial |v| < 1.0e6
  * (vsseg_hard_dice_counts keeps REAL doubles: its sums are integers, exact in fp64 in any order.)
  * A partial sum outside its range, or a NaN / Inf one, is clamped and sets a sticky per-process device flag; while the flag is set the decoding
- * kernels (vsseg_bn_finalize, vsseg_bn_act_bwd_finalize, vsseg_dice_finalize) return NaN, so a diverging run or an out-of-range loss scale
+ * kernels (vsseg_bn_finalize, vsseg_bn_act_bwd_finalize, vsseg_dice_finalize, vsseg_dice_ce_finalize) return NaN, so a diverging run or an out-of-range loss scale
  * surfaces as NaN in the loss / statistics / gradients instead of as wrapped integers.  vsseg_fx_status reads (and optionally clears) the flag. */
 typedef double vsseg_fx_acc; /* one accumulator slot (reinterpret as int64_t) */
 #define VSSEG_FX_STAT_SCALE 1048576.0
@@ -392,6 +393,28 @@ int vsseg_dice_att_bwd_levels(const vsseg_dice_bwd_levels_desc* d, void* stream)
    gradient tensor, no cast pass): dst = 2 channels of `n * nvox` voxels, fp32 or bf16 (round-to-nearest-even, as vsseg_copy_cast), pitch 2, or pitch 8 =
    VSSEG_ZERO_PADDED rows whose channels 2..7 are written as zeros (bf16) / left as they are (fp32).  gscale may be NULL (= 1). */
 int vsseg_dice_pred_bwd_to(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* gscale, vsseg_tensor dst, void* stream);
+
+/* A voxel-wise cross-entropy term beside the Dice loss (ABI version 14; what MONAI users know as DiceCELoss, the default loss of nnU-Net):
+ *     loss = Dice_spvPA + ce_weight * CE,   CE = sum_{b,v} w[y] * (-log softmax(x_{b,v})[y]) / sum_{b,v} w[y],   w = (1, ce_foreground_weight)
+ * = ce_weight * torch.nn.functional.cross_entropy(logits, y, weight=[1, ce_foreground_weight]): ONE mean over all n * nvox voxels of the batch, final logits only (the
+ * attention-map terms and the hardness weight do not enter).  Label cast: y = 1 where (int)label == 1, else 0 — the cast of the Dice kernels.
+ *   value     of a voxel: softplus(z) = max(z, 0) + log1p(exp(-|z|)) with z = x[1-y] - x[y]: finite for every finite logit (-log(p_y) is inf once p_y underflows)
+ *   gradient  of a voxel: ce_weight * w[y] / W * (softmax(x) - onehot(y)), W = N_bg + ce_foreground_weight * N_fg, times *gscale where given, formed from the OTHER class's
+ *             probability — (+k p0, -k p0) for y = 1, (-k p1, +k p1) for y = 0 — because p_y - 1 cancels once p_y rounds to 1
+ * vsseg_ce_sums — one pass over logits and label: ce_sums[0..2] += (S_bg, S_fg, N_fg), the CE sums over the background / foreground voxels and the foreground count of
+ *   the whole batch.  The slots are fixed-point accumulators (below) of scale VSSEG_FX_STAT_SCALE (2^20), NOT VSSEG_FX_DICE_SCALE: a voxel's value is |z|, not bounded by 1
+ *   (batch 4 of 384x128x128 with every |z| = 100: 4.9e6 per workgroup — 2^32 leaves room for 1.0e6, 2^20 for 4.3e9; resolution 2^-20 per workgroup, <= 512 workgroups,
+ *   on a sum that is divided by W >= the voxel count).  Zero the three slots first.  A NaN / Inf partial sum sets the sticky flag like every other accumulator.
+ * vsseg_dice_ce_finalize — vsseg_dice_finalize that also decodes ce_sums: loss += ce_weight * (S_bg + w_fg * S_fg) / W in fp64 before the one cast to fp32, and
+ *   ce_coef[0..1] = (ce_weight / W, ce_weight * w_fg / W) in device memory for the backward (no host read of N_fg).  coef is vsseg_dice_finalize's, unchanged.  While the
+ *   fixed-point flag is set the loss and all coefficients are NaN.
+ * vsseg_dice_ce_pred_bwd / _to — vsseg_dice_pred_bwd / _to with the CE gradient of the voxel added in fp32 to the Dice gradient and the sum stored ONCE, in every layout
+ *   (a second pass would round the bf16 operand twice).  With ce_weight == 0 callers use the plain entry points: same launches and bits as before version 14. */
+int vsseg_ce_sums(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, double* ce_sums /* [3] */, void* stream);
+int vsseg_dice_ce_finalize(const double* pred_sums, const double* att_sums, int32_t n, int32_t nlevels, const double* ce_sums, int64_t nvox, double ce_weight, double ce_foreground_weight, float* loss, float* coef,
+                           float* ce_coef /* [2] */, void* stream);
+int vsseg_dice_ce_pred_bwd(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* ce_coef, const float* gscale, float* dlogits, void* stream);
+int vsseg_dice_ce_pred_bwd_to(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* ce_coef, const float* gscale, vsseg_tensor dst, void* stream);
 
 /* torch.optim.Adam(lr, weight_decay) over the flat parameter buffer (ref:params/VSparams.py:388-391,462). */
 int vsseg_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float wd, float bc1, float bc2, float gscale, void* stream);

@@ -1,6 +1,12 @@
 """Micro-benchmark of the loss kernels at the benchmark shape (tuning tool): every launch of the fused loss phase alone, and the coarse-level tail launch by level subset.
 
     python tools/bench_loss.py [--batch 4] [--dims 384 128 128]
+
+With --ce_weight LAMBDA [--ce_foreground_weight W] it times the cross-entropy term instead: the whole loss phase of the fused train step (Dice_spvPA.forward_backward_into,
+gradient of the logits written as bf16) with ce_weight = 0 and with the term, in the same process, at the benchmark shape and at batch 2 of 384x384x64, and the two launches
+the term adds or changes.
+
+    python tools/bench_loss.py --ce_weight 1 [--ce_foreground_weight 1]
 """
 import argparse
 import os
@@ -24,11 +30,67 @@ def timed(fn, reps=20):
     return e0.elapsed_time(e1) / reps * 1e3
 
 
+def bench_ce(lam, wfg, shapes):
+    """The loss phase with and without the cross-entropy term, interleaved (three rounds each, the median), and the launches of the term on their own."""
+    import vs_seg_amd as V
+
+    lib = L.lib()
+    S = torch.cuda.current_stream().cuda_stream
+    ratios = [(2, 2, 1), (2, 2, 1), (2, 2, 2), (2, 2, 2), (2, 2, 2)]
+    print(f"loss phase of the fused train step (forward_backward_into, bf16 gradient of the logits), ce_weight 0 against ce_weight {lam}, ce_foreground_weight {wfg}")
+    for B, d0 in shapes:
+        dims = [d0]
+        for r in ratios:
+            dims.append(tuple(x // y for x, y in zip(dims[-1], r)))
+        nvox = d0[0] * d0[1] * d0[2]
+        torch.manual_seed(0)
+        lg = torch.randn(B, *d0, 2, device="cuda")
+        logits = lg.permute(0, 4, 1, 2, 3)  # channels-last storage, as the network hands it out
+        lab = (torch.rand(B, 1, *d0, device="cuda") > 0.999).float()  # about one voxel in a thousand
+        atts = [torch.rand(B, 1, *d, device="cuda") for d in reversed(dims)]
+        dst = torch.empty(B, *d0, 2, device="cuda", dtype=torch.bfloat16)
+        bufs = [torch.empty(B, *a.shape[2:], device="cuda") for a in atts]
+        landing = (L.Tensor(dst.data_ptr(), L.BF16, 2, 2, B, *d0), bufs)
+        off = V.Dice_spvPA(to_onehot_y=True, softmax=True)
+        on = V.Dice_spvPA(to_onehot_y=True, softmax=True, ce_weight=lam, ce_foreground_weight=wfg)
+        t_off, t_on = [], []
+        for _ in range(3):
+            t_off.append(timed(lambda: off.forward_backward_into((logits, atts), lab, landing)))
+            t_on.append(timed(lambda: on.forward_backward_into((logits, atts), lab, landing)))
+        a, b = sorted(t_off)[1], sorted(t_on)[1]
+        l0, l1 = float(off.forward_backward_into((logits, atts), lab, landing)[0]), float(on.forward_backward_into((logits, atts), lab, landing)[0])
+        print(f"batch {B} of {d0[0]}x{d0[1]}x{d0[2]} ({B * nvox / 1e6:.1f} M voxels): loss {l0:.6f} -> {l1:.6f}")
+        print(f"  loss phase, ce_weight 0       {a:8.1f} us   (rounds: {', '.join(f'{t:.1f}' for t in t_off)})")
+        print(f"  loss phase, ce_weight {lam:<7g} {b:8.1f} us   (rounds: {', '.join(f'{t:.1f}' for t in t_on)})")
+        print(f"  added by the term             {b - a:8.1f} us")
+        sums = torch.zeros(3, dtype=torch.float64, device="cuda")
+        coef = torch.full((B * 4,), 1e-6, device="cuda")
+        cek = torch.full((2,), 1e-8, device="cuda")
+        l2 = lab.reshape(B, *d0)
+        t = timed(lambda: lib.vsseg_ce_sums(lg.data_ptr(), 2, l2.data_ptr(), B, nvox, sums.data_ptr(), S))
+        print(f"  vsseg_ce_sums                 {t:8.1f} us   ({B * nvox * 12 / t / 1e6:.2f} TB/s over logits + label)")
+        t0 = timed(lambda: lib.vsseg_dice_pred_bwd_to(lg.data_ptr(), 2, l2.data_ptr(), B, nvox, 1, coef.data_ptr(), None, landing[0], S))
+        t1 = timed(lambda: lib.vsseg_dice_ce_pred_bwd_to(lg.data_ptr(), 2, l2.data_ptr(), B, nvox, 1, coef.data_ptr(), cek.data_ptr(), None, landing[0], S))
+        print(f"  vsseg_dice_pred_bwd_to bf16   {t0:8.1f} us")
+        print(f"  vsseg_dice_ce_pred_bwd_to     {t1:8.1f} us   ({t1 - t0:+.1f} us)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--dims", type=int, nargs=3, default=[384, 128, 128])
+    ap.add_argument("--ce_weight", type=float, default=0.0, help="> 0: time the loss phase with and without the cross-entropy term instead (at the benchmark shape and at batch 2 of 384x384x64)")
+    ap.add_argument("--ce_foreground_weight", type=float, default=1.0)
     a = ap.parse_args()
+    from vs_seg_amd import check_ce
+
+    try:
+        lam, wfg = check_ce(a.ce_weight, a.ce_foreground_weight)
+    except ValueError as e:
+        ap.error(str(e))
+    if lam > 0:
+        bench_ce(lam, wfg, [(a.batch, tuple(a.dims)), (2, (384, 384, 64))])
+        return
     lib = L.lib()
     S = torch.cuda.current_stream().cuda_stream
     B, d0 = a.batch, tuple(a.dims)

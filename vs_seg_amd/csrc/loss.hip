@@ -313,8 +313,67 @@ extern "C" int vsseg_dice_tail_sums(const vsseg_dice_tail_desc* d, void* stream)
   return VSSEG_OK;
 }
 
+// The voxel-wise cross-entropy term beside the Dice loss (Dice_spvPA(ce_weight=lambda, ce_foreground_weight=w_fg); include/vsseg_hip.h states the formulas):
+//   CE = sum_{b,v} w[y] * softplus(x[1-y] - x[y]) / W,  y = ((int)label == 1),  w = (1, w_fg),  W = N_bg + w_fg * N_fg
+// = torch's F.cross_entropy(logits, y, weight=[1, w_fg]).  softplus(z) = max(z, 0) + log1p(exp(-|z|)) is -log softmax(x)[y] without the overflow of -log(p_y) once p_y
+// underflows.  sums[0..2] = (S_bg, S_fg, N_fg) of the whole batch: the CE sums over the background and the foreground voxels and the foreground count.
+// Scale: VSSEG_FX_STAT (2^20), NOT VSSEG_FX_DICE — a voxel's value is |z|, not bounded by 1: at batch 4 of 384x128x128 with every |z| = 100 a workgroup (1/512 of the
+// voxels) adds 4.9e6, beyond the 1.0e6 that 2^32 leaves room for and far inside the 4.3e9 of 2^20; the total (2.5e9) stays below 2^63 / 2^20 = 8.8e12.  The resolution,
+// 2^-20 per workgroup (rounded to nearest) and 512 workgroups at most, is 2.4e-4 on a sum that is divided by W >= the number of voxels.
+__device__ __forceinline__ void ce_terms(float l0, float l1, float lab, float* t) {
+  const bool fg = (int)(long long)lab == 1;
+  const float z = fg ? l0 - l1 : l1 - l0;
+  // log1p(e), e = exp(-|z|) in (0, 1]: e - e^2 / 2 below 2^-12 (the next term, e^3 / 3, is below 2^-26 e), log(1 + e) above it, where rounding 1 + e costs at most
+  // 2^-24 absolute — a library log1pf made the pass compute-bound (99 us against the 51 us of vsseg_dice_pred_sums over the same bytes).  A NaN logit: NaN through it.
+  const float e = __expf(-fabsf(z));
+  const float v = (z > 0.f ? z : 0.f) + (e < 0x1p-12f ? e * (1.f - 0.5f * e) : __logf(1.f + e));
+  t[0] += fg ? 0.f : v; t[1] += fg ? v : 0.f; t[2] += fg ? 1.f : 0.f;
+}
+// dice_pred_sums_kernel's launch shape and its two paths; a thread adds four voxels in fp32 and keeps its running sums in fp64
+__global__ __launch_bounds__(DICE_THREADS) void ce_sums_kernel(const float* __restrict__ logits, int pitch, const float* __restrict__ label, int64_t nvox, double* __restrict__ sums, unsigned* fxflag) {
+  const int b = blockIdx.y;
+  const float* lg = logits + (int64_t)b * nvox * pitch;
+  const float* lb = label + (int64_t)b * nvox;
+  double acc[3] = {0, 0, 0};
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+  if (pitch == 2 && (nvox & 3) == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0 && (reinterpret_cast<uintptr_t>(label) & 15) == 0) {
+    const float4* lg4 = reinterpret_cast<const float4*>(lg);
+    const float4* lb4 = reinterpret_cast<const float4*>(lb);
+    for (int64_t i = tid; i < (nvox >> 2); i += nthr) {
+      const float4 a = lg4[2 * i], c = lg4[2 * i + 1], g = lb4[i];
+      float t[3] = {0.f, 0.f, 0.f};
+      ce_terms(a.x, a.y, g.x, t);
+      ce_terms(a.z, a.w, g.y, t);
+      ce_terms(c.x, c.y, g.z, t);
+      ce_terms(c.z, c.w, g.w, t);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) acc[k] += (double)t[k];
+    }
+  } else {
+    for (int64_t v = tid; v < nvox; v += nthr) {
+      const float2 l = *reinterpret_cast<const float2*>(lg + v * pitch);
+      float t[3] = {0.f, 0.f, 0.f};
+      ce_terms(l.x, l.y, lb[v], t);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) acc[k] += (double)t[k];
+    }
+  }
+  block_reduce_add(acc, 3, sums, VSSEG_FX_STAT, fxflag);  // (one mean over the batch: every sample adds to the same three slots)
+}
+extern "C" int vsseg_ce_sums(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, double* sums, void* stream) {
+  VSSEG_CHECK(logits && label && sums && pitch >= 2 && pitch % 2 == 0 && n >= 1 && nvox >= 1, "vsseg_ce_sums: bad arguments");
+  dim3 g(dice_blocks(nvox / 4, n), n);
+  VSSEG_FX_FLAG(fxflag, "vsseg_ce_sums");
+  hipLaunchKernelGGL(ce_sums_kernel, g, dim3(DICE_THREADS), 0, as_stream(stream), logits, pitch, label, nvox, sums, fxflag);
+  VSSEG_LAUNCH_CHECK("vsseg_ce_sums");
+  return VSSEG_OK;
+}
+
 // loss = mean_{b,c} f_pred + sum_l (1/L) mean_b f_att,  f = 1 - (2I+eps)/(G+P+eps).  coef holds d(loss)/dI and d(loss)/dG(=dP).
-__global__ void dice_finalize_kernel(const double* pred_sums, const double* att_sums, int n, int nlevels, float* loss, float* coef, const unsigned* fxflag) {
+// With `ce_sums` (vsseg_dice_ce_finalize): + ce_weight * (S_bg + w_fg * S_fg) / W, added in fp64 before the one cast, and ce_coef = (ce_weight / W, ce_weight * w_fg / W),
+// W = (voxels - N_fg) + w_fg * N_fg — the backward reads the two from device memory: no host read of N_fg.
+__global__ void dice_finalize_kernel(const double* pred_sums, const double* att_sums, int n, int nlevels, float* loss, float* coef, const unsigned* fxflag,
+                                     const double* ce_sums, double voxels, double ce_weight, double ce_fg_weight, float* ce_coef) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   double total = vsseg_fx_poison(fxflag);  // NaN while a partial sum of this process was non-finite / out of range (common.h)
   for (int b = 0; b < n; ++b)
@@ -335,18 +394,36 @@ __global__ void dice_finalize_kernel(const double* pred_sums, const double* att_
       coef[n * 4 + (l * n + b) * 2 + 0] = (float)(-2.0 / D * wgt);
       coef[n * 4 + (l * n + b) * 2 + 1] = (float)(num / (D * D) * wgt);
     }
+  if (ce_sums) {
+    const double sbg = vsseg_fx_get(ce_sums, VSSEG_FX_STAT), sfg = vsseg_fx_get(ce_sums + 1, VSSEG_FX_STAT), nfg = vsseg_fx_get(ce_sums + 2, VSSEG_FX_STAT);
+    const double W = (voxels - nfg) + ce_fg_weight * nfg + total * 0.0;  // (+ NaN when poisoned: the coefficients too)
+    total += ce_weight * (sbg + ce_fg_weight * sfg) / W;
+    ce_coef[0] = (float)(ce_weight / W);
+    ce_coef[1] = (float)(ce_weight * ce_fg_weight / W);
+  }
   *loss = (float)total;
 }
 extern "C" int vsseg_dice_finalize(const double* pred_sums, const double* att_sums, int32_t n, int32_t nlevels, float* loss, float* coef, void* stream) {
   VSSEG_CHECK(pred_sums && loss && coef && (nlevels == 0 || att_sums), "vsseg_dice_finalize: bad arguments");
   VSSEG_FX_FLAG(fxflag, "vsseg_dice_finalize");
-  hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(64), 0, as_stream(stream), pred_sums, att_sums, n, nlevels, loss, coef, fxflag);
+  hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(64), 0, as_stream(stream), pred_sums, att_sums, n, nlevels, loss, coef, fxflag, (const double*)nullptr, 0.0, 0.0, 0.0, (float*)nullptr);
   VSSEG_LAUNCH_CHECK("vsseg_dice_finalize");
+  return VSSEG_OK;
+}
+extern "C" int vsseg_dice_ce_finalize(const double* pred_sums, const double* att_sums, int32_t n, int32_t nlevels, const double* ce_sums, int64_t nvox, double ce_weight, double ce_foreground_weight, float* loss, float* coef,
+                                      float* ce_coef, void* stream) {
+  VSSEG_CHECK(pred_sums && loss && coef && (nlevels == 0 || att_sums) && ce_sums && ce_coef && n >= 1 && nvox >= 1, "vsseg_dice_ce_finalize: bad arguments");
+  VSSEG_CHECK(ce_weight >= 0.0 && ce_weight < INFINITY && ce_foreground_weight > 0.0 && ce_foreground_weight < INFINITY, "vsseg_dice_ce_finalize: ce_weight must be finite and >= 0, ce_foreground_weight finite and > 0");
+  VSSEG_FX_FLAG(fxflag, "vsseg_dice_ce_finalize");
+  hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(64), 0, as_stream(stream), pred_sums, att_sums, n, nlevels, loss, coef, fxflag, ce_sums, (double)n * (double)nvox, ce_weight, ce_foreground_weight, ce_coef);
+  VSSEG_LAUNCH_CHECK("vsseg_dice_ce_finalize");
   return VSSEG_OK;
 }
 
 // d(loss)/d(logits) of one voxel: through the Dice sums, the (non-detached) hardness weight (ref :279-283) and the softmax
-__device__ __forceinline__ float2 dice_pred_grad(float l0, float l1, float lab, int hardness, float A0, float B0, float A1, float B1) {
+// CE: + the gradient of the cross-entropy term of the voxel, k * w[y] * (softmax(x) - onehot(y)) with kbg = k * w[0], kfg = k * w[1] (vsseg_dice_ce_finalize's ce_coef),
+// formed from the OTHER class's probability — (+kfg p0, -kfg p0) for y = 1, (-kbg p1, +kbg p1) for y = 0: p_y - 1 cancels once p_y rounds to 1 — and added in fp32
+template <bool CE> __device__ __forceinline__ float2 dice_pred_grad(float l0, float l1, float lab, int hardness, float A0, float B0, float A1, float B1, float kbg, float kfg) {
   const float m = fmaxf(l0, l1), e0 = __expf(l0 - m), e1 = __expf(l1 - m), inv = 1.f / (e0 + e1);
   const float p0 = e0 * inv, p1 = e1 * inv;
   const int cls = (int)(long long)lab;
@@ -362,18 +439,26 @@ __device__ __forceinline__ float2 dice_pred_grad(float l0, float l1, float lab, 
   const float dp0 = A0 * g0 * t0 + B0 * (g0 * s0 + t0);
   const float dp1 = A1 * g1 * t1 + B1 * (g1 * s1 + t1);
   const float dot = dp0 * p0 + dp1 * p1;
-  return make_float2(p0 * (dp0 - dot), p1 * (dp1 - dot));
+  float2 r = make_float2(p0 * (dp0 - dot), p1 * (dp1 - dot));
+  if constexpr (CE) {
+    const float c = cls == 1 ? kfg * p0 : -(kbg * p1);
+    r.x += c; r.y -= c;
+  }
+  return r;
 }
 // OUT 0: fp32 [voxel][2];  1: bf16 [voxel][2] (the compact operand of the marching backward kernels);  2: bf16 rows of 8 channels, channels 2..7 written as zeros;
 // 3: fp32, any pitch (channels >= 2 are not touched).  1-3 are the layouts the training plan stages the gradient in (vsseg_dice_pred_bwd_to): written here, the
 // fp32 tensor and the cast pass over it (0.3 GB read + written per step at 4 x 384x128x128) do not exist.  Same values: the cast was the same round-to-nearest-even.
-template <int OUT> __global__ __launch_bounds__(256) void dice_pred_bwd_kernel(const float* __restrict__ logits, int pitch, const float* __restrict__ label, int64_t nvox, int hardness, const float* __restrict__ coef,
-                                                                                 const float* __restrict__ gscale, void* __restrict__ dst, int dpitch) {
+// CE: the cross-entropy gradient is formed here as well (vsseg_dice_ce_pred_bwd / _to) and the sum is stored once — a second pass would round the bf16 operand twice.
+template <int OUT, bool CE> __global__ __launch_bounds__(256) void dice_pred_bwd_kernel(const float* __restrict__ logits, int pitch, const float* __restrict__ label, int64_t nvox, int hardness, const float* __restrict__ coef,
+                                                                                          const float* __restrict__ gscale, void* __restrict__ dst, int dpitch, const float* __restrict__ ce_coef) {
   const int b = blockIdx.y;
   const float* lg = logits + (int64_t)b * nvox * pitch;
   const float* lb = label + (int64_t)b * nvox;
   const float gs = gscale ? *gscale : 1.f;
   const float A0 = coef[(b * 2 + 0) * 2] * gs, B0 = coef[(b * 2 + 0) * 2 + 1] * gs, A1 = coef[(b * 2 + 1) * 2] * gs, B1 = coef[(b * 2 + 1) * 2 + 1] * gs;
+  float kbg = 0.f, kfg = 0.f;
+  if constexpr (CE) { kbg = ce_coef[0] * gs; kfg = ce_coef[1] * gs; }
   const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
   auto store = [&](int64_t v, float2 g) {
     const int64_t e = ((int64_t)b * nvox + v) * dpitch;
@@ -386,8 +471,8 @@ template <int OUT> __global__ __launch_bounds__(256) void dice_pred_bwd_kernel(c
     const float4* lb4 = reinterpret_cast<const float4*>(lb);
     for (int64_t i = tid; i < (nvox >> 2); i += nthr) {
       const float4 a = lg4[2 * i], c = lg4[2 * i + 1], g = lb4[i];
-      const float2 r0 = dice_pred_grad(a.x, a.y, g.x, hardness, A0, B0, A1, B1), r1 = dice_pred_grad(a.z, a.w, g.y, hardness, A0, B0, A1, B1);
-      const float2 r2 = dice_pred_grad(c.x, c.y, g.z, hardness, A0, B0, A1, B1), r3 = dice_pred_grad(c.z, c.w, g.w, hardness, A0, B0, A1, B1);
+      const float2 r0 = dice_pred_grad<CE>(a.x, a.y, g.x, hardness, A0, B0, A1, B1, kbg, kfg), r1 = dice_pred_grad<CE>(a.z, a.w, g.y, hardness, A0, B0, A1, B1, kbg, kfg);
+      const float2 r2 = dice_pred_grad<CE>(c.x, c.y, g.z, hardness, A0, B0, A1, B1, kbg, kfg), r3 = dice_pred_grad<CE>(c.z, c.w, g.w, hardness, A0, B0, A1, B1, kbg, kfg);
       if constexpr (OUT == 0) {
         float4* o = reinterpret_cast<float4*>(reinterpret_cast<float*>(dst) + ((int64_t)b * nvox + 4 * i) * 2);
         o[0] = make_float4(r0.x, r0.y, r1.x, r1.y);
@@ -401,33 +486,52 @@ template <int OUT> __global__ __launch_bounds__(256) void dice_pred_bwd_kernel(c
   } else {
     for (int64_t v = tid; v < nvox; v += nthr) {
       const float2 l = *reinterpret_cast<const float2*>(lg + v * pitch);
-      store(v, dice_pred_grad(l.x, l.y, lb[v], hardness, A0, B0, A1, B1));
+      store(v, dice_pred_grad<CE>(l.x, l.y, lb[v], hardness, A0, B0, A1, B1, kbg, kfg));
     }
   }
 }
-static int dice_pred_bwd_launch(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* gscale, void* dst, int out, int dpitch, void* stream,
-                                const char* who) {
-  VSSEG_CHECK(logits && label && coef && dst && pitch >= 2 && pitch % 2 == 0 && n >= 1, "%s: bad arguments", who);
+template <bool CE>
+static int dice_pred_bwd_launch(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* ce_coef, const float* gscale, void* dst, int out, int dpitch,
+                                void* stream, const char* who) {
+  VSSEG_CHECK(logits && label && coef && dst && pitch >= 2 && pitch % 2 == 0 && n >= 1 && (!CE || ce_coef), "%s: bad arguments", who);
   dim3 g(grid_for((nvox + 3) / 4, 256, 2048), n), t(256);
   hipStream_t s = as_stream(stream);
-  if (out == 0) hipLaunchKernelGGL(dice_pred_bwd_kernel<0>, g, t, 0, s, logits, pitch, label, nvox, hardness, coef, gscale, dst, 2);
-  else if (out == 1) hipLaunchKernelGGL(dice_pred_bwd_kernel<1>, g, t, 0, s, logits, pitch, label, nvox, hardness, coef, gscale, dst, 2);
-  else if (out == 2) hipLaunchKernelGGL(dice_pred_bwd_kernel<2>, g, t, 0, s, logits, pitch, label, nvox, hardness, coef, gscale, dst, 8);
-  else hipLaunchKernelGGL(dice_pred_bwd_kernel<3>, g, t, 0, s, logits, pitch, label, nvox, hardness, coef, gscale, dst, dpitch);
+  if (out == 0) hipLaunchKernelGGL((dice_pred_bwd_kernel<0, CE>), g, t, 0, s, logits, pitch, label, nvox, hardness, coef, gscale, dst, 2, ce_coef);
+  else if (out == 1) hipLaunchKernelGGL((dice_pred_bwd_kernel<1, CE>), g, t, 0, s, logits, pitch, label, nvox, hardness, coef, gscale, dst, 2, ce_coef);
+  else if (out == 2) hipLaunchKernelGGL((dice_pred_bwd_kernel<2, CE>), g, t, 0, s, logits, pitch, label, nvox, hardness, coef, gscale, dst, 8, ce_coef);
+  else hipLaunchKernelGGL((dice_pred_bwd_kernel<3, CE>), g, t, 0, s, logits, pitch, label, nvox, hardness, coef, gscale, dst, dpitch, ce_coef);
   VSSEG_LAUNCH_CHECK(who);
   return VSSEG_OK;
 }
+// the layout (OUT of dice_pred_bwd_kernel) a staged destination asks for, or -1 with the error set
+static int dice_pred_bwd_layout(const vsseg_tensor& dst, int32_t n, int64_t nvox, const char* who) {
+  if (!(dst.ptr && !dst.ptr2 && dst.c == 2 && dst.pitch >= 2 && tensor_voxels(dst) == (int64_t)n * nvox)) {
+    vsseg_set_error("%s: destination is not a 2-channel tensor of %lld voxels", who, (long long)n * nvox);
+    return -1;
+  }
+  if (dst.dtype == VSSEG_BF16 && dst.pitch == 2) return 1;
+  if (dst.dtype == VSSEG_BF16 && dst.pitch == 8 && (reinterpret_cast<uintptr_t>(dst.ptr) & 15) == 0) return 2;
+  if (dst.dtype == VSSEG_F32 && dst.pitch % 2 == 0) return dst.pitch == 2 ? 0 : 3;
+  vsseg_set_error("%s: destination layout (dtype %d, pitch %d) is not one the training plan stages the gradient in", who, dst.dtype, dst.pitch);
+  return -1;
+}
 extern "C" int vsseg_dice_pred_bwd(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* gscale, float* dlogits, void* stream) {
-  return dice_pred_bwd_launch(logits, pitch, label, n, nvox, hardness, coef, gscale, dlogits, 0, 2, stream, "vsseg_dice_pred_bwd");
+  return dice_pred_bwd_launch<false>(logits, pitch, label, n, nvox, hardness, coef, nullptr, gscale, dlogits, 0, 2, stream, "vsseg_dice_pred_bwd");
 }
 extern "C" int vsseg_dice_pred_bwd_to(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* gscale, vsseg_tensor dst, void* stream) {
-  VSSEG_CHECK(dst.ptr && !dst.ptr2 && dst.c == 2 && dst.pitch >= 2 && tensor_voxels(dst) == (int64_t)n * nvox, "vsseg_dice_pred_bwd_to: destination is not a 2-channel tensor of %lld voxels", (long long)n * nvox);
-  int out;
-  if (dst.dtype == VSSEG_BF16 && dst.pitch == 2) out = 1;
-  else if (dst.dtype == VSSEG_BF16 && dst.pitch == 8 && (reinterpret_cast<uintptr_t>(dst.ptr) & 15) == 0) out = 2;
-  else if (dst.dtype == VSSEG_F32 && dst.pitch % 2 == 0) out = dst.pitch == 2 ? 0 : 3;
-  else { vsseg_set_error("vsseg_dice_pred_bwd_to: destination layout (dtype %d, pitch %d) is not one the training plan stages the gradient in", dst.dtype, dst.pitch); return VSSEG_EINVAL; }
-  return dice_pred_bwd_launch(logits, pitch, label, n, nvox, hardness, coef, gscale, dst.ptr, out, dst.pitch, stream, "vsseg_dice_pred_bwd_to");
+  const int out = dice_pred_bwd_layout(dst, n, nvox, "vsseg_dice_pred_bwd_to");
+  if (out < 0) return VSSEG_EINVAL;
+  return dice_pred_bwd_launch<false>(logits, pitch, label, n, nvox, hardness, coef, nullptr, gscale, dst.ptr, out, dst.pitch, stream, "vsseg_dice_pred_bwd_to");
+}
+extern "C" int vsseg_dice_ce_pred_bwd(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* ce_coef, const float* gscale, float* dlogits,
+                                      void* stream) {
+  return dice_pred_bwd_launch<true>(logits, pitch, label, n, nvox, hardness, coef, ce_coef, gscale, dlogits, 0, 2, stream, "vsseg_dice_ce_pred_bwd");
+}
+extern "C" int vsseg_dice_ce_pred_bwd_to(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* ce_coef, const float* gscale, vsseg_tensor dst,
+                                         void* stream) {
+  const int out = dice_pred_bwd_layout(dst, n, nvox, "vsseg_dice_ce_pred_bwd_to");
+  if (out < 0) return VSSEG_EINVAL;
+  return dice_pred_bwd_launch<true>(logits, pitch, label, n, nvox, hardness, coef, ce_coef, gscale, dst.ptr, out, dst.pitch, stream, "vsseg_dice_ce_pred_bwd_to");
 }
 
 __global__ void dice_att_bwd_kernel(const float* __restrict__ label, int64_t nvox, const float* __restrict__ coef, const float* __restrict__ gscale, float* __restrict__ datt) {

@@ -6,15 +6,36 @@ w = 0.6 |softmax(x) - onehot(target)| + 0.4 (differentiable, ref :279-283).
 Forward = label pyramid + per-sample fp64 reductions (logits read once); backward = one elementwise kernel for the
 logits and one per supervised attention map.  Returns a 0-dim tensor supporting `.backward()` / `.item()`
 (ref call sites: params/VSparams.py:460-463, 488-492).
+
+Beyond the reference: `ce_weight` adds a voxel-wise cross-entropy term on the final logits (MONAI's DiceCELoss, nnU-Net's default loss),
+loss += ce_weight * F.cross_entropy(logits, target == 1, weight=[1, ce_foreground_weight]) — one more reduction pass forward, its gradient
+formed inside the Dice backward kernel (include/vsseg_hip.h).  0 (the default) issues exactly the launches of the plain Dice loss.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence
+import math
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 from torch.nn.modules.loss import _Loss
 
 from .. import _lib as L
+
+
+def check_ce(ce_weight: float, ce_foreground_weight: float = 1.0) -> Tuple[float, float]:
+    """The two numbers of the cross-entropy term as floats, or ValueError: ce_weight finite and >= 0 (0: the term is off), ce_foreground_weight finite and > 0,
+    and not a foreground weight without the term — a flag that would silently do nothing."""
+    try:
+        lam, wfg = float(ce_weight), float(ce_foreground_weight)
+    except (TypeError, ValueError):
+        raise ValueError(f"ce_weight and ce_foreground_weight must be numbers (got {ce_weight!r}, {ce_foreground_weight!r})") from None
+    if not math.isfinite(lam) or lam < 0:
+        raise ValueError(f"ce_weight must be finite and >= 0 (got {ce_weight!r})")
+    if not math.isfinite(wfg) or wfg <= 0:
+        raise ValueError(f"ce_foreground_weight must be finite and > 0 (got {ce_foreground_weight!r})")
+    if lam == 0 and wfg != 1:
+        raise ValueError(f"ce_foreground_weight = {ce_foreground_weight!r} has no effect without the cross-entropy term: give ce_weight > 0 as well")
+    return lam, wfg
 
 
 def _cl_logits(x: torch.Tensor) -> torch.Tensor:
@@ -33,11 +54,12 @@ def _c1(x: torch.Tensor) -> torch.Tensor:
 
 
 class _State:
-    """What the forward leaves for the backward: channels-last logits, labels (full resolution + the pyramid), the coefficients of vsseg_dice_finalize."""
-    __slots__ = ("lg", "lab", "labels", "coef", "hardness", "nl", "shape", "att_shapes", "loss")
+    """What the forward leaves for the backward: channels-last logits, labels (full resolution + the pyramid), the coefficients of vsseg_dice_finalize
+    (and, with the cross-entropy term, the two of vsseg_dice_ce_finalize; None without it)."""
+    __slots__ = ("lg", "lab", "labels", "coef", "ce_coef", "hardness", "nl", "shape", "att_shapes", "loss")
 
 
-def _dice_forward(logits, target, supervised, hardness, atts) -> _State:
+def _dice_forward(logits, target, supervised, hardness, atts, ce=(0.0, 1.0)) -> _State:
     lib = L.lib()
     stream = torch.cuda.current_stream().cuda_stream
     dev = logits.device
@@ -49,9 +71,11 @@ def _dice_forward(logits, target, supervised, hardness, atts) -> _State:
     lg, lab = _cl_logits(logits), _c1(target)
     nvox = X * Y * Z
     nl = len(atts) if supervised else 0
-    sums = torch.empty(B * 6 + max(nl, 1) * B * 3, dtype=torch.float64, device=dev)  # [pred | att levels], zeroed through the C ABI (no ATen fill kernels on the step)
+    ce_on = ce[0] > 0
+    nsums = B * 6 + max(nl, 1) * B * 3
+    sums = torch.empty(nsums + (3 if ce_on else 0), dtype=torch.float64, device=dev)  # [pred | att levels | CE], zeroed through the C ABI (no ATen fill kernels on the step)
     L.check(lib.vsseg_memset_zero(sums.data_ptr(), sums.numel() * 8, stream), "memset_zero")
-    pred_sums, att_sums = sums[: B * 6], sums[B * 6 :]
+    pred_sums, att_sums, ce_sums = sums[: B * 6], sums[B * 6 : nsums], sums[nsums:]
     labels: List[torch.Tensor] = []
     plan = _fused_plan(B, (X, Y, Z), [tuple(a.shape) for a in atts], lg, lab, [_c1(a) for a in atts]) if nl else None
     if plan is not None:
@@ -97,8 +121,14 @@ def _dice_forward(logits, target, supervised, hardness, atts) -> _State:
             labels.append(g)
     loss = torch.empty((), dtype=torch.float32, device=dev)  # vsseg_dice_finalize assigns the loss and every coefficient it is asked for
     coef = torch.empty(B * 4 + max(nl, 1) * B * 2, dtype=torch.float32, device=dev)
-    L.check(lib.vsseg_dice_finalize(pred_sums.data_ptr(), att_sums.data_ptr(), B, nl, loss.data_ptr(), coef.data_ptr(), stream), "dice_finalize")
     st = _State()
+    if ce_on:  # one more pass over logits and label; the finalize decodes its three sums too and leaves the two gradient coefficients on the device
+        L.check(lib.vsseg_ce_sums(lg.data_ptr(), 2, lab.data_ptr(), B, nvox, ce_sums.data_ptr(), stream), "ce_sums")
+        st.ce_coef = torch.empty(2, dtype=torch.float32, device=dev)
+        L.check(lib.vsseg_dice_ce_finalize(pred_sums.data_ptr(), att_sums.data_ptr(), B, nl, ce_sums.data_ptr(), nvox, ce[0], ce[1], loss.data_ptr(), coef.data_ptr(), st.ce_coef.data_ptr(), stream), "dice_ce_finalize")
+    else:
+        st.ce_coef = None
+        L.check(lib.vsseg_dice_finalize(pred_sums.data_ptr(), att_sums.data_ptr(), B, nl, loss.data_ptr(), coef.data_ptr(), stream), "dice_finalize")
     st.lg, st.lab, st.labels, st.coef, st.hardness, st.nl, st.shape = lg, lab, labels, coef, int(hardness), nl, (B, X, Y, Z)
     st.att_shapes = [tuple(a.shape) for a in atts]
     st.loss = loss
@@ -133,8 +163,8 @@ def _att_backward(st: _State, level: int, gs_ptr, dst: torch.Tensor):
 
 class _DiceFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, target, supervised, hardness, *atts):
-        ctx.st = st = _dice_forward(logits, target, supervised, hardness, atts)
+    def forward(ctx, logits, target, supervised, hardness, ce, *atts):
+        ctx.st = st = _dice_forward(logits, target, supervised, hardness, atts, ce)
         return st.loss
 
     @staticmethod
@@ -146,24 +176,28 @@ class _DiceFn(torch.autograd.Function):
         dev = st.lg.device
         gs = gout.detach().to(torch.float32).contiguous()
         dlog = torch.empty((B, X, Y, Z, 2), dtype=torch.float32, device=dev)
-        L.check(lib.vsseg_dice_pred_bwd(st.lg.data_ptr(), 2, st.lab.data_ptr(), B, X * Y * Z, st.hardness, st.coef.data_ptr(), gs.data_ptr(), dlog.data_ptr(), stream), "dice_pred_bwd")
+        if st.ce_coef is None:
+            L.check(lib.vsseg_dice_pred_bwd(st.lg.data_ptr(), 2, st.lab.data_ptr(), B, X * Y * Z, st.hardness, st.coef.data_ptr(), gs.data_ptr(), dlog.data_ptr(), stream), "dice_pred_bwd")
+        else:
+            L.check(lib.vsseg_dice_ce_pred_bwd(st.lg.data_ptr(), 2, st.lab.data_ptr(), B, X * Y * Z, st.hardness, st.coef.data_ptr(), st.ce_coef.data_ptr(), gs.data_ptr(), dlog.data_ptr(), stream), "dice_ce_pred_bwd")
         datts: List[Optional[torch.Tensor]] = [None] * len(st.att_shapes)
         for level in range(st.nl):
             i = st.nl - level - 1
             d = torch.empty(st.att_shapes[i], dtype=torch.float32, device=dev)
             _att_backward(st, level, gs.data_ptr(), d)
             datts[i] = d
-        return (dlog.permute(0, 4, 1, 2, 3), None, None, None, *datts)
+        return (dlog.permute(0, 4, 1, 2, 3), None, None, None, None, *datts)
 
 
 class Dice_spvPA(_Loss):
     def __init__(self, include_background: bool = True, to_onehot_y: bool = False, sigmoid: bool = False, softmax: bool = False, other_act=None, squared_pred: bool = False,
-                 jaccard: bool = False, reduction="mean", supervised_attention=True, hardness_weighting=True) -> None:
+                 jaccard: bool = False, reduction="mean", supervised_attention=True, hardness_weighting=True, ce_weight: float = 0.0, ce_foreground_weight: float = 1.0) -> None:
         super().__init__(reduction=getattr(reduction, "value", reduction))
         if other_act is not None and not callable(other_act):
             raise TypeError(f"other_act must be None or callable but is {type(other_act).__name__}.")
         if int(sigmoid) + int(softmax) + int(other_act is not None) > 1:
             raise ValueError("Incompatible values: more than 1 of [sigmoid=True, softmax=True, other_act is not None].")
+        self.ce_weight, self.ce_foreground_weight = check_ce(ce_weight, ce_foreground_weight)  # beyond the reference: + ce_weight * cross-entropy on the final logits
         # the reference's Dice_spvPA.forward ignores every option except the two below (it builds its inner Dice objects with fixed options)
         self.include_background, self.to_onehot_y, self.sigmoid, self.softmax = include_background, to_onehot_y, sigmoid, softmax
         self.other_act, self.squared_pred, self.jaccard = other_act, squared_pred, jaccard
@@ -177,7 +211,7 @@ class Dice_spvPA(_Loss):
         if smooth != 1e-5:
             raise NotImplementedError("smooth is fixed at 1e-5 (the value the reference always uses)")
         atts: Sequence[torch.Tensor] = list(att_maps) if self.supervised_attention else []
-        return _DiceFn.apply(x, target, bool(self.supervised_attention), bool(self.hardness_weighting), *atts)
+        return _DiceFn.apply(x, target, bool(self.supervised_attention), bool(self.hardness_weighting), (self.ce_weight, self.ce_foreground_weight), *atts)
 
     def forward_backward_into(self, input, target: torch.Tensor, landing):
         """The loss AND its gradients in one call, outside autograd (the fused train step of vs_seg_amd.parallel.DataParallelTrainer): d(loss)/d(logits) and
@@ -191,10 +225,13 @@ class Dice_spvPA(_Loss):
         atts: Sequence[torch.Tensor] = list(att_maps) if self.supervised_attention else []
         glogits_dst, gatt_bufs = landing
         with torch.no_grad():
-            st = _dice_forward(x, target, bool(self.supervised_attention), bool(self.hardness_weighting), atts)
+            st = _dice_forward(x, target, bool(self.supervised_attention), bool(self.hardness_weighting), atts, (self.ce_weight, self.ce_foreground_weight))
             B, X, Y, Z = st.shape
             stream = torch.cuda.current_stream().cuda_stream
-            L.check(L.lib().vsseg_dice_pred_bwd_to(st.lg.data_ptr(), 2, st.lab.data_ptr(), B, X * Y * Z, st.hardness, st.coef.data_ptr(), None, glogits_dst, stream), "dice_pred_bwd_to")
+            if st.ce_coef is None:
+                L.check(L.lib().vsseg_dice_pred_bwd_to(st.lg.data_ptr(), 2, st.lab.data_ptr(), B, X * Y * Z, st.hardness, st.coef.data_ptr(), None, glogits_dst, stream), "dice_pred_bwd_to")
+            else:
+                L.check(L.lib().vsseg_dice_ce_pred_bwd_to(st.lg.data_ptr(), 2, st.lab.data_ptr(), B, X * Y * Z, st.hardness, st.coef.data_ptr(), st.ce_coef.data_ptr(), None, glogits_dst, stream), "dice_ce_pred_bwd_to")
             written, coarse = [], []
             for level in range(st.nl):
                 i = st.nl - level - 1

@@ -26,7 +26,7 @@ from typing import Dict, Iterator, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import Adam, Dice_spvPA, UNet2d5_spvPA, compute_dice_score, sliding_window_inference
+from . import Adam, Dice_spvPA, UNet2d5_spvPA, check_ce, compute_dice_score, sliding_window_inference
 from .inferers import argmax_segmentation, tta_masks
 from .metrics import compute_surface_distances, voxel_spacing
 from .postprocess import keep_largest_component
@@ -111,9 +111,12 @@ class VSparams:
         parser.add_argument("--aug_contrast", type=float, default=0.0, metavar="FRAC", help="training augmentation: scale the image of a training patch about its mean by a factor drawn from [1 - FRAC, 1 + FRAC], clipped to the range it had (0: off)")
         parser.add_argument("--aug_gamma", type=float, default=0.0, metavar="FRAC", help="training augmentation: apply a gamma curve over the value range of the image of a training patch, with an exponent drawn from [1 - FRAC, 1 + FRAC] (0: off)")
         parser.add_argument("--aug_appearance_prob", type=float, default=0.25, metavar="P", help="probability with which each of the blur, low-resolution, contrast and gamma augmentations is applied to a training sample, independently of the others")
+        parser.add_argument("--ce_weight", type=float, default=0.0, metavar="LAMBDA", help="training loss: add LAMBDA times the voxel-wise cross-entropy of the final logits to the Dice loss (the Dice + CE loss of nnU-Net, MONAI's DiceCELoss; 0: off, the reference's loss)")
+        parser.add_argument("--ce_foreground_weight", type=float, default=1.0, metavar="W", help="class weight of the foreground voxels in the cross-entropy term, the background's being 1 (needs --ce_weight > 0)")
         args = parser.parse_args(argv)
         try:
             tta_masks(args.tta_flips, args.tta_average)
+            ce_weight, ce_foreground_weight = check_ce(args.ce_weight, args.ce_foreground_weight)
             augment = check_augment(*(getattr(args, "aug_" + k) for k in AUGMENT_KEYS))
             field = check_field_augment(args.aug_elastic_mag, args.aug_bias_field, args.aug_field_spacing)
             appearance = check_appearance_augment(*(getattr(args, "aug_" + k) for k in APPEARANCE_KEYS))
@@ -144,6 +147,7 @@ class VSparams:
         self.aug_rotate_deg, self.aug_scale, self.aug_intensity_scale, self.aug_intensity_shift, self.aug_noise_std = (augment[k] for k in AUGMENT_KEYS)
         self.aug_elastic_mag, self.aug_bias_field, self.aug_field_spacing = (field[k] for k in FIELD_KEYS)
         self.aug_blur_sigma, self.aug_lowres, self.aug_contrast, self.aug_gamma, self.aug_appearance_prob = (appearance[k] for k in APPEARANCE_KEYS)
+        self.ce_weight, self.ce_foreground_weight = ce_weight, ce_foreground_weight
         self.results_folder_path = os.path.join(self.data_root, "results", "debug" if self.debug else args.results_folder_name)
         self.logs_path = os.path.join(self.results_folder_path, "logs")
         self.model_path = os.path.join(self.results_folder_path, "model")
@@ -181,7 +185,7 @@ class VSparams:
                       ("keep_largest_component", "component_connectivity") if self.keep_largest_component else ()) + (("tta_flips", "tta_average") if self.tta_flips else ()) + (
                           tuple("aug_" + k for k in AUGMENT_KEYS) if any(self.augment.values()) else ()) + (
                               ("aug_elastic_mag", "aug_bias_field", "aug_field_spacing") if self.aug_elastic_mag or self.aug_bias_field else ()) + (
-                                  tuple("aug_" + k for k in APPEARANCE_KEYS) if self._appearance_on else ()):
+                                  tuple("aug_" + k for k in APPEARANCE_KEYS) if self._appearance_on else ()) + (("ce_weight", "ce_foreground_weight") if self.ce_weight > 0 else ()):
             log("{:<34s} {}".format(k + " =", getattr(self, k)))
         log("-" * 10)
 
@@ -298,7 +302,7 @@ class VSparams:
 
     def set_and_get_loss_function(self):
         self.logger.info("Setting up the loss function...")
-        return Dice_spvPA(to_onehot_y=True, softmax=True, supervised_attention=self.attention, hardness_weighting=self.hardness)
+        return Dice_spvPA(to_onehot_y=True, softmax=True, supervised_attention=self.attention, hardness_weighting=self.hardness, ce_weight=self.ce_weight, ce_foreground_weight=self.ce_foreground_weight)
 
     def set_and_get_optimizer(self, model):
         self.logger.info("Setting up the optimizer...")
