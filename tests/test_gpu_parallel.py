@@ -88,10 +88,10 @@ def test_late_weight_gradient_launches_change_the_order_and_nothing_else(monkeyp
         torch.cuda.synchronize()
         plan = next(p for k, p in m._engine.plans.items() if k[2])
         assert (len(plan._fork_events) > 20) == (bound == "1")
-        moved = [rec for rec in plan.bwd if len(rec) > 2 and rec[2].get("late")]
+        moved = [launch for launch in plan.bwd if launch.late]
         assert len(moved) == {"0": 0, "1": 2, "2": 2}[late]
         if moved:
-            assert plan.bwd[-len(moved):] == moved and not any(rec[2].get("side") for rec in moved)
+            assert all(a is b for a, b in zip(plan.bwd[-len(moved):], moved)) and not any(launch.side for launch in moved)
         res.append((losses, gflat.clone(), flat.clone(), m._bflat.clone()))
     for other in res[1:]:
         assert other[0] == res[0][0]

@@ -1,5 +1,6 @@
 """CPU tests of the host side: the C-ABI library loads and exports every declared symbol, plans lower without a GPU."""
 import ctypes
+import functools
 import os
 import re
 
@@ -54,34 +55,78 @@ def test_depth_that_selects_no_kernel_is_rejected():
     assert b"-10" in lib.vsseg_last_error()
 
 
-@pytest.mark.parametrize("att", [True, False])
-@pytest.mark.parametrize("dt", ["bf16", "fp32"])
-def test_plans_lower_on_cpu(att, dt):
+@functools.lru_cache(maxsize=None)
+def _dry_plans(att, dt):
+    """The engine and its CPU-lowered train (2, 64x32x16) and eval (1, 64x32x16) plans, lowered once for the tests below."""
     lay = ParamLayout(state_manifest(att))
     flat = torch.zeros(lay.n_param)
     eng = Engine(att, dt, flat, torch.zeros_like(flat), torch.zeros(lay.n_buf), torch.zeros(lay.n_cnt, dtype=torch.int64), lay, dry_run=True)
-    tr = eng.plan(2, (64, 32, 16), True)
-    ev = eng.plan(1, (64, 32, 16), False)
+    return eng, eng.plan(2, (64, 32, 16), True), eng.plan(1, (64, 32, 16), False)
+
+
+@pytest.mark.parametrize("att", [True, False])
+@pytest.mark.parametrize("dt", ["bf16", "fp32"])
+def test_plans_lower_on_cpu(att, dt):
+    eng, tr, ev = _dry_plans(att, dt)
     prog = build_program(att)
     n_conv = len(prog.layers)
-    igemms = [r for r in tr.fwd if r[0] is eng.lib.vsseg_igemm]
+    igemms = [r for r in tr.fwd if r.fn is eng.lib.vsseg_igemm]
     # one igemm launch per convolution: the output-parity classes of the transposed convolutions share one launch (planner.class_split_plans);
     # the merged residual conv has none and the 1-channel attention map convolutions run on the narrow kernel
     assert n_conv - 2 <= len(igemms) <= n_conv
-    assert sum(1 for r in igemms if r[1][0]._obj.class_split == 8) == 3 and sum(1 for r in tr.bwd if r[0] is eng.lib.vsseg_igemm and r[1][0]._obj.class_split == 8) == 3
+    assert sum(1 for r in igemms if r.desc.class_split == 8) == 3 and sum(1 for r in tr.bwd if r.fn is eng.lib.vsseg_igemm and r.desc.class_split == 8) == 3
     # (bf16: the stride-1 3x3x1 blocks of the finest levels run BatchNorm-backward apply + data gradient + weight gradient as ONE launch, csrc/mbwd.hip)
-    n_fused = sum(1 for r in tr.bwd if r[0] in (eng.lib.vsseg_conv_bwd_fused, eng.lib.vsseg_wgrad_narrow_bn))
+    n_fused = sum(1 for r in tr.bwd if r.fn in (eng.lib.vsseg_conv_bwd_fused, eng.lib.vsseg_wgrad_narrow_bn))
     assert (n_fused >= 2) == (dt == "bf16")
-    assert sum(1 for r in tr.bwd if r[0] in (eng.lib.vsseg_wgrad, eng.lib.vsseg_wgrad_narrow)) + n_fused == n_conv - len(tr.merged)  # the final 1x1x1 residual conv is merged into the final 3x3x1 conv
-    assert len(tr.merged) == 1 and sum(1 for r in tr.bwd if r[0] is eng.lib.vsseg_merge_residual_grads) == 1
+    assert sum(1 for r in tr.bwd if r.fn in (eng.lib.vsseg_wgrad, eng.lib.vsseg_wgrad_narrow)) + n_fused == n_conv - len(tr.merged)  # the final 1x1x1 residual conv is merged into the final 3x3x1 conv
+    assert len(tr.merged) == 1 and sum(1 for r in tr.bwd if r.fn is eng.lib.vsseg_merge_residual_grads) == 1
     assert len(ev.bwd) == 0 and len(ev.fwd) < len(tr.fwd)
     # every dropout launch reads the seed through the plan's device scalar (fixed arguments: the lists can be captured as hipGraphs)
-    seeded = [r for lst in (tr.fwd, tr.bwd) for r in lst if tr.seed_dev.data_ptr() in [a for a in r[1] if isinstance(a, int)]]
+    seeded = [r for lst in (tr.fwd, tr.bwd) for r in lst if tr.seed_dev.data_ptr() in [a for a in r.args if isinstance(a, int)]]
     assert len(seeded) == 3 * sum(1 for L_ in prog.layers if L_.has_bn) - n_fused and len(tr.bwd_pre) == 1 and len(tr.ext_slots) == 1  # (a fused launch reads the stored keep-mask: no seed)
     # the LDS request the C side computes equals the planner's (mirrored formula)
-    for rec in igemms[:10]:
-        d = rec[1][0]._obj
-        assert eng.lib.vsseg_igemm_lds_bytes(ctypes.byref(d)) > 0
+    for r in igemms[:10]:
+        assert eng.lib.vsseg_igemm_lds_bytes(ctypes.byref(r.desc)) > 0
+
+
+def _scratch_of(launch):
+    """(pointer, element count) of a weight-gradient launch's partial-sum scratch: the descriptor's fields, or — the narrow entry point — the two arguments
+    its prototype in include/vsseg_hip.h calls scratch and scratch_elems."""
+    if launch.desc is not None:
+        return launch.desc.scratch, launch.desc.scratch_elems
+    header = re.sub(r"/\*.*?\*/", "", open("include/vsseg_hip.h").read(), flags=re.S)
+    params = [p.split()[-1].lstrip("*") for p in re.search(r"\bint %s\((.*?)\);" % launch.fn.__name__, header, re.S).group(1).split(",")]
+    i = params.index("scratch")
+    assert params[i + 1] == "scratch_elems" and len(launch.args) == len(params) - 1  # (the runner appends the stream)
+    return launch.args[i], launch.args[i + 1]
+
+
+def test_launch_records_of_the_cpu_plans():
+    """What the runner and Plan._move_late_wgrads rely on in a Launch: the descriptor behind the byref argument, side launches in the backward list only, and the weight
+    gradients moved to the end of the main stream's list — off the side stream, on the main stream's scratch, while every other one keeps the side stream's."""
+    n_late = 0
+    for att in (True, False):
+        for dt in ("bf16", "fp32"):
+            eng, tr, ev = _dry_plans(att, dt)
+            lib, fs, ws = eng.lib, eng.fused_scratch(), eng.wgrad_scratch()
+            assert fs.data_ptr() != ws.data_ptr()
+            for plan in (tr, ev):
+                for lst in (plan.fwd_pre, plan.fwd, plan.bwd_pre, plan.bwd):
+                    for la in lst:
+                        assert la.desc is None or la.args[0]._obj is la.desc, la.name
+                        assert not la.side or lst is plan.bwd, la.name
+                        assert not la.late or lst is plan.bwd, la.name
+            late = [la for la in tr.bwd if la.late]
+            n_late += len(late)
+            assert late and all(a is b for a, b in zip(tr.bwd[-len(late):], late))  # they are the tail of the list
+            for la in tr.bwd:
+                if la.fn in (lib.vsseg_wgrad, lib.vsseg_wgrad_narrow):
+                    scr = fs if la.late else ws
+                    assert _scratch_of(la) == (scr.data_ptr(), scr.numel()), la.name
+                    assert not (la.late and la.side), la.name
+                else:
+                    assert not la.late, la.name
+    assert n_late == 8
 
 
 @pytest.mark.parametrize("att", [True, False])

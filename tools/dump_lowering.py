@@ -1,4 +1,5 @@
-"""One line per launch of a plan's four lists (fwd_pre, fwd, bwd_pre, bwd): function, arguments, metadata; ctypes descriptors field by field.  Two trees lower the same
+"""One line per launch of a plan's four lists (fwd_pre, fwd, bwd_pre, bwd): function, arguments, then in braces the reporting metadata and the scheduling flags that
+are set; ctypes descriptors field by field.  Two trees lower the same
 launches exactly when their dumps are byte-identical (`diff`): `--dry-run` for the CPU plans of tests/test_host.py::test_plans_lower_on_cpu, else one model on the GPU
 (`--shape NxXxYxZ [--dtype fp32] [--eval]`).  Device addresses print as `storage+byte offset` of the plan's / engine's buffer they lie in (`?`: in none of them, e.g. a
 temporary; `0`: null), `_Slot` arguments as their kind."""
@@ -12,6 +13,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vs_seg_amd.engine import Engine, ParamLayout, _Slot  # noqa: E402
 from vs_seg_amd.graph import HP, state_manifest  # noqa: E402
+
+BYREF = type(C.byref(C.c_int()))  # a launch's byref(descriptor) argument: shown as Launch.desc
 
 
 def storages(plan):
@@ -33,8 +36,6 @@ def address(v, ranges):
 def show(v, ranges, ctype=None):
     if isinstance(v, _Slot):
         return f"<slot {v.kind}>"
-    if hasattr(v, "_obj"):  # ctypes.byref(descriptor)
-        return show(v._obj, ranges)
     if isinstance(v, C.Structure):
         return type(v).__name__ + "{" + ", ".join(f"{f[0]}={show(getattr(v, f[0]), ranges, f[1])}" for f in v._fields_) + "}"
     if isinstance(v, C.Array):
@@ -49,10 +50,10 @@ def show(v, ranges, ctype=None):
 def dump(title, plan, out):
     ranges = storages(plan)
     for lname in ("fwd_pre", "fwd", "bwd_pre", "bwd"):
-        for i, rec in enumerate(getattr(plan, lname)):
-            meta = rec[2] if len(rec) > 2 else {}
-            print(f"{title} {lname}[{i}] {rec[0].__name__}(" + ", ".join(show(a, ranges) for a in rec[1]) + ") {"
-                  + ", ".join(f"{k}={meta[k]!r}" for k in sorted(meta)) + "}", file=out)
+        for i, launch in enumerate(getattr(plan, lname)):
+            braces = dict(launch.meta or {}, **{k: True for k in ("side", "own_dy", "late_ok", "late") if getattr(launch, k)})
+            print(f"{title} {lname}[{i}] {launch.fn.__name__}(" + ", ".join(show(launch.desc if isinstance(a, BYREF) else a, ranges) for a in launch.args) + ") {"
+                  + ", ".join(f"{k}={braces[k]!r}" for k in sorted(braces)) + "}", file=out)
 
 
 def main():

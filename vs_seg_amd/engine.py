@@ -143,6 +143,27 @@ class _Slot:
         self.kind, self.name = kind, name
 
 
+class Launch:
+    """One entry of a plan's launch lists: the runner calls `fn(*args, stream)`.  `args` is the list it reads (Plan._index_slots substitutes `_Slot` entries in
+    place); `desc` is the ctypes descriptor where args[0] is byref(desc) — the record keeps it alive — else None; `meta` is what the profiles report (name, kind,
+    tag, flops, bytes), None where a launch reports nothing.  The rest decides the schedule: `side` = goes to the side stream under Engine.overlap (the weight
+    gradients); `own_dy` / `late_ok` = Plan._move_late_wgrads may move it to the end of the main stream's list, `late` = it did; `scratch_at` = position in `args`
+    of a partial-sum scratch pointer followed by its element count, where those are arguments and not descriptor fields."""
+
+    __slots__ = ("fn", "args", "desc", "meta", "side", "own_dy", "late_ok", "late", "scratch_at")
+
+    def __init__(self, fn, args: list, meta: Optional[dict] = None, *, desc=None, side=False, own_dy=False, late_ok=False, scratch_at: Optional[int] = None):
+        self.fn, self.args, self.desc, self.meta = fn, args, desc, meta
+        self.side, self.own_dy, self.late_ok, self.late, self.scratch_at = side, own_dy, late_ok, False, scratch_at
+
+    @property
+    def name(self) -> str:
+        """What timer events, the timer's `only` filter and error messages call this launch."""
+        if self.meta is not None and "name" in self.meta:
+            return self.meta["name"]
+        return getattr(self.fn, "__name__", "memset")
+
+
 def fill_igemm_desc(d: L.IgemmDesc, pl: P.IgemmPlan):
     """Everything of a launch descriptor that its plan decides (the tensors, the packed weights and the epilogue are the caller's)."""
     d.q, d.is_, d.os, d.oo = L.i3(pl.q), L.i3(pl.cls.is_), L.i3(pl.cls.os), L.i3(pl.cls.oo)
@@ -178,15 +199,14 @@ class Plan:
         self.lv = level_dims(dims, eng.hp)
         self.compact_input: Optional[torch.Tensor] = None  # [N,X,Y,Z,1] copy of the network input for the z-folded first-layer launches
         self.needs_padded_input = False  # set by the first launch descriptor that reads the 8-channel zero-extended copy of the network input (_desc): staged per step only then
-        self.fwd: List[list] = []
-        self.fwd_pre: List[list] = []  # eval only: launches that depend on parameters / buffers alone (BatchNorm folding); re-run with the weight packing when those change
+        self.fwd: List[Launch] = []
+        self.fwd_pre: List[Launch] = []  # eval only: launches that depend on parameters / buffers alone (BatchNorm folding); re-run with the weight packing when those change
         self.params_key = None  # parameter version the packed weights + folded BatchNorm constants of an eval plan belong to
-        self.bwd: List[list] = []
-        self.keep: list = []  # ctypes objects that must outlive the launches
+        self.bwd: List[Launch] = []
         self.bufs: Dict[str, torch.Tensor] = {}
         self.grads: Dict[str, torch.Tensor] = {}
         self.flat_ptr = eng.flat.data_ptr()
-        self.timer = None  # set to {'only': set|None, 'events': []} to time launches with HIP events
+        self.timer = None  # or {'only': None (every launch) | set of Launch.name, 'events': [], optional 'active': bool}: Plan.run appends (name, meta, e0, e1) HIP-event pairs to 'events'
         self.generation = 0  # bumped by every training forward: a backward belongs to exactly one forward of this plan
         # The launch lists have FIXED kernel arguments (the dropout seed is read from `seed_dev`, external gradients are staged into
         # plan-owned buffers), so after two eager warm-up runs each list is captured in a hipGraph and replayed: one host call per list
@@ -195,7 +215,7 @@ class Plan:
         self.gatt_buf: Dict[str, torch.Tensor] = {}
         self._gatt_set: Dict[str, bool] = {}
         self._fork_events: list = []  # events of the side-stream forks (created once, re-recorded every step)
-        self.bwd_pre: List[list] = []  # backward launches that read caller-owned memory (the loss' gradient of the logits): never captured
+        self.bwd_pre: List[Launch] = []  # backward launches that read caller-owned memory (the loss' gradient of the logits): never captured
         self._graphs: Dict[str, object] = {}
         self._graph_runs: Dict[str, int] = {}
         self._tune_gflat: Optional[torch.Tensor] = None  # scratch copy of the gradient buffer the measured weight-gradient launches accumulate into
@@ -539,12 +559,12 @@ class Plan:
             for ch in variant:
                 self._igemm(tmp, ch, inp, out, res=res, probe=True, **kw)
                 wp = self._gather_tmp(ch.probe_plan.pack_map, ch.woff)
-                tmp[-1][1][0]._obj.wpack = wp.data_ptr()
+                tmp[-1].desc.wpack = wp.data_ptr()
                 packs.append(wp)
 
             def run():
-                for fn, args, _meta in tmp:
-                    L.check(fn(*args, stream), "class-split decision")
+                for launch in tmp:
+                    L.check(launch.fn(*launch.args, stream), "class-split decision")
 
             times.append(min(self._event_ms(run) for _ in range(1 + eng.tune_reps)))  # (not _time_launch: here every run is timed, the first included, and a rejected launch is an error)
         use = times[1] < times[0]
@@ -557,8 +577,8 @@ class Plan:
     def _igemm(self, lst, ch: _Choice, inp: L.Tensor, out: L.Tensor, *, bias=0, bias2=0, scale=0, shift=0, alpha=0, act=L.ACT_NONE, res: Optional[L.Tensor] = None,
                res_mode=L.RES_NONE, accumulate=0, stats=0, stats_stride=0, ncls=1, gate=0, nb: Optional[int] = None, in_gate=0, probe=False, res_out: Optional[L.Tensor] = None, bias_res=0,
                in1=None):
-        """probe: build the launch (plan chosen / measured as usual) WITHOUT making it part of the step — no packed-weight registration, the descriptor
-        is only referenced by `lst` (Plan._use_class_split times two alternative lowerings of an op this way; ch.probe_plan = the plan it used)."""
+        """probe: build the launch (plan chosen / measured as usual) WITHOUT making it part of the step — no packed-weight registration
+        (Plan._use_class_split times two alternative lowerings of an op this way; ch.probe_plan = the plan it used)."""
         nb = self.n if nb is None else nb
         d = L.IgemmDesc()
         d.gate = gate or None
@@ -590,7 +610,6 @@ class Plan:
             self._wpack_fixups.append((d, "wpack", ch.map_off))
             if pl.res_tiles:
                 self._wpack_fixups.append((d, "wpack_res", ch.map_off_res))
-            self.keep.append(d)
         nvalid = nb  # output voxels this lattice class writes
         for a, oa in enumerate((out.x, out.y, out.z)):
             nvalid *= min(pl.q[a], -(-(oa - pl.cls.oo[a]) // pl.cls.os[a]))
@@ -609,7 +628,7 @@ class Plan:
                     # accumulating launch has to read: one more output-sized tensor)
                     bytes=float(nvalid) * pl.nc * es_out * (2 if (accumulate or res is not None) else 1) + float(nb) * inp.x * inp.y * inp.z * pl.kreal * es_in / (1 if pl.classes is not None else ncls)
                     + (float(nvalid) * rn * es_out if res_out is not None else 0.0))
-        lst.append([self.eng.lib.vsseg_igemm, [C.byref(d)], meta])
+        lst.append(Launch(self.eng.lib.vsseg_igemm, [C.byref(d)], meta, desc=d))
 
     def _march_cands(self, ch: _Choice, Lr: Layer) -> List[P.IgemmPlan]:
         """The marching-kernel plans of a stride-1 3x3x1 forward launch: those among its candidates when the autotuner listed them, else
@@ -790,7 +809,7 @@ class Plan:
         for op in self.eng.prog.ops:
             if isinstance(op, AttGate):
                 if op.out.name not in self.gate_onload:
-                    self.fwd.append([self.eng.lib.vsseg_att_apply_fwd, [self._desc(op.x), self._alloc(op.att, self.bufs).data_ptr(), self._desc(op.out)], self._ew_meta("att_apply_fwd", op.x.level, 2 * op.x.c + 2)])
+                    self.fwd.append(Launch(self.eng.lib.vsseg_att_apply_fwd, [self._desc(op.x), self._alloc(op.att, self.bufs).data_ptr(), self._desc(op.out)], self._ew_meta("att_apply_fwd", op.x.level, 2 * op.x.c + 2)))
             elif op.layer.prefix in self.chain_second:  # emitted with the first convolution of its chain
                 continue
             elif op.layer.prefix in self.chain_first:
@@ -815,7 +834,7 @@ class Plan:
         if bn:
             ba, bb = self.bn[La.prefix], self.bn[Lb.prefix]
             for Lr, r in ((La, ba), (Lb, bb)):
-                self.fwd_pre.append([lib.vsseg_bn_fold_eval, [r.gamma, r.beta, r.rmean, r.rvar, BN_EPS, r.scale, r.shift, Lr.cout]])
+                self.fwd_pre.append(Launch(lib.vsseg_bn_fold_eval, [r.gamma, r.beta, r.rmean, r.rvar, BN_EPS, r.scale, r.shift, Lr.cout]))
             d.scale_a, d.shift_a, d.alpha_a, d.act_a = ba.scale, ba.shift, ba.alpha, L.ACT_PRELU
             d.scale_b, d.shift_b, d.alpha_b, d.act_b = bb.scale, bb.shift, bb.alpha, L.ACT_PRELU
             if compact:
@@ -843,12 +862,12 @@ class Plan:
         d.wpack_res = dummy.data_ptr() if rcv is not None else None  # (placeholders for the domain check; the real pointers are set once the packed-weight buffer exists)
         if lib.vsseg_conv_chain_lds_bytes(C.byref(d)) < 0:
             raise RuntimeError("vsseg_conv_chain rejected a launch the planner offered: " + lib.vsseg_last_error().decode())
-        self.keep.append(d)
         nvox = float(self.n) * q[0] * q[1] * q[2]
         cin_r = a.x.real
-        self.fwd.append([lib.vsseg_conv_chain, [C.byref(d)], dict(tag=f"chain q={q} K={cin_r}x9 -> {La.cout}x9 -> N={Lb.cout}{'+res' if rcv is not None else ''} tz={plan_c['tz']} waves={plan_c['waves']} mtw={plan_c['mtw']} lead={plan_c['lead']} lx={plan_c['lx']}",
-                                                                  name=f"chain<bf16,{8 if compact else La.cin}>", kind="mfma", flops=2.0 * nvox * (9 * (cin_r * La.cout + La.cout * Lb.cout) + (cin_r * Lb.cout if rcv is not None else 0)),
-                                                                  bytes=nvox * (cin_r * eng.es + Lb.cout * (4 if b.out.kind == "f32" else eng.es) + (La.cout * eng.es if (self.train and not bn) else 0)))])
+        meta = dict(tag=f"chain q={q} K={cin_r}x9 -> {La.cout}x9 -> N={Lb.cout}{'+res' if rcv is not None else ''} tz={plan_c['tz']} waves={plan_c['waves']} mtw={plan_c['mtw']} lead={plan_c['lead']} lx={plan_c['lx']}",
+                    name=f"chain<bf16,{8 if compact else La.cin}>", kind="mfma", flops=2.0 * nvox * (9 * (cin_r * La.cout + La.cout * Lb.cout) + (cin_r * Lb.cout if rcv is not None else 0)),
+                    bytes=nvox * (cin_r * eng.es + Lb.cout * (4 if b.out.kind == "f32" else eng.es) + (La.cout * eng.es if (self.train and not bn) else 0)))
+        self.fwd.append(Launch(lib.vsseg_conv_chain, [C.byref(d)], meta, desc=d))
 
     def _emit_conv_bn_act(self, op: ConvBnAct):
         prog, lib, F = self.eng.prog, self.eng.lib, self.fwd
@@ -875,17 +894,17 @@ class Plan:
             seed = self.seed_dev.data_ptr()  # the kernels read the seed through seed_dev (the salt carries SEED_INDIRECT)
             yd = self._tdesc(self._raw("y:" + pre, Lr.out_level, Lr.cout), Lr.out_level)
             self._igemm_classes(F, cp.fwd, xin, yd, bias=self._pp(Lr.bkey), stats=b.stats_fwd, stats_stride=b.cpad, ncls=len(cp.fwd), **rkw)
-            F.append([lib.vsseg_bn_finalize, [b.stats_fwd, b.cpad, Lr.cout, float(self._vox(Lr.out_level)), b.gamma, b.beta, BN_EPS, BN_MOMENTUM, b.rmean, b.rvar,
-                                              b.counter, b.mean, b.invstd, b.scale, b.shift]])
+            F.append(Launch(lib.vsseg_bn_finalize, [b.stats_fwd, b.cpad, Lr.cout, float(self._vox(Lr.out_level)), b.gamma, b.beta, BN_EPS, BN_MOMENTUM, b.rmean, b.rvar,
+                                                    b.counter, b.mean, b.invstd, b.scale, b.shift]))
             if fused_res is not None:
                 x1 = self._xdesc(fused_res.x, True)  # compact 1-channel copy of the network input
-                F.append([lib.vsseg_bn_act_fwd_res1, [yd, b.scale, b.shift, b.alpha, self.p_drop, seed, b.salt, x1.ptr, self._pp(fused_res.layer.wkey), self._pp(fused_res.layer.bkey), out, b.keep],
-                          self._ew_meta("bn_act_fwd", Lr.out_level, 2 * Lr.cout + 1)])
+                F.append(Launch(lib.vsseg_bn_act_fwd_res1, [yd, b.scale, b.shift, b.alpha, self.p_drop, seed, b.salt, x1.ptr, self._pp(fused_res.layer.wkey), self._pp(fused_res.layer.bkey), out, b.keep],
+                                self._ew_meta("bn_act_fwd", Lr.out_level, 2 * Lr.cout + 1)))
             else:
-                F.append([lib.vsseg_bn_act_fwd, [yd, b.scale, b.shift, b.alpha, self.p_drop, seed, b.salt, res if res is not None else L.Tensor(), 1 if res is not None else 0, out, b.keep],
-                          self._ew_meta("bn_act_fwd", Lr.out_level, (3 if res is not None else 2) * Lr.cout)])
+                F.append(Launch(lib.vsseg_bn_act_fwd, [yd, b.scale, b.shift, b.alpha, self.p_drop, seed, b.salt, res if res is not None else L.Tensor(), 1 if res is not None else 0, out, b.keep],
+                                self._ew_meta("bn_act_fwd", Lr.out_level, (3 if res is not None else 2) * Lr.cout)))
             return
-        self.fwd_pre.append([lib.vsseg_bn_fold_eval, [b.gamma, b.beta, b.rmean, b.rvar, BN_EPS, b.scale, b.shift, Lr.cout]])  # depends on parameters only
+        self.fwd_pre.append(Launch(lib.vsseg_bn_fold_eval, [b.gamma, b.beta, b.rmean, b.rvar, BN_EPS, b.scale, b.shift, Lr.cout]))  # depends on parameters only
         if rcv is not None and op.res is rcv.out:  # out = act(bn(conv(x))) + residual(x) entirely inside the launch: the residual tensor does not exist
             res = None
         pr1 = self.eval_in1.get(pre)
@@ -925,8 +944,8 @@ class Plan:
                 nxs = max(1, round(256 / (self.n * nzb)))  # about one 512-thread workgroup per CU (measured best at batch 1 and 4 on both levels: tools/bench_nconv.py)
                 lx = -(-self.lv[Lr.level][0] // nxs)
                 nq = float(self._vox(Lr.level))
-                F.append([lib.vsseg_conv_to1, [xd, self._pp(Lr.wkey), self._pp(Lr.bkey), ACT_CODE[op.act], od, lx],
-                          dict(name="nconv<bf16>", kind="hbm", flops=2.0 * nq * 9 * Lr.cin, bytes=nq * (2.0 * Lr.cin + (4.0 if od.dtype == L.F32 else 2.0)), tag=f"{Lr.prefix[-40:]} {Lr.cin}->1 k={Lr.kernel} lx={lx}")])
+                F.append(Launch(lib.vsseg_conv_to1, [xd, self._pp(Lr.wkey), self._pp(Lr.bkey), ACT_CODE[op.act], od, lx],
+                                dict(name="nconv<bf16>", kind="hbm", flops=2.0 * nq * 9 * Lr.cin, bytes=nq * (2.0 * Lr.cin + (4.0 if od.dtype == L.F32 else 2.0)), tag=f"{Lr.prefix[-40:]} {Lr.cin}->1 k={Lr.kernel} lx={lx}")))
                 return
         xin, out = self._xdesc(op.x, cp.fold_fwd), self._desc(op.out)
         res = self._desc(op.res) if (op.res is not None and absorbed is None) else None
@@ -969,7 +988,7 @@ class Plan:
                 buf = self._raw("g:logits8", 0, 8)  # channels 2..7 stay zero
                 staged["p"] = self._tdesc(buf, 0)
                 self.glogits_dst = L.Tensor(buf.data_ptr(), _tdtype(buf), logits.c, 8, self.n, *self.lv[0], None, 0, L.ZERO_PADDED)
-            self.bwd_pre.append([self.eng.lib.vsseg_copy_cast, [_Slot("glogits"), self.glogits_dst]])
+            self.bwd_pre.append(Launch(self.eng.lib.vsseg_copy_cast, [_Slot("glogits"), self.glogits_dst]))
         return staged["c" if compact else "p"]
 
     def _contribution(self, spec: TensorSpec) -> int:
@@ -984,7 +1003,7 @@ class Plan:
         self._written[root] = True
         if spec.c != spec.root.c:  # first contribution covers only a channel slice: start from zero
             gbuf = self._alloc(spec, self.grads)
-            self.bwd.append([self.eng.lib.vsseg_memset_zero, [gbuf.data_ptr(), gbuf.numel() * gbuf.element_size()]])
+            self.bwd.append(Launch(self.eng.lib.vsseg_memset_zero, [gbuf.data_ptr(), gbuf.numel() * gbuf.element_size()]))
             return 1
         return 0
 
@@ -1006,13 +1025,15 @@ class Plan:
         if Lr.cin == 1 and Lr.cout in (8, 16, 32, 64) and x.root.name == self.eng.prog.input.name and dy.c == Lr.cout and not dy.ptr2:
             x1 = self._xdesc(x, True)  # the compact one-channel copy of the network input
             assert not bias_grad, "the 1 -> C narrow weight gradient does not reduce a bias gradient (those convolutions sit in front of a BatchNorm)"
-            self.bwd.append([lib.vsseg_wgrad_narrow, [dy, x1.ptr, k3, 1, self._gp(Lr.wkey), k3 * k3, None, scr.data_ptr(), scr.numel()],
-                             dict(name="wgrad_narrow", kind="hbm", side=True, late_ok=(k3 == 1), flops=0.0, bytes=float(es) * self._vox(Lr.level) * (Lr.cout + 1), tag=f"{Lr.prefix[-40:]} 1->{Lr.cout} k={Lr.kernel}")])
+            head = [dy, x1.ptr, k3, 1, self._gp(Lr.wkey), k3 * k3, None]  # (the scratch pair follows: _move_late_wgrads retargets it through scratch_at)
+            self.bwd.append(Launch(lib.vsseg_wgrad_narrow, head + [scr.data_ptr(), scr.numel()],
+                                   dict(name="wgrad_narrow", kind="hbm", flops=0.0, bytes=float(es) * self._vox(Lr.level) * (Lr.cout + 1), tag=f"{Lr.prefix[-40:]} 1->{Lr.cout} k={Lr.kernel}"),
+                                   side=True, late_ok=(k3 == 1), scratch_at=len(head)))
             return True
         if Lr.cout == 1 and Lr.cin in (8, 16, 32, 64) and dy_compact is not None and x.parts is None and x.base is None:
             # (the bias gradient of the C -> 1 convolution = sum of its one-channel dY rides in the same slabs: fixed summation order)
-            self.bwd.append([lib.vsseg_wgrad_narrow, [self._desc(x), dy_compact.ptr, k3, -1, self._gp(Lr.wkey), k3 * k3, self._gp(Lr.bkey) if bias_grad else None, scr.data_ptr(), scr.numel()],
-                             dict(name="wgrad_narrow", kind="hbm", side=True, flops=0.0, bytes=float(es) * self._vox(Lr.level) * (Lr.cin + 1), tag=f"{Lr.prefix[-40:]} {Lr.cin}->1 k={Lr.kernel}")])
+            self.bwd.append(Launch(lib.vsseg_wgrad_narrow, [self._desc(x), dy_compact.ptr, k3, -1, self._gp(Lr.wkey), k3 * k3, self._gp(Lr.bkey) if bias_grad else None, scr.data_ptr(), scr.numel()],
+                                   dict(name="wgrad_narrow", kind="hbm", flops=0.0, bytes=float(es) * self._vox(Lr.level) * (Lr.cin + 1), tag=f"{Lr.prefix[-40:]} {Lr.cin}->1 k={Lr.kernel}"), side=True))
             return True
         return False
 
@@ -1043,7 +1064,6 @@ class Plan:
         # few persistent workgroups with many tiles each: the per-workgroup flush is as large as the weight gradient itself
         scr = eng.wgrad_scratch()
         d.scratch, d.scratch_elems = scr.data_ptr(), scr.numel()
-        self.keep.append(d)
         # H-chunk group: one workgroup multiplies the P tile it fetched with `hgroup` 16-channel chunks of H (P is then read
         # ceil(chunks / hgroup) times instead of once per chunk); the library clamps the request to a divisor of the chunk count
         # that fits registers and LDS.  Heuristic: as large as allowed.
@@ -1082,11 +1102,12 @@ class Plan:
         d.tile = live_tile
         set_blocks(wpc)
         nq = self.n * wg.q[0] * wg.q[1] * wg.q[2]
-        B.append([eng.lib.vsseg_wgrad, [C.byref(d)], dict(own_dy=own_dy, tag=f"{Lr.prefix[-40:]} q={wg.q} taps={len(wg.taps)} cin={Lr.cin} cout={Lr.cout} " + (f"compute chunks/wg={d.hgroup}" if d.march == 2 else f"march tile={tuple(d.tile)}" if d.march else f"tile={wg.tile} blocks={d.persistent_blocks}x{hch} sb={d.single_buffer} hg={d.hgroup} lds={wg.lds}") + tuned,
-                                                          name=(f"cwgrad<bf16,{wg.ntp}>" if d.march == 2 else f"mwgrad<bf16,{wg.ntp}>" if d.march else f"wgrad<{'bf16' if eng.es == 2 else 'f32'},{wg.ntp}>"), kind="mfma", side=True, flops=2.0 * nq * len(wg.taps) * Lr.cin * Lr.cout,
-                                                          bytes=float(eng.es) * (nq * (Lr.cout if not Lr.transposed else Lr.cin) + self._vox(Lr.level if not Lr.transposed else Lr.out_level) * (Lr.cin if not Lr.transposed else Lr.cout)))])
+        meta = dict(tag=f"{Lr.prefix[-40:]} q={wg.q} taps={len(wg.taps)} cin={Lr.cin} cout={Lr.cout} " + (f"compute chunks/wg={d.hgroup}" if d.march == 2 else f"march tile={tuple(d.tile)}" if d.march else f"tile={wg.tile} blocks={d.persistent_blocks}x{hch} sb={d.single_buffer} hg={d.hgroup} lds={wg.lds}") + tuned,
+                    name=(f"cwgrad<bf16,{wg.ntp}>" if d.march == 2 else f"mwgrad<bf16,{wg.ntp}>" if d.march else f"wgrad<{'bf16' if eng.es == 2 else 'f32'},{wg.ntp}>"), kind="mfma", flops=2.0 * nq * len(wg.taps) * Lr.cin * Lr.cout,
+                    bytes=float(eng.es) * (nq * (Lr.cout if not Lr.transposed else Lr.cin) + self._vox(Lr.level if not Lr.transposed else Lr.out_level) * (Lr.cin if not Lr.transposed else Lr.cout)))
+        B.append(Launch(eng.lib.vsseg_wgrad, [C.byref(d)], meta, desc=d, side=True, own_dy=own_dy))
         if bias_grad and Lr.transposed:  # (does not occur in this network: transposed convolutions are followed by BatchNorm)
-            B.append([eng.lib.vsseg_channel_sum, [L.Tensor(dy.ptr, dy.dtype, Lr.cout, dy.pitch, dy.n, dy.x, dy.y, dy.z), self._gp(Lr.bkey)]])
+            B.append(Launch(eng.lib.vsseg_channel_sum, [L.Tensor(dy.ptr, dy.dtype, Lr.cout, dy.pitch, dy.n, dy.x, dy.y, dy.z), self._gp(Lr.bkey)]))
         self._conv_backward_data(Lr, x, dy, relumask, dy_compact, gate)
 
     def _tune_wgrad(self, key: str, d: L.WgradDesc, wg: P.WgradPlan, hgs, tile_kernel: bool, mtiles, cgs, set_blocks):
@@ -1183,7 +1204,6 @@ class Plan:
         d.dw = self._gp(Lr.wkey)
         d.scratch, d.scratch_elems = scr.data_ptr(), scr.numel()
         self._wpack_fixups.append((d, "wpack", ch.map_off))
-        self.keep.append(d)
         res_tag = ""
         if dres is not None:
             rp = P.residual_dgrad_pack_plan(rc.layer.wshape, self.lv[Lr.level])
@@ -1199,9 +1219,9 @@ class Plan:
             tile, tuned = self._tune_fused_backward(key, d, tiles, mp.pack_map.size, bool(res_tag))
         d.tile = L.i3(tile)
         nq = float(self._vox(Lr.level))
-        self.bwd.append([eng.lib.vsseg_conv_bwd_fused, [C.byref(d)], dict(tag=f"{pre[-40:]} q={self.lv[Lr.level]} cin={Lr.cin} cout={Lr.cout} tile={tuple(tile)}{res_tag}{tuned}", name=f"mbwd<bf16,{Lr.cout // 16},{Lr.cin // 16}>", kind="mfma",
-                                                                          flops=2.0 * 2.0 * nq * (10 if res_tag else 9) * Lr.cin * Lr.cout,
-                                                                          bytes=eng.es * nq * ((3 if res_tag.endswith("[unit dA]") else 2) * Lr.cout + 2 * Lr.cin) + nq * Lr.cout / 8)])
+        meta = dict(tag=f"{pre[-40:]} q={self.lv[Lr.level]} cin={Lr.cin} cout={Lr.cout} tile={tuple(tile)}{res_tag}{tuned}", name=f"mbwd<bf16,{Lr.cout // 16},{Lr.cin // 16}>", kind="mfma",
+                    flops=2.0 * 2.0 * nq * (10 if res_tag else 9) * Lr.cin * Lr.cout, bytes=eng.es * nq * ((3 if res_tag.endswith("[unit dA]") else 2) * Lr.cout + 2 * Lr.cin) + nq * Lr.cout / 8)
+        self.bwd.append(Launch(eng.lib.vsseg_conv_bwd_fused, [C.byref(d)], meta, desc=d))
         return True
 
     def _tune_fused_backward(self, key: str, d: L.ConvBwdDesc, tiles, npack: int, res: bool):
@@ -1237,9 +1257,9 @@ class Plan:
             return False
         x1 = self._xdesc(op.x, True)  # the compact one-channel copy of the network input
         scr = self.eng.wgrad_scratch()
-        self.bwd.append([self.eng.lib.vsseg_wgrad_narrow_bn, [yd, dA, b.keep, b.mean, b.invstd, b.gamma, b.scale, b.shift, b.alpha, b.mean_dz, b.mean_dzx,
-                                                              self.p_drop, x1.ptr, self._gp(Lr.wkey), 9, scr.data_ptr(), scr.numel()],
-                         dict(name="wgrad_narrow", kind="hbm", side=True, flops=0.0, bytes=float(self.eng.es) * self._vox(Lr.level) * (2 * Lr.cout + 1) + self._vox(Lr.level) * Lr.cout / 8, tag=f"{pre[-40:]} 1->{Lr.cout} k={Lr.kernel} +bn on load")])
+        self.bwd.append(Launch(self.eng.lib.vsseg_wgrad_narrow_bn, [yd, dA, b.keep, b.mean, b.invstd, b.gamma, b.scale, b.shift, b.alpha, b.mean_dz, b.mean_dzx,
+                                                                    self.p_drop, x1.ptr, self._gp(Lr.wkey), 9, scr.data_ptr(), scr.numel()],
+                               dict(name="wgrad_narrow", kind="hbm", flops=0.0, bytes=float(self.eng.es) * self._vox(Lr.level) * (2 * Lr.cout + 1) + self._vox(Lr.level) * Lr.cout / 8, tag=f"{pre[-40:]} 1->{Lr.cout} k={Lr.kernel} +bn on load"), side=True))
         return True
 
     def _bwd_conv_bn_act(self, op: ConvBnAct):
@@ -1248,13 +1268,13 @@ class Plan:
         seed, written = self.seed_dev.data_ptr(), self._written
         yd = self._tdesc(self.bufs["y:" + pre], Lr.out_level)
         dA = self._grad_of_out(op.out)
-        B.append([lib.vsseg_bn_act_bwd_reduce, [yd, dA, b.mean, b.invstd, b.gamma, b.beta, b.scale, b.shift, b.alpha, self.p_drop, seed, b.salt, b.stats_bwd, b.cpad, b.slope, b.keep],
-                  self._ew_meta("bn_act_bwd_reduce", Lr.out_level, 2 * Lr.cout)])
+        B.append(Launch(lib.vsseg_bn_act_bwd_reduce, [yd, dA, b.mean, b.invstd, b.gamma, b.beta, b.scale, b.shift, b.alpha, self.p_drop, seed, b.salt, b.stats_bwd, b.cpad, b.slope, b.keep],
+                        self._ew_meta("bn_act_bwd_reduce", Lr.out_level, 2 * Lr.cout)))
         pr = eng.prog.producer(op.res) if op.res is not None else None  # residual conv: d(out)/d(res) = 1, its bias gradient is sum(dA) (reduced above)
         if pr is not None:
             self._folded_bias.add(pr.layer.prefix)
-        B.append([lib.vsseg_bn_act_bwd_finalize, [b.stats_bwd, b.cpad, b.slope, Lr.cout, float(self._vox(Lr.out_level)), self._gp(pre + ".norm.weight"), self._gp(pre + ".norm.bias"),
-                                                  self._gp(pre + ".act.weight"), b.mean_dz, b.mean_dzx, self._gp(pr.layer.bkey) if pr is not None else None]])
+        B.append(Launch(lib.vsseg_bn_act_bwd_finalize, [b.stats_bwd, b.cpad, b.slope, Lr.cout, float(self._vox(Lr.out_level)), self._gp(pre + ".norm.weight"), self._gp(pre + ".norm.bias"),
+                                                        self._gp(pre + ".act.weight"), b.mean_dz, b.mean_dzx, self._gp(pr.layer.bkey) if pr is not None else None]))
         if pr is not None and eng.early_res_wgrad == "1":
             # The 1x1x1 residual convolution of the network input (first ResidualUnit): its weight gradient needs d(out) of the unit only — which exists from here on — but in list
             # order it came LAST, behind the unit's first block, where nothing else is left to run beside it (0.13 ms at the end of the step with the main stream idle,
@@ -1265,8 +1285,8 @@ class Plan:
         fused = (op.res is None or op.res.name.endswith(":res")) and (self._fused_backward(op, yd, dA) or self._fused_narrow(op, yd, dA))  # (an identity residual re-uses dA's buffer below: keep those unfused)
         if not fused:
             dyd = self._tdesc(self._raw("dy:" + pre, Lr.out_level, Lr.cout), Lr.out_level)
-            B.append([lib.vsseg_bn_act_bwd_apply, [yd, dA, b.mean, b.invstd, b.gamma, b.beta, b.scale, b.shift, b.alpha, self.p_drop, seed, b.salt, b.mean_dz, b.mean_dzx, dyd, b.keep],
-                      self._ew_meta("bn_act_bwd_apply", Lr.out_level, 3 * Lr.cout)])
+            B.append(Launch(lib.vsseg_bn_act_bwd_apply, [yd, dA, b.mean, b.invstd, b.gamma, b.beta, b.scale, b.shift, b.alpha, self.p_drop, seed, b.salt, b.mean_dz, b.mean_dzx, dyd, b.keep],
+                            self._ew_meta("bn_act_bwd_apply", Lr.out_level, 3 * Lr.cout)))
         if op.res is not None and not op.res.name.endswith(":res"):  # identity residual: d(res) += d(out)
             r, o = op.res, self._grad_alias.get(op.out.name, op.out)
             if (r.parts is None and r.base is None and o.parts is None and o.base is None and r.kind == o.kind == "act" and (r.level, r.c) == (o.level, o.c)
@@ -1276,9 +1296,9 @@ class Plan:
                 self.grads[r.name] = self.grads[o.name]
                 written[r.name] = True
             elif self._contribution(op.res):
-                B.append([lib.vsseg_add_inplace, [self._desc(op.res, self.grads), dA], self._ew_meta("grad_add/copy", Lr.out_level, 3 * Lr.cout)])
+                B.append(Launch(lib.vsseg_add_inplace, [self._desc(op.res, self.grads), dA], self._ew_meta("grad_add/copy", Lr.out_level, 3 * Lr.cout)))
             else:
-                B.append([lib.vsseg_copy_cast, [dA, self._desc(op.res, self.grads)], self._ew_meta("grad_add/copy", Lr.out_level, 2 * Lr.cout)])
+                B.append(Launch(lib.vsseg_copy_cast, [dA, self._desc(op.res, self.grads)], self._ew_meta("grad_add/copy", Lr.out_level, 2 * Lr.cout)))
         if not fused:
             self._conv_backward(Lr, op.x, dyd, bias_grad=False, own_dy=True)  # a bias in front of a training-mode BatchNorm has zero gradient
 
@@ -1288,7 +1308,8 @@ class Plan:
             big = self.merged[Lr.prefix].layer
             kx, ky, kz = big.kernel
             centre = ((kx // 2) * ky + ky // 2) * kz + kz // 2
-            self.bwd.append([self.eng.lib.vsseg_merge_residual_grads, [self._gp(big.wkey), self._gp(big.bkey), self._gp(Lr.wkey), self._gp(Lr.bkey), Lr.cout, Lr.cin, kx * ky * kz, centre], dict(name="vsseg_merge_residual_grads", kind="hbm", flops=0.0, bytes=0.0, side=True)])
+            self.bwd.append(Launch(self.eng.lib.vsseg_merge_residual_grads, [self._gp(big.wkey), self._gp(big.bkey), self._gp(Lr.wkey), self._gp(Lr.bkey), Lr.cout, Lr.cin, kx * ky * kz, centre],
+                                   dict(name="vsseg_merge_residual_grads", kind="hbm", flops=0.0, bytes=0.0), side=True))
             return
         if Lr.prefix in self._early_res:  # issued with the unit's last block (_bwd_conv_bn_act)
             return
@@ -1326,8 +1347,8 @@ class Plan:
                        and self._compact_choice(cps.dgrad[0], sig) is not None)
         dpre = None if all_compact else self._raw("dpre:" + op.att.name, op.att.level, 16 if sig.prefix in self.wide_dpre else 8)  # (channels 8..15 of the wide rows are never written: zero)
         gbuf = self.gatt_buf[op.att.name] = torch.zeros((self.n, *self.lv[op.att.level]), dtype=torch.float32, device=dev)  # the loss' gradient of this attention map is staged here
-        self.bwd.append([self.eng.lib.vsseg_att_apply_bwd, [self._desc(op.x), self._alloc(op.att, self.bufs).data_ptr(), gout, gbuf.data_ptr(), self._desc(op.x, self.grads), acc, self._dpre_desc(dpre, op.att.level) if dpre is not None else L.Tensor(), None, dpre1],
-                         self._ew_meta("att_apply_bwd", op.x.level, (2 if acc == 2 else (4 if acc else 3)) * op.x.c + (8 if dpre is not None else 1) + 4)])
+        self.bwd.append(Launch(self.eng.lib.vsseg_att_apply_bwd, [self._desc(op.x), self._alloc(op.att, self.bufs).data_ptr(), gout, gbuf.data_ptr(), self._desc(op.x, self.grads), acc, self._dpre_desc(dpre, op.att.level) if dpre is not None else L.Tensor(), None, dpre1],
+                               self._ew_meta("att_apply_bwd", op.x.level, (2 if acc == 2 else (4 if acc else 3)) * op.x.c + (8 if dpre is not None else 1) + 4)))
 
     def _move_late_wgrads(self):
         """The LAST weight-gradient launches of the list leave the side stream for the END of the main stream's list: the step ends with the first block's chain
@@ -1337,26 +1358,26 @@ class Plan:
         eng, lib, B = self.eng, self.eng.lib, self.bwd
         if eng.late_wgrad <= 0:
             return
-        late = [i for i, rec in enumerate(B) if len(rec) > 2 and rec[2].get("side") and rec[2].get("own_dy") and rec[0] is lib.vsseg_wgrad][-eng.late_wgrad:]
+        late = [la for la in B if la.side and la.own_dy and la.fn is lib.vsseg_wgrad][-eng.late_wgrad:]
         if eng.early_res_wgrad == "late":  # + the first unit's 1x1x1 residual-convolution weight gradient (the last launch of the side stream's list)
-            late += [i for i, rec in enumerate(B) if len(rec) > 2 and rec[2].get("late_ok") and rec[0] is lib.vsseg_wgrad_narrow]
+            late += [la for la in B if la.late_ok and la.fn is lib.vsseg_wgrad_narrow]
         fs = eng.fused_scratch()
-        for rec in (B[i] for i in late):
-            if rec[0] is lib.vsseg_wgrad:
-                rec[1][0]._obj.scratch, rec[1][0]._obj.scratch_elems = fs.data_ptr(), fs.numel()
+        for la in late:
+            if la.fn is lib.vsseg_wgrad:
+                la.desc.scratch, la.desc.scratch_elems = fs.data_ptr(), fs.numel()
             else:
-                rec[1][7], rec[1][8] = fs.data_ptr(), fs.numel()
-            rec[2] = dict(rec[2], side=False, late=True)
-        B[:] = [r for j, r in enumerate(B) if j not in late] + [B[i] for i in late]
+                la.args[la.scratch_at:la.scratch_at + 2] = [fs.data_ptr(), fs.numel()]
+            la.side, la.late = False, True
+        B[:] = [la for la in B if not la.late] + late
 
     def _index_slots(self):
         self.ext_slots = []
         for lst in (self.fwd, self.bwd, self.bwd_pre):
-            for rec in lst:
-                for i, a in enumerate(rec[1]):
+            for launch in lst:
+                for i, a in enumerate(launch.args):
                     if isinstance(a, _Slot):
                         assert lst is self.bwd_pre, "a captured launch list may not depend on caller-owned memory"
-                        self.ext_slots.append((rec[1], i, a))
+                        self.ext_slots.append((launch.args, i, a))
 
     # ------------------------------------------------------------------ run
     def set_seed(self, seed: int, stream=None):
@@ -1408,13 +1429,14 @@ class Plan:
         L.check(self.eng.lib.vsseg_gather_cast(self.eng.flat.data_ptr(), self.pack_map.data_ptr(), m2, self.wpack.data_ptr(), self.pack_map.numel(), L.BF16 if self.eng.es == 2 else L.F32, stream), "gather_cast")
 
     def run(self, lst, stream, graph_key: Optional[str] = None):
-        tm = self.timer
-        if tm is not None and tm["only"] is None:  # the per-kernel profile: every launch between two events, each kernel alone on the GPU
-            return self._run_timed(lst, stream)
+        tm, timed = self.timer, None
+        if tm is not None and tm["only"] is None:  # the per-kernel profile: every launch between two events
+            timed = "all"
         # tm with a set of names (bench.py's timed region: the dominant kernel's launches measured live): the product's schedule — hipGraph replay of the lists that hold none
         # of those launches, bound forks in the eager ones — with two events around the named launches only
-        timed_here = tm is not None and tm.get("active", True) and any(_rec_name(r) in tm["only"] for r in lst)
-        if graph_key is not None and self.eng.use_graphs and not timed_here and not (self.eng.overlap and any(len(r) > 2 and r[2].get("side") for r in lst)):
+        elif tm is not None and tm.get("active", True) and any(la.name in tm["only"] for la in lst):
+            timed = tm["only"]
+        if graph_key is not None and self.eng.use_graphs and timed is None and not (self.eng.overlap and any(la.side for la in lst)):
             g = self._graphs.get(graph_key)
             if g is not None:
                 g.replay()
@@ -1439,25 +1461,30 @@ class Plan:
                         raise RuntimeError(f"vs_seg_amd: hipGraph capture of the {graph_key} launch list failed ({e}) and left the stream capturing") from e
                     warnings.warn(f"vs_seg_amd: hipGraph capture of the {graph_key} launch list failed ({e}); launching eagerly")
                     self.eng.use_graphs = False
-        self._run_eager(lst, stream, tm if timed_here else None)
+        self._run_eager(lst, stream, timed)
 
-    def _run_eager(self, lst, stream, tm=None):
-        """Launches in list order on `stream` (torch's current stream).  With Engine.overlap, the launches marked side=True — the weight
+    def _run_eager(self, lst, stream, timed=None):
+        """Launches in list order on `stream` (torch's current stream).  With Engine.overlap, the launches with Launch.side — the weight
         gradients, which nothing in the backward pass reads (they feed the optimizer) — go to a second HIP stream: each forks from the main
         stream where the list places it (its operands are final there; every gradient tensor has its own buffer, so nothing later on the
         main stream overwrites them), they serialise among themselves (shared partial-sum scratch), and the main stream joins the side
-        stream at the end of the list.  Under hipGraph capture the fork / join events become graph edges."""
+        stream at the end of the list.  Under hipGraph capture the fork / join events become graph edges.
+        `timed`: None, or the names of the launches that run between two HIP events (recorded on the stream the launch goes to, appended to
+        Plan.timer's events), or "all"."""
         side = None
-        overlap = self.eng.overlap
+        every = timed == "all"
+        # "all" is the per-kernel profile: it wants each kernel alone on the GPU, not sharing it with a concurrent weight gradient — no side stream, no fork
+        overlap = self.eng.overlap and not every
         lib = self.eng.lib
         # A fork = the side stream waits for the main-stream launch in front of it.  With Engine.bound_forks that launch's kernels carry the fork's event as the stop event of
         # their own dispatch (vsseg_fork_arm: no marker packet on the main stream, whose next kernel a hipEventRecord delays by 5-8 us, 42 times per step: DESIGN 3.18)
         bound = overlap and self.eng.bound_forks and not torch.cuda.is_current_stream_capturing()
-        is_side = [overlap and len(rec) > 2 and bool(rec[2].get("side")) for rec in lst]
+        is_side = [overlap and la.side for la in lst]
         events = self._fork_events if bound else None
-        nfork, ready = 0, None  # ready: the event the launch in front of the next side launch carried
-        for i, rec in enumerate(lst):
-            if is_side[i]:
+        nfork, ready, n = 0, None, len(lst)  # ready: the event the launch in front of the next side launch carried
+        for i, la in enumerate(lst):
+            on_side = is_side[i]
+            if on_side:
                 if side is None:
                     side = self.eng.side_stream()
                 if ready is not None:
@@ -1465,75 +1492,33 @@ class Plan:
                 elif i == 0 or not is_side[i - 1]:  # (consecutive side launches share the fork of the first)
                     side.wait_stream(torch.cuda.current_stream())
                 ready = None
-                timed = tm is not None and _rec_name(rec) in tm["only"]
-                if timed:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record(side)
-                rc = rec[0](*rec[1], side.cuda_stream)
-                if timed:
-                    e1.record(side)
-                    tm["events"].append((_rec_name(rec), rec[2], e0, e1))
-            else:
-                timed = tm is not None and _rec_name(rec) in tm["only"]
-                if timed:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                arm = bound and i + 1 < len(lst) and is_side[i + 1]
-                if arm:
-                    if nfork == len(events):
-                        events.append(lib.vsseg_fork_event_create())
-                    ev = events[nfork]
-                    nfork += 1
-                    L.check(lib.vsseg_fork_arm(ev), "fork_arm")
-                try:
-                    rc = rec[0](*rec[1], stream)
-                finally:
-                    if arm:
-                        ready = ev if lib.vsseg_fork_disarm() > 0 else None  # 0: the record launched no kernel of the library (a memset): plain fork
-                if timed:
-                    e1.record()
-                    tm["events"].append((_rec_name(rec), rec[2] if len(rec) > 2 else None, e0, e1))
-            if rc:
-                L.check(rc, getattr(rec[0], "__name__", "launch"))
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side)
-
-    def _run_timed(self, lst, stream):
-        """Per-launch HIP-event timing (events are recorded on the stream the kernels are launched on).  With Engine.overlap the side
-        launches go to the second stream exactly as in _run_eager — unless EVERY launch is timed (tm['only'] is None: the per-kernel profile
-        wants each kernel alone on the GPU, not sharing it with a concurrent weight gradient)."""
-        tm = self.timer
-        overlap = self.eng.overlap and tm["only"] is not None
-        side = None
-        for rec in lst:
-            name = rec[2]["name"] if len(rec) > 2 else getattr(rec[0], "__name__", "memset")
-            on_side = overlap and len(rec) > 2 and rec[2].get("side")
-            if on_side:
-                if side is None:
-                    side = self.eng.side_stream()
-                side.wait_stream(torch.cuda.current_stream())
-            s_obj = side if on_side else None
-            s_raw = side.cuda_stream if on_side else stream
-            if tm["only"] is not None and name not in tm["only"]:
-                rc = rec[0](*rec[1], s_raw)
-            else:
+            e0 = None
+            if timed is not None and (every or la.name in timed):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(s_obj) if s_obj is not None else e0.record()
-                rc = rec[0](*rec[1], s_raw)
-                e1.record(s_obj) if s_obj is not None else e1.record()
-                tm["events"].append((name, rec[2] if len(rec) > 2 else None, e0, e1))
+                e0.record(side if on_side else None)  # (None: the current stream)
+            arm = bound and not on_side and i + 1 < n and is_side[i + 1]
+            if arm:
+                if nfork == len(events):
+                    events.append(lib.vsseg_fork_event_create())
+                fork = events[nfork]
+                nfork += 1
+                L.check(lib.vsseg_fork_arm(fork), "fork_arm")
+            try:
+                rc = la.fn(*la.args, side.cuda_stream if on_side else stream)
+            finally:
+                if arm:
+                    ready = fork if lib.vsseg_fork_disarm() > 0 else None  # 0: the record launched no kernel of the library (a memset): plain fork
+            if e0 is not None:
+                e1.record(side if on_side else None)
+                self.timer["events"].append((la.name, la.meta, e0, e1))
             if rc:
-                L.check(rc, name)
+                L.check(rc, la.name)
         if side is not None:
             torch.cuda.current_stream().wait_stream(side)
 
     def memory_bytes(self) -> int:
         tot = sum(t.numel() * t.element_size() for t in self.bufs.values()) + sum(t.numel() * t.element_size() for t in self.grads.values())
         return tot + self.wpack.numel() * self.wpack.element_size() + self.pack_map.numel() * 4
-
-
-def _rec_name(rec) -> str:
-    return rec[2]["name"] if len(rec) > 2 and "name" in rec[2] else getattr(rec[0], "__name__", "memset")
 
 
 class Engine:
