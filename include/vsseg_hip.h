@@ -235,7 +235,7 @@ int vsseg_fork_event_destroy(void* ev);
 int vsseg_fork_arm(void* ev);
 int vsseg_fork_disarm(void);
 int vsseg_stream_wait_event(void* stream, void* ev);
-int vsseg_version(void); /* 14: + vsseg_ce_sums, vsseg_dice_ce_finalize, vsseg_dice_ce_pred_bwd, vsseg_dice_ce_pred_bwd_to; 13: + vsseg_patch_filter, vsseg_patch_tone; 12: + vsseg_crop_field, vsseg_field_job; 11: + vsseg_crop_affine, vsseg_affine_job; 10: + vsseg_swi_finalize_mirrored, vsseg_crop_job.flip is a three-axis mirror mask (was flip_x); 9: + vsseg_components_scratch_bytes, vsseg_components_label, vsseg_keep_largest_component; 8: + vsseg_surface_distances, vsseg_surface_scratch_bytes; 7: + vsseg_dice_pred_bwd_to, vsseg_dice_level_sums, vsseg_dice_tail_sums, vsseg_dice_att_bwd_levels, vsseg_fork_*, vsseg_stream_wait_event; 6: + launch plans with depth -8 (transition kernel) and -9 (gathering marching kernel); 5: vsseg_wgrad march = 2 (compute weight-gradient kernel), + vsseg_conv_to1, vsseg_conv_chain_desc without h_out (the training variant measured no gain and was deleted); 4: + vsseg_conv_chain; 3: the BatchNorm-block-on-load fields (in_bn_*, keep_*, x_bn_*: round-4 experiment, measured a loss, deleted) left the descriptors, depth -7 plans;
+int vsseg_version(void); /* 15: + vsseg_grad_norm_scratch_bytes, vsseg_grad_norm, vsseg_sgd, vsseg_adam_clipped, vsseg_clip_record; 14: + vsseg_ce_sums, vsseg_dice_ce_finalize, vsseg_dice_ce_pred_bwd, vsseg_dice_ce_pred_bwd_to; 13: + vsseg_patch_filter, vsseg_patch_tone; 12: + vsseg_crop_field, vsseg_field_job; 11: + vsseg_crop_affine, vsseg_affine_job; 10: + vsseg_swi_finalize_mirrored, vsseg_crop_job.flip is a three-axis mirror mask (was flip_x); 9: + vsseg_components_scratch_bytes, vsseg_components_label, vsseg_keep_largest_component; 8: + vsseg_surface_distances, vsseg_surface_scratch_bytes; 7: + vsseg_dice_pred_bwd_to, vsseg_dice_level_sums, vsseg_dice_tail_sums, vsseg_dice_att_bwd_levels, vsseg_fork_*, vsseg_stream_wait_event; 6: + launch plans with depth -8 (transition kernel) and -9 (gathering marching kernel); 5: vsseg_wgrad march = 2 (compute weight-gradient kernel), + vsseg_conv_to1, vsseg_conv_chain_desc without h_out (the training variant measured no gain and was deleted); 4: + vsseg_conv_chain; 3: the BatchNorm-block-on-load fields (in_bn_*, keep_*, x_bn_*: round-4 experiment, measured a loss, deleted) left the descriptors, depth -7 plans;
                             * 2: fixed-point accumulators documented + vsseg_fx_status; 1: the buffers below were described as plain doubles */
 
 /* ---- Accumulator buffers are 64-bit FIXED-POINT integers, not doubles ------------------------------------------------------------------
@@ -418,6 +418,39 @@ int vsseg_dice_ce_pred_bwd_to(const float* logits, int32_t pitch, const float* l
 
 /* torch.optim.Adam(lr, weight_decay) over the flat parameter buffer (ref:params/VSparams.py:388-391,462). */
 int vsseg_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float wd, float bc1, float bc2, float gscale, void* stream);
+
+/* ---- gradient-norm clipping, SGD and AdamW over the same flat buffers (ABI version 15; beyond the reference, whose only optimiser is the Adam above) --------------
+ * The clip record: 64 bytes of device memory, 8-byte aligned, owned and zeroed by the caller (zeroing it again resets the statistics).  vsseg_grad_norm writes it, the
+ * update kernels read it, the host reads it only when it wants the statistics — nothing on the step path waits for the norm. */
+typedef struct {
+  double norm;      /*  0: L2 norm of gscale * g of the last vsseg_grad_norm call (NaN / Inf when the gradient held one) */
+  float coef;       /*  8: min(1, max_norm / (norm + 1e-6)), formed in fp64 and rounded once (torch.nn.utils.clip_grad_norm_); 0 when skip is set */
+  int32_t skip;     /* 12: 1 when the norm is NaN or Inf: the update kernels then leave parameters and optimiser state bitwise untouched */
+  int64_t steps;    /* 16: calls since the record was zeroed */
+  int64_t clipped;  /* 24: of them with a finite norm and coef < 1 */
+  int64_t skipped;  /* 32: of them with skip = 1 */
+  double norm_sum;  /* 40: sum of the finite norms */
+  double norm_max;  /* 48: largest finite norm */
+  int64_t reserved; /* 56 */
+} vsseg_clip_record;
+#define VSSEG_GRAD_NORM_SHARD 8192 /* elements per partial sum (one workgroup pass) */
+#define VSSEG_GRAD_NORM_FINAL 256  /* partials the finalising workgroup consumes per pass */
+/* vsseg_grad_norm — norm = |gscale| * sqrt(sum g[i]^2) over n elements, every square and every addition in fp64 (an fp32 square of 1e-30 is 0, of 1e25 is Inf).  Stage 1:
+ *   partial s = the sum over the elements [s * SHARD, (s + 1) * SHARD) in a fixed in-workgroup order, stored to scratch[s].  Stage 2: one workgroup adds the partials
+ *   (thread t: t, t + FINAL, ... in that order, then a fixed tree) and writes the record.  No atomics, no dependence on the grid: the same gradient gives the same bits on
+ *   every run and every rank.  scratch: vsseg_grad_norm_scratch_bytes(n) bytes, 8-byte aligned, overwritten.  n == 0: norm 0, coef 1.  g may be null only then.
+ *   VSSEG_EINVAL (before any launch): null / misaligned pointers, n < 0, max_norm not finite or <= 0, gscale not finite, too little scratch.
+ * vsseg_sgd — torch.optim.SGD(lr, momentum, dampening 0, weight_decay, nesterov): g' = coef * gscale * g + wd * p; buf = momentum * buf + g' (a zeroed buf reproduces torch's
+ *   first step); d = nesterov ? g' + momentum * buf : buf; p -= lr * d.  momentum == 0: d = g', buf is not touched and may be null.  VSSEG_EINVAL: null pointers, n < 0,
+ *   momentum outside [0, 1), nesterov with momentum 0.
+ * vsseg_adam_clipped — vsseg_adam with the gradient multiplied by coef; decoupled != 0: torch.optim.AdamW (p *= 1 - lr * wd first, no wd * p in the gradient).  With
+ *   record == NULL and decoupled == 0 it IS vsseg_adam (same launch, same bits).
+ * Both updates: record may be NULL (coef 1, never skipped); with record->skip set they return before their first store.  n == 0: no launch. */
+int64_t vsseg_grad_norm_scratch_bytes(int64_t n); /* bytes of scratch, or VSSEG_EINVAL */
+int vsseg_grad_norm(const float* g, int64_t n, float gscale, double max_norm, double* scratch, int64_t scratch_bytes, vsseg_clip_record* record, void* stream);
+int vsseg_sgd(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float wd, int32_t nesterov, float gscale, const vsseg_clip_record* record, void* stream);
+int vsseg_adam_clipped(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float wd, float bc1, float bc2, float gscale, int32_t decoupled,
+                       const vsseg_clip_record* record, void* stream);
 
 /* ---- data side: the reference's MONAI transform chain on volumes cached in HBM -------------------- */
 /* One crop of one cached volume: RandFlipd(spatial_axis=0) then RandSpatialCropd / SpatialPadd's zero padding

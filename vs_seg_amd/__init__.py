@@ -1,6 +1,6 @@
 """vs_seg_amd — MI355X-native (gfx950) hot path of KCL-BMEIS/VS_Seg behind the reference's own Python interfaces.
 
-    from vs_seg_amd import UNet2d5_spvPA, Dice_spvPA, sliding_window_inference, Adam
+    from vs_seg_amd import UNet2d5_spvPA, Dice_spvPA, sliding_window_inference, Adam, AdamW, SGD
 
 `UNet2d5_spvPA` / `Dice_spvPA` mirror ref:params/networks/nets/unet2d5_spvPA.py and ref:params/losses/dice_spvPA.py;
 `sliding_window_inference` mirrors the MONAI 0.4.0 function called at ref:params/VSparams.py:568-574.  All compute is
@@ -11,7 +11,7 @@ from .inferers import compute_dice_score, sliding_window_inference  # noqa: F401
 from .losses.dice_spvPA import Dice_spvPA, check_ce  # noqa: F401
 from .metrics import compute_surface_distances, voxel_spacing  # noqa: F401
 from .networks.nets.unet2d5_spvPA import UNet2d5_spvPA  # noqa: F401
-from .optim import Adam  # noqa: F401
+from .optim import SGD, Adam, AdamW, check_optimizer, poly_lr  # noqa: F401
 from .postprocess import connected_components, keep_largest_component  # noqa: F401
 
-__all__ = ["UNet2d5_spvPA", "Dice_spvPA", "check_ce", "sliding_window_inference", "compute_dice_score", "compute_surface_distances", "voxel_spacing", "connected_components", "keep_largest_component", "Adam", "fx_status", "VssegError"]
+__all__ = ["UNet2d5_spvPA", "Dice_spvPA", "check_ce", "sliding_window_inference", "compute_dice_score", "compute_surface_distances", "voxel_spacing", "connected_components", "keep_largest_component", "Adam", "AdamW", "SGD", "check_optimizer", "poly_lr", "fx_status", "VssegError"]

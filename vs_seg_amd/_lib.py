@@ -58,6 +58,13 @@ class ToneJob(C.Structure):  # vsseg_tone_job
     _fields_ = [("contrast", C.c_float), ("gamma", C.c_float)]  # 1, 1: the job is left untouched
 
 
+GRAD_NORM_SHARD, GRAD_NORM_FINAL = 8192, 256  # VSSEG_GRAD_NORM_SHARD / _FINAL: elements per partial of vsseg_grad_norm, partials per pass of its finalising workgroup
+
+
+class ClipRecord(C.Structure):  # vsseg_clip_record: 64 bytes of device memory written by vsseg_grad_norm
+    _fields_ = [("norm", C.c_double), ("coef", C.c_float), ("skip", C.c_int32), ("steps", C.c_int64), ("clipped", C.c_int64), ("skipped", C.c_int64), ("norm_sum", C.c_double), ("norm_max", C.c_double), ("reserved", C.c_int64)]
+
+
 TONE_SHARDS = 128  # VSSEG_TONE_SHARDS: vsseg_patch_tone's `work` is njobs * TONE_SHARDS * 3 doubles
 
 
@@ -231,6 +238,7 @@ SYMBOLS = [
     "vsseg_adam", "vsseg_swi_accumulate", "vsseg_swi_finalize", "vsseg_swi_finalize_mirrored", "vsseg_hard_dice_counts", "vsseg_argmax2",
     "vsseg_surface_scratch_bytes", "vsseg_surface_distances",
     "vsseg_components_scratch_bytes", "vsseg_components_label", "vsseg_keep_largest_component",
+    "vsseg_grad_norm_scratch_bytes", "vsseg_grad_norm", "vsseg_sgd", "vsseg_adam_clipped",
 ]  # fmt: skip
 
 _lib = None
@@ -315,6 +323,10 @@ def lib():
         L.vsseg_components_scratch_bytes.argtypes, L.vsseg_components_scratch_bytes.restype = [I3], i64
         L.vsseg_components_label.argtypes = [vp, i32, I3, i32, vp, i64, vp, vp, vp]
         L.vsseg_keep_largest_component.argtypes = [vp, i32, I3, i32, vp, i64, vp, vp, vp]
+        L.vsseg_grad_norm_scratch_bytes.argtypes, L.vsseg_grad_norm_scratch_bytes.restype = [i64], i64
+        L.vsseg_grad_norm.argtypes = [vp, i64, f32, f64, vp, i64, vp, vp]
+        L.vsseg_sgd.argtypes = [vp, vp, vp, i64, f32, f32, f32, i32, f32, vp, vp]
+        L.vsseg_adam_clipped.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, f32, i32, vp, vp]
         _lib = L
     return _lib
 

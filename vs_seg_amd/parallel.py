@@ -4,8 +4,8 @@ The reference is single-device (`"cuda:0"`, ref:params/VSparams.py:83); the sema
 
 * training — pure data parallel.  Every rank steps on its own shard of the shuffled index list; ONE collective per step:
   all-reduce(sum) of the flat 3.45 M-element fp32 gradient buffer (13.8 MB, a single bucket — xGMI links are
-  point-to-point, so one large transfer per step beats 178 per-tensor ones), folded into a mean by the fused Adam kernel
-  (`grad_scale = 1/world`).  BatchNorm uses per-rank batch statistics (PyTorch-DDP default); running statistics and
+  point-to-point, so one large transfer per step beats 178 per-tensor ones), folded into a mean by the fused optimiser kernel
+  (`grad_scale = 1/world`: Adam, AdamW and SGD of `vs_seg_amd.optim`; with `max_grad_norm` the norm is taken after the all-reduce, of the mean).  BatchNorm uses per-rank batch statistics (PyTorch-DDP default); running statistics and
   checkpoints come from rank 0.
 * inference — cases are sharded round-robin over ranks (`shard_indices`), Dice scalars all-gathered at the end; for a
   single volume the windows are sharded (`sharded_sliding_window_inference`): window i -> rank i mod W, window logits
@@ -125,7 +125,7 @@ def broadcast_buffers(model, src: int = 0):
 
 
 def allreduce_gradients(gflat: torch.Tensor, async_op: bool = False):
-    """Sum the flat gradient buffer over ranks (single bucket).  The mean is applied by Adam's `grad_scale`."""
+    """Sum the flat gradient buffer over ranks (single bucket).  The mean is applied by the fused optimiser's `grad_scale`."""
     if _collectives_on():
         return _all_reduce_sum(gflat, async_op)
     return None
@@ -237,7 +237,7 @@ def sharded_sliding_window_inference(inputs: torch.Tensor, roi_size, predictor: 
 
 
 class DataParallelTrainer:
-    """fwd + loss + bwd + gradient all-reduce + fused Adam for one rank (the train step of ref:params/VSparams.py:454-463 under DP)."""
+    """fwd + loss + bwd + gradient all-reduce + fused optimiser step (Adam, AdamW or SGD of `vs_seg_amd.optim`) for one rank (the train step of ref:params/VSparams.py:454-463 under DP)."""
 
     def __init__(self, model, loss_fn, optimizer):
         self.model, self.loss_fn, self.opt = model, loss_fn, optimizer
@@ -248,7 +248,7 @@ class DataParallelTrainer:
         # VSSEG_FUSED_LOSS=0: the autograd route (loss.backward() through fp32 gradient tensors), for A/B measurements
         self.fused_loss = hasattr(model, "train_forward_landing") and hasattr(loss_fn, "forward_backward_into") and os.environ.get("VSSEG_FUSED_LOSS", "1") != "0"
         if self.fused_mean:
-            optimizer.grad_scale = 1.0 / self.world  # the fused Adam kernel multiplies the summed gradient by 1/world
+            optimizer.grad_scale = 1.0 / self.world  # the fused update kernel multiplies the summed gradient by 1/world
         if self.world > 1 and hasattr(model, "decorrelate_dropout"):
             model.decorrelate_dropout(get_rank())  # every rank seeds torch identically (VS_train.py): give each its own keep-masks
 

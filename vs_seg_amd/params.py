@@ -26,7 +26,8 @@ from typing import Dict, Iterator, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import Adam, Dice_spvPA, UNet2d5_spvPA, check_ce, compute_dice_score, sliding_window_inference
+from . import SGD, Adam, AdamW, Dice_spvPA, UNet2d5_spvPA, check_ce, check_optimizer, compute_dice_score, poly_lr, sliding_window_inference
+from .optim import DEFAULT_WEIGHT_DECAY, LR_SCHEDULES, OPTIMIZERS
 from .inferers import argmax_segmentation, tta_masks
 from .metrics import compute_surface_distances, voxel_spacing
 from .postprocess import keep_largest_component
@@ -113,9 +114,17 @@ class VSparams:
         parser.add_argument("--aug_appearance_prob", type=float, default=0.25, metavar="P", help="probability with which each of the blur, low-resolution, contrast and gamma augmentations is applied to a training sample, independently of the others")
         parser.add_argument("--ce_weight", type=float, default=0.0, metavar="LAMBDA", help="training loss: add LAMBDA times the voxel-wise cross-entropy of the final logits to the Dice loss (the Dice + CE loss of nnU-Net, MONAI's DiceCELoss; 0: off, the reference's loss)")
         parser.add_argument("--ce_foreground_weight", type=float, default=1.0, metavar="W", help="class weight of the foreground voxels in the cross-entropy term, the background's being 1 (needs --ce_weight > 0)")
+        parser.add_argument("--optimizer", type=str, default="adam", choices=list(OPTIMIZERS), help="adam: the reference's Adam with coupled weight decay; adamw: decoupled weight decay (torch.optim.AdamW); sgd: SGD with --momentum / --nesterov (nnU-Net: --optimizer sgd --nesterov --weight_decay 3e-5 --clip_grad_norm 12 --lr_schedule poly --initial_learning_rate 1e-2)")
+        parser.add_argument("--momentum", type=float, default=None, metavar="MU", help="momentum of --optimizer sgd, in [0, 1) (default 0.99; sgd only)")
+        parser.add_argument("--nesterov", action="store_true", help="Nesterov momentum (--optimizer sgd only)")
+        parser.add_argument("--weight_decay", type=float, default=DEFAULT_WEIGHT_DECAY, metavar="WD", help="weight decay of the optimizer (1e-7: the reference's)")
+        parser.add_argument("--clip_grad_norm", type=float, default=0.0, metavar="NORM", help="clip the L2 norm of the whole gradient to NORM inside the optimizer step, on the GPU (torch.nn.utils.clip_grad_norm_; a step whose norm is NaN / Inf is skipped; 0: off)")
+        parser.add_argument("--lr_schedule", type=str, default="halving", choices=list(LR_SCHEDULES), help="halving: the reference's division by 2 every 100 epochs; poly: lr = initial_learning_rate * (1 - epoch / num_epochs) ** poly_power, set at the start of every epoch")
+        parser.add_argument("--poly_power", type=float, default=None, metavar="P", help="exponent of --lr_schedule poly (default 0.9)")
         args = parser.parse_args(argv)
         try:
             tta_masks(args.tta_flips, args.tta_average)
+            opt = check_optimizer(args.optimizer, args.momentum, args.nesterov, args.weight_decay, args.clip_grad_norm, args.lr_schedule, args.poly_power)
             ce_weight, ce_foreground_weight = check_ce(args.ce_weight, args.ce_foreground_weight)
             augment = check_augment(*(getattr(args, "aug_" + k) for k in AUGMENT_KEYS))
             field = check_field_augment(args.aug_elastic_mag, args.aug_bias_field, args.aug_field_spacing)
@@ -133,7 +142,9 @@ class VSparams:
         self.initial_learning_rate = args.initial_learning_rate
         self.epochs_with_const_lr = 3 if self.debug else 100
         self.lr_divisor = 2.0
-        self.weight_decay = 1e-7
+        self.weight_decay = opt["weight_decay"]
+        self.optimizer, self.momentum, self.nesterov, self.clip_grad_norm = opt["optimizer"], opt["momentum"], opt["nesterov"], opt["clip_grad_norm"]
+        self.lr_schedule, self.poly_power = opt["lr_schedule"], opt["poly_power"]
         self.num_epochs = args.num_epochs or (10 if self.debug else 300)
         self.val_interval = 2
         self.model = "UNet2d5_spvPA"
@@ -185,7 +196,9 @@ class VSparams:
                       ("keep_largest_component", "component_connectivity") if self.keep_largest_component else ()) + (("tta_flips", "tta_average") if self.tta_flips else ()) + (
                           tuple("aug_" + k for k in AUGMENT_KEYS) if any(self.augment.values()) else ()) + (
                               ("aug_elastic_mag", "aug_bias_field", "aug_field_spacing") if self.aug_elastic_mag or self.aug_bias_field else ()) + (
-                                  tuple("aug_" + k for k in APPEARANCE_KEYS) if self._appearance_on else ()) + (("ce_weight", "ce_foreground_weight") if self.ce_weight > 0 else ()):
+                                  tuple("aug_" + k for k in APPEARANCE_KEYS) if self._appearance_on else ()) + (("ce_weight", "ce_foreground_weight") if self.ce_weight > 0 else ()) + (
+                                      (("optimizer",) + (("momentum", "nesterov") if self.optimizer == "sgd" else ())) if self.optimizer != "adam" else ()) + (
+                                          ("clip_grad_norm",) if self.clip_grad_norm > 0 else ()) + (("lr_schedule", "poly_power") if self.lr_schedule == "poly" else ()):
             log("{:<34s} {}".format(k + " =", getattr(self, k)))
         log("-" * 10)
 
@@ -306,7 +319,12 @@ class VSparams:
 
     def set_and_get_optimizer(self, model):
         self.logger.info("Setting up the optimizer...")
-        return Adam(model.parameters(), lr=self.initial_learning_rate, weight_decay=self.weight_decay)
+        clip = self.clip_grad_norm if self.clip_grad_norm > 0 else None
+        if self.optimizer == "sgd":
+            return SGD(model.parameters(), lr=self.initial_learning_rate, momentum=self.momentum, weight_decay=self.weight_decay, nesterov=self.nesterov, max_grad_norm=clip)
+        if self.optimizer == "adamw":
+            return AdamW(model.parameters(), lr=self.initial_learning_rate, weight_decay=self.weight_decay, max_grad_norm=clip)
+        return Adam(model.parameters(), lr=self.initial_learning_rate, weight_decay=self.weight_decay, max_grad_norm=clip)
 
     def compute_dice_score(self, predicted_probabilities, label):
         return compute_dice_score(predicted_probabilities, label)  # [1,1] tensor, as the reference's
@@ -325,6 +343,10 @@ class VSparams:
             if epoch == self.val_interval:
                 el = perf_counter() - start
                 logger.info("Average duration of first {0:.0f} epochs = {1:.2f} s. Expected total training time = {2:.2f} h".format(self.val_interval, el / self.val_interval, el * self.num_epochs / self.val_interval / 3600))
+            if self.lr_schedule == "poly":
+                for group in optimizer.param_groups:
+                    group["lr"] = poly_lr(self.initial_learning_rate, epoch, self.num_epochs, self.poly_power)
+                    logger.info("Polynomial learning rate schedule: lr = {}".format(group["lr"]))
             model.train()
             step, losses = 0, []
             for batch in train_loader:
@@ -335,6 +357,10 @@ class VSparams:
                 denom = len(train_loader) // train_loader.batch_size  # the reference's denominator (ref:params/VSparams.py:466)
                 for i, v in enumerate(lv.tolist()):
                     logger.info("{}/{}, train_loss: {:.4f}".format(i + 1, denom, v))
+            if self.clip_grad_norm > 0 and hasattr(optimizer, "grad_norm_stats"):  # one more host read, beside the epoch's own
+                gn = optimizer.grad_norm_stats(reset=True)
+                logger.info("epoch {} gradient norm: mean {:.4f} max {:.4f}, clipped {}/{} steps at {}, skipped {} (NaN / Inf norm)".format(
+                    epoch + 1, gn["mean_norm"], gn["max_norm"], gn["clipped"], gn["steps"], self.clip_grad_norm, gn["skipped"]))
             epoch_loss = float(lv.sum()) / max(step, 1)
             if not np.isfinite(epoch_loss):
                 # the fixed-point accumulators (BatchNorm statistics, backward sums, Dice sums) flag an out-of-range or non-finite partial sum and every kernel that decodes
@@ -358,7 +384,7 @@ class VSparams:
                     logger.info("saved new best metric model")
                 logger.info("current epoch {} current mean dice: {:.4f} best mean dice: {:.4f} at epoch {}".format(epoch + 1, metric, best_metric, best_metric_epoch))
 
-            if (epoch + 1) % self.epochs_with_const_lr == 0:
+            if self.lr_schedule == "halving" and (epoch + 1) % self.epochs_with_const_lr == 0:
                 for group in optimizer.param_groups:
                     group["lr"] = group["lr"] / self.lr_divisor
                     logger.info("Dividing learning rate by {}. New learning rate is: lr = {}".format(self.lr_divisor, group["lr"]))
