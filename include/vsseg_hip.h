@@ -235,7 +235,7 @@ int vsseg_fork_event_destroy(void* ev);
 int vsseg_fork_arm(void* ev);
 int vsseg_fork_disarm(void);
 int vsseg_stream_wait_event(void* stream, void* ev);
-int vsseg_version(void); /* 15: + vsseg_grad_norm_scratch_bytes, vsseg_grad_norm, vsseg_sgd, vsseg_adam_clipped, vsseg_clip_record; 14: + vsseg_ce_sums, vsseg_dice_ce_finalize, vsseg_dice_ce_pred_bwd, vsseg_dice_ce_pred_bwd_to; 13: + vsseg_patch_filter, vsseg_patch_tone; 12: + vsseg_crop_field, vsseg_field_job; 11: + vsseg_crop_affine, vsseg_affine_job; 10: + vsseg_swi_finalize_mirrored, vsseg_crop_job.flip is a three-axis mirror mask (was flip_x); 9: + vsseg_components_scratch_bytes, vsseg_components_label, vsseg_keep_largest_component; 8: + vsseg_surface_distances, vsseg_surface_scratch_bytes; 7: + vsseg_dice_pred_bwd_to, vsseg_dice_level_sums, vsseg_dice_tail_sums, vsseg_dice_att_bwd_levels, vsseg_fork_*, vsseg_stream_wait_event; 6: + launch plans with depth -8 (transition kernel) and -9 (gathering marching kernel); 5: vsseg_wgrad march = 2 (compute weight-gradient kernel), + vsseg_conv_to1, vsseg_conv_chain_desc without h_out (the training variant measured no gain and was deleted); 4: + vsseg_conv_chain; 3: the BatchNorm-block-on-load fields (in_bn_*, keep_*, x_bn_*: round-4 experiment, measured a loss, deleted) left the descriptors, depth -7 plans;
+int vsseg_version(void); /* 16: + vsseg_topk_scratch_bytes, vsseg_topk_select, vsseg_ce_topk_select, vsseg_dice_ce_topk_finalize, vsseg_dice_ce_topk_pred_bwd, vsseg_dice_ce_topk_pred_bwd_to; 15: + vsseg_grad_norm_scratch_bytes, vsseg_grad_norm, vsseg_sgd, vsseg_adam_clipped, vsseg_clip_record; 14: + vsseg_ce_sums, vsseg_dice_ce_finalize, vsseg_dice_ce_pred_bwd, vsseg_dice_ce_pred_bwd_to; 13: + vsseg_patch_filter, vsseg_patch_tone; 12: + vsseg_crop_field, vsseg_field_job; 11: + vsseg_crop_affine, vsseg_affine_job; 10: + vsseg_swi_finalize_mirrored, vsseg_crop_job.flip is a three-axis mirror mask (was flip_x); 9: + vsseg_components_scratch_bytes, vsseg_components_label, vsseg_keep_largest_component; 8: + vsseg_surface_distances, vsseg_surface_scratch_bytes; 7: + vsseg_dice_pred_bwd_to, vsseg_dice_level_sums, vsseg_dice_tail_sums, vsseg_dice_att_bwd_levels, vsseg_fork_*, vsseg_stream_wait_event; 6: + launch plans with depth -8 (transition kernel) and -9 (gathering marching kernel); 5: vsseg_wgrad march = 2 (compute weight-gradient kernel), + vsseg_conv_to1, vsseg_conv_chain_desc without h_out (the training variant measured no gain and was deleted); 4: + vsseg_conv_chain; 3: the BatchNorm-block-on-load fields (in_bn_*, keep_*, x_bn_*: round-4 experiment, measured a loss, deleted) left the descriptors, depth -7 plans;
                             * 2: fixed-point accumulators documented + vsseg_fx_status; 1: the buffers below were described as plain doubles */
 
 /* ---- Accumulator buffers are 64-bit FIXED-POINT integers, not doubles ------------------------------------------------------------------
@@ -250,7 +250,7 @@ int vsseg_version(void); /* 15: + vsseg_grad_norm_scratch_bytes, vsseg_grad_norm
  *     VSSEG_FX_DICE_SCALE  2^32  Dice sums (pred_sums, att_sums)                              per-workgroup partial |v| < 1.0e6
  * (vsseg_hard_dice_counts keeps REAL doubles: its sums are integers, exact in fp64 in any order.)
  * A partial sum outside its range, or a NaN / Inf one, is clamped and sets a sticky per-process device flag; while the flag is set the decoding
- * kernels (vsseg_bn_finalize, vsseg_bn_act_bwd_finalize, vsseg_dice_finalize, vsseg_dice_ce_finalize) return NaN, so a diverging run or an out-of-range loss scale
+ * kernels (vsseg_bn_finalize, vsseg_bn_act_bwd_finalize, vsseg_dice_finalize, vsseg_dice_ce_finalize, vsseg_dice_ce_topk_finalize) return NaN, so a diverging run or an out-of-range loss scale
  * surfaces as NaN in the loss / statistics / gradients instead of as wrapped integers.  vsseg_fx_status reads (and optionally clears) the flag. */
 typedef double vsseg_fx_acc; /* one accumulator slot (reinterpret as int64_t) */
 #define VSSEG_FX_STAT_SCALE 1048576.0
@@ -415,6 +415,48 @@ int vsseg_dice_ce_finalize(const double* pred_sums, const double* att_sums, int3
                            float* ce_coef /* [2] */, void* stream);
 int vsseg_dice_ce_pred_bwd(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* ce_coef, const float* gscale, float* dlogits, void* stream);
 int vsseg_dice_ce_pred_bwd_to(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* ce_coef, const float* gscale, vsseg_tensor dst, void* stream);
+
+/* The cross-entropy term over the HARDEST voxels only (ABI version 16; nnU-Net's Dice + TopK loss, DC_and_topk_loss with k = 10).  N = n * nvox voxels of the batch,
+ * K = max(1, floor(N * P / 100)) computed by the caller from the shapes, P in (0, 100]:
+ *     loss = Dice_spvPA + ce_weight * TopK,   TopK = (1 / K) * (sum of the K largest v_i),   v_i = w[y_i] * softplus(z_i)
+ * with y, z, softplus and w = (1, ce_foreground_weight) as above, evaluated in fp32
+ * = ce_weight * F.cross_entropy(logits, y, weight=[1, w_fg], reduction='none').flatten().topk(K).values.mean().  THE DIVISION IS BY K, as in nnU-Net and torch, NOT by the
+ * weight sum W of the plain term; at P = 100 and w_fg = 1 the two terms are equal up to rounding.  The K voxels are those of the WHOLE BATCH of the call: in data-parallel
+ * training each rank selects among the voxels of its own batch (nnU-Net's DDP behaviour).
+ *   With t the K-th largest value, n_gt = #{v_i > t}, n_eq = #{v_i = t} (order-independent, ties included):
+ *   value     (S_gt + (K - n_gt) * t) / K,  S_gt = sum of the v_i > t
+ *   gradient  of a voxel: ce_weight * w[y] / K * c_i * (softmax(x) - onehot(y)), c_i = 1 where v_i > t, (K - n_gt) / n_eq where v_i = t (the tied voxels share what is
+ *             left of K; one voxel at the threshold: torch's gradient), 0 below t; formed from the other class's probability and added in fp32 to the Dice gradient
+ *             before the one store, as vsseg_dice_ce_pred_bwd does.
+ * Values are ranked by their KEY: the uint32 bit pattern of the fp32 value (non-negative floats order like their bits), -0 as 0, a NaN as 0xFFFFFFFF — a NaN is always
+ * selected: the loss is NaN and the sticky fixed-point flag is set, as with vsseg_ce_sums.
+ * The select is a radix select, digits of 11 + 11 + 10 bits: three histogram passes over the elements (per-workgroup LDS histograms, flushed with integer atomics),
+ * each followed by a one-workgroup scan that leaves the digit in the record; nothing is read by the host.  scratch: vsseg_topk_scratch_bytes() bytes of device memory,
+ * 8-byte aligned, owned by the caller and ZEROED before every select (vsseg_memset_zero, together with the loss sums).  Its first 32 bytes are the result:
+ *     offset  0  uint32  threshold_bits   key of the K-th largest element
+ *     offset  4  uint32  passes_done      3 once the record is complete
+ *     offset  8  uint64  n_gt             elements with a key above the threshold
+ *     offset 16  uint64  n_eq             elements with the threshold's key        (n_gt < K <= n_gt + n_eq)
+ *     offset 24  uint64  K
+ * (both counts come from the histograms: there is no counting pass); the rest is the state that goes from kernel to kernel (vs_seg_amd/csrc/topk.h), S_gt included:
+ * a fixed-point accumulator of scale VSSEG_FX_STAT_SCALE (the range argument of vsseg_ce_sums) filled by the LAST histogram pass, plus the part that the last
+ * histogram itself determines (a bin of the last digit is one bit pattern: count * value, exact in fp64) — no pass for the sum either.
+ * vsseg_topk_select — the select over an array of n values, 1 <= k <= n: the machinery on its own (no sum).  Negative values are outside the contract.
+ * vsseg_ce_topk_select — keys are the v_i, computed on the fly from logits and label (vsseg_ce_sums's two load paths).
+ * vsseg_dice_ce_topk_finalize — vsseg_dice_finalize that also decodes the record: loss += ce_weight * value in fp64 before the one cast, and
+ *   topk_coef[0..7] = (ce_weight / K, ce_weight * w_fg / K, the tie share (K - n_gt) / n_eq, threshold_bits (uint32), (float)w_fg, 0, 0, 0) in device memory for the
+ *   backward.  While the fixed-point flag is set the loss and the five coefficients are NaN (the threshold's bits 0xFFFFFFFF).
+ * vsseg_dice_ce_topk_pred_bwd / _to — vsseg_dice_ce_pred_bwd / _to that recompute v_i, compare its key with the threshold and scale the voxel's cross-entropy gradient
+ *   by c_i.  The select, the sum and the backward evaluate v_i by ONE device function with floating-point contraction off: the same bits in all of them. */
+int64_t vsseg_topk_scratch_bytes(void);
+int vsseg_topk_select(const float* values, int64_t n, int64_t k, void* scratch, void* stream);
+int vsseg_ce_topk_select(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, double ce_foreground_weight, int64_t k, void* scratch, void* stream);
+int vsseg_dice_ce_topk_finalize(const double* pred_sums, const double* att_sums, int32_t n, int32_t nlevels, const void* topk_scratch, double ce_weight, double ce_foreground_weight, float* loss, float* coef,
+                                float* topk_coef /* [8] */, void* stream);
+int vsseg_dice_ce_topk_pred_bwd(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* topk_coef, const float* gscale, float* dlogits,
+                                void* stream);
+int vsseg_dice_ce_topk_pred_bwd_to(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* topk_coef, const float* gscale, vsseg_tensor dst,
+                                   void* stream);
 
 /* torch.optim.Adam(lr, weight_decay) over the flat parameter buffer (ref:params/VSparams.py:388-391,462). */
 int vsseg_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float wd, float bc1, float bc2, float gscale, void* stream);

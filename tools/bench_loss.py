@@ -7,6 +7,11 @@ gradient of the logits written as bf16) with ce_weight = 0 and with the term, in
 the term adds or changes.
 
     python tools/bench_loss.py --ce_weight 1 [--ce_foreground_weight 1]
+
+With --ce_topk PCT as well it times the top-k term (Dice_spvPA(ce_topk=PCT)): the loss phase with ce_weight = 0, with the plain term and with the top-k term, alternating
+in the same process, at the same two shapes, for N(0, 1) logits and for the confident logits of a trained network, and the launches of the top-k term one by one.
+
+    python tools/bench_loss.py --ce_weight 1 --ce_topk 10        # profiles/topk_loss_bench.txt
 """
 import argparse
 import os
@@ -75,19 +80,90 @@ def bench_ce(lam, wfg, shapes):
         print(f"  vsseg_dice_ce_pred_bwd_to     {t1:8.1f} us   ({t1 - t0:+.1f} us)")
 
 
+def bench_topk(lam, wfg, pct, shapes):
+    """The loss phase without the cross-entropy term, with the plain term and with the top-k term, alternating in one process (three rounds each, the median), and the
+    launches the top-k term adds, one by one.  Twice per shape: N(0, 1) logits, whose values spread over many histogram bins, and the logits of a trained network — the
+    background confidently right (logit difference 16 +- 2: values around 1e-7), the foreground undecided — where a few bins take almost every voxel."""
+    import vs_seg_amd as V
+
+    lib = L.lib()
+    S = torch.cuda.current_stream().cuda_stream
+    ratios = [(2, 2, 1), (2, 2, 1), (2, 2, 2), (2, 2, 2), (2, 2, 2)]
+    print(f"loss phase of the fused train step (forward_backward_into, bf16 gradient of the logits): ce_weight 0, ce_weight {lam} (plain term), ce_weight {lam} with ce_topk {pct}; ce_foreground_weight {wfg}")
+    for B, d0 in shapes:
+        dims = [d0]
+        for r in ratios:
+            dims.append(tuple(x // y for x, y in zip(dims[-1], r)))
+        nvox = d0[0] * d0[1] * d0[2]
+        budget = {(4, (384, 128, 128)): 259.0, (2, (384, 384, 64)): 227.0}.get((B, d0))
+        torch.manual_seed(0)
+        lab = (torch.rand(B, 1, *d0, device="cuda") > 0.999).float()  # about one voxel in a thousand
+        atts = [torch.rand(B, 1, *d, device="cuda") for d in reversed(dims)]
+        dst = torch.empty(B, *d0, 2, device="cuda", dtype=torch.bfloat16)
+        bufs = [torch.empty(B, *a.shape[2:], device="cuda") for a in atts]
+        landing = (L.Tensor(dst.data_ptr(), L.BF16, 2, 2, B, *d0), bufs)
+        fns = [("ce_weight 0", V.Dice_spvPA(to_onehot_y=True, softmax=True)), (f"ce_weight {lam:g}", V.Dice_spvPA(to_onehot_y=True, softmax=True, ce_weight=lam, ce_foreground_weight=wfg)),
+               (f"ce_weight {lam:g} ce_topk {pct:g}", V.Dice_spvPA(to_onehot_y=True, softmax=True, ce_weight=lam, ce_foreground_weight=wfg, ce_topk=pct))]
+        for kind in ("N(0, 1) logits", "trained logits"):
+            lg = torch.randn(B, *d0, 2, device="cuda")
+            if kind == "trained logits":
+                lg[..., 0] += 8.0 * (1.0 - lab.reshape(B, *d0))
+                lg[..., 1] -= 8.0 * (1.0 - lab.reshape(B, *d0))
+            logits = lg.permute(0, 4, 1, 2, 3)  # channels-last storage, as the network hands it out
+            times = [[] for _ in fns]
+            for _ in range(3):
+                for t, (_, fn) in zip(times, fns):
+                    t.append(timed(lambda: fn.forward_backward_into((logits, atts), lab, landing)))
+            med = [sorted(t)[1] for t in times]
+            losses = [float(fn.forward_backward_into((logits, atts), lab, landing)[0]) for _, fn in fns]
+            rec = [int(v) for v in fns[2][1].topk_record.cpu().tolist()]
+            print(f"batch {B} of {d0[0]}x{d0[1]}x{d0[2]} ({B * nvox / 1e6:.1f} M voxels), {kind}: losses {', '.join(f'{v:.6f}' for v in losses)}; K {rec[3]}, n_gt {rec[1]}, n_eq {rec[2]}")
+            for (name, _), m, t in zip(fns, med, times):
+                print(f"  loss phase, {name:<28s} {m:8.1f} us   (rounds: {', '.join(f'{x:.1f}' for x in t)})")
+            print(f"  top-k against ce_weight 0                {med[2] - med[0]:8.1f} us" + (f"   (budget of an optional family: 1 % of the step = {budget:.0f} us)" if budget else ""))
+            print(f"  top-k against the plain term             {med[2] - med[1]:8.1f} us")
+            sums = torch.zeros(B * 6 + L.topk_scratch_bytes() // 8, dtype=torch.float64, device="cuda")
+            rec_at = sums.data_ptr() + 8 * B * 6
+            coef = torch.full((B * 4 + 6 * B * 2,), 1e-6, device="cuda")
+            tk = torch.zeros(8, device="cuda")
+            l2 = lab.reshape(B, *d0)
+            k = V.topk_count(B * nvox, pct)
+
+            def select():
+                lib.vsseg_memset_zero(sums.data_ptr(), sums.numel() * 8, S)
+                L.check(lib.vsseg_ce_topk_select(lg.data_ptr(), 2, l2.data_ptr(), B, nvox, wfg, k, rec_at, S))
+
+            t = timed(select)
+            print(f"  vsseg_ce_topk_select (3 x histogram + scan) {t:6.1f} us   ({3 * B * nvox * 12 / t / 1e6:.2f} TB/s over three reads of logits + label)")
+            t = timed(lambda: lib.vsseg_dice_ce_topk_finalize(sums.data_ptr(), None, B, 0, rec_at, lam, wfg, coef.data_ptr(), coef.data_ptr(), tk.data_ptr(), S))
+            print(f"  vsseg_dice_ce_topk_finalize   {t:8.1f} us")
+            cek = torch.full((2,), 1e-8, device="cuda")
+            t0 = timed(lambda: lib.vsseg_dice_ce_pred_bwd_to(lg.data_ptr(), 2, l2.data_ptr(), B, nvox, 1, coef.data_ptr(), cek.data_ptr(), None, landing[0], S))
+            t1 = timed(lambda: lib.vsseg_dice_ce_topk_pred_bwd_to(lg.data_ptr(), 2, l2.data_ptr(), B, nvox, 1, coef.data_ptr(), tk.data_ptr(), None, landing[0], S))
+            print(f"  vsseg_dice_ce_pred_bwd_to bf16 {t0:7.1f} us")
+            print(f"  vsseg_dice_ce_topk_pred_bwd_to {t1:7.1f} us   ({t1 - t0:+.1f} us)")
+            t = timed(lambda: lib.vsseg_ce_sums(lg.data_ptr(), 2, l2.data_ptr(), B, nvox, sums.data_ptr(), S))
+            print(f"  vsseg_ce_sums (the plain term's pass) {t:6.1f} us")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--dims", type=int, nargs=3, default=[384, 128, 128])
     ap.add_argument("--ce_weight", type=float, default=0.0, help="> 0: time the loss phase with and without the cross-entropy term instead (at the benchmark shape and at batch 2 of 384x384x64)")
     ap.add_argument("--ce_foreground_weight", type=float, default=1.0)
+    ap.add_argument("--ce_topk", type=float, default=0.0, metavar="PCT", help="> 0 (with --ce_weight): time the loss phase without the term, with the plain term and with the top-k term over the hardest PCT percent")
     a = ap.parse_args()
-    from vs_seg_amd import check_ce
+    from vs_seg_amd import check_ce, check_ce_topk
 
     try:
         lam, wfg = check_ce(a.ce_weight, a.ce_foreground_weight)
+        pct = check_ce_topk(a.ce_topk, lam)
     except ValueError as e:
         ap.error(str(e))
+    if pct > 0:
+        bench_topk(lam, wfg, pct, [(a.batch, tuple(a.dims)), (2, (384, 384, 64))])
+        return
     if lam > 0:
         bench_ce(lam, wfg, [(a.batch, tuple(a.dims)), (2, (384, 384, 64))])
         return

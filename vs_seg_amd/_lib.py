@@ -239,6 +239,7 @@ SYMBOLS = [
     "vsseg_surface_scratch_bytes", "vsseg_surface_distances",
     "vsseg_components_scratch_bytes", "vsseg_components_label", "vsseg_keep_largest_component",
     "vsseg_grad_norm_scratch_bytes", "vsseg_grad_norm", "vsseg_sgd", "vsseg_adam_clipped",
+    "vsseg_topk_scratch_bytes", "vsseg_topk_select", "vsseg_ce_topk_select", "vsseg_dice_ce_topk_finalize", "vsseg_dice_ce_topk_pred_bwd", "vsseg_dice_ce_topk_pred_bwd_to",
 ]  # fmt: skip
 
 _lib = None
@@ -307,6 +308,12 @@ def lib():
         L.vsseg_dice_ce_finalize.argtypes = [vp, vp, i32, i32, vp, i64, f64, f64, vp, vp, vp, vp]
         L.vsseg_dice_ce_pred_bwd.argtypes = [vp, i32, vp, i32, i64, i32, vp, vp, vp, vp, vp]
         L.vsseg_dice_ce_pred_bwd_to.argtypes = [vp, i32, vp, i32, i64, i32, vp, vp, vp, Tensor, vp]
+        L.vsseg_topk_scratch_bytes.argtypes, L.vsseg_topk_scratch_bytes.restype = [], i64
+        L.vsseg_topk_select.argtypes = [vp, i64, i64, vp, vp]
+        L.vsseg_ce_topk_select.argtypes = [vp, i32, vp, i32, i64, f64, i64, vp, vp]
+        L.vsseg_dice_ce_topk_finalize.argtypes = [vp, vp, i32, i32, vp, f64, f64, vp, vp, vp, vp]
+        L.vsseg_dice_ce_topk_pred_bwd.argtypes = [vp, i32, vp, i32, i64, i32, vp, vp, vp, vp, vp]
+        L.vsseg_dice_ce_topk_pred_bwd_to.argtypes = [vp, i32, vp, i32, i64, i32, vp, vp, vp, Tensor, vp]
         L.vsseg_fork_event_create.argtypes, L.vsseg_fork_event_create.restype = [], vp
         L.vsseg_fork_event_destroy.argtypes = [vp]
         L.vsseg_fork_arm.argtypes = [vp]
@@ -360,6 +367,18 @@ def fx_status(reset: bool = False) -> bool:
     if rc < 0:
         check(rc, "fx_status")
     return bool(rc)
+
+
+_topk_bytes = None
+
+
+def topk_scratch_bytes() -> int:
+    """Bytes of the caller-owned scratch of vsseg_topk_select / vsseg_ce_topk_select (a multiple of 8; asked once)."""
+    global _topk_bytes
+    if _topk_bytes is None:
+        _topk_bytes = int(lib().vsseg_topk_scratch_bytes())
+        assert _topk_bytes > 32 and _topk_bytes % 8 == 0
+    return _topk_bytes
 
 
 def i3(v):

@@ -2,6 +2,7 @@
 // and the hard-Dice metric (ref:params/VSparams.py:393-408).  Everything here is HBM-bound: logits are read once
 // forward and once backward; the ~25 ATen temporaries of the reference never exist.
 #include "common.h"
+#include "topk.h"
 
 #define SMOOTH 1e-5
 
@@ -372,8 +373,10 @@ extern "C" int vsseg_ce_sums(const float* logits, int32_t pitch, const float* la
 // loss = mean_{b,c} f_pred + sum_l (1/L) mean_b f_att,  f = 1 - (2I+eps)/(G+P+eps).  coef holds d(loss)/dI and d(loss)/dG(=dP).
 // With `ce_sums` (vsseg_dice_ce_finalize): + ce_weight * (S_bg + w_fg * S_fg) / W, added in fp64 before the one cast, and ce_coef = (ce_weight / W, ce_weight * w_fg / W),
 // W = (voxels - N_fg) + w_fg * N_fg — the backward reads the two from device memory: no host read of N_fg.
+// With `topk` (vsseg_dice_ce_topk_finalize; the record of vsseg_ce_topk_select, topk.h): + ce_weight * (S_gt + (K - n_gt) * t) / K, S_gt = s_above + s_tail, and
+// topk_coef = (ce_weight / K, ce_weight * w_fg / K, the tie share (K - n_gt) / n_eq, the threshold's bits, w_fg as the select rounded it) — the division is by K, not by W.
 __global__ void dice_finalize_kernel(const double* pred_sums, const double* att_sums, int n, int nlevels, float* loss, float* coef, const unsigned* fxflag,
-                                     const double* ce_sums, double voxels, double ce_weight, double ce_fg_weight, float* ce_coef) {
+                                     const double* ce_sums, double voxels, double ce_weight, double ce_fg_weight, float* ce_coef, const TopkRec* topk, float* topk_coef) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   double total = vsseg_fx_poison(fxflag);  // NaN while a partial sum of this process was non-finite / out of range (common.h)
   for (int b = 0; b < n; ++b)
@@ -401,12 +404,25 @@ __global__ void dice_finalize_kernel(const double* pred_sums, const double* att_
     ce_coef[0] = (float)(ce_weight / W);
     ce_coef[1] = (float)(ce_weight * ce_fg_weight / W);
   }
+  if (topk) {
+    const double K = (double)topk->k + total * 0.0, ngt = (double)topk->n_gt, neq = (double)topk->n_eq;  // (+ NaN when poisoned: the coefficients too)
+    const double t = (double)__uint_as_float(topk->threshold_bits);
+    const double rest = K - ngt;  // what the elements at the threshold share: 1 <= rest <= n_eq
+    total += ce_weight * ((vsseg_fx_get(&topk->s_above, VSSEG_FX_STAT) + topk->s_tail) + rest * t) / K;
+    topk_coef[0] = (float)(ce_weight / K);
+    topk_coef[1] = (float)(ce_weight * ce_fg_weight / K);
+    topk_coef[2] = (float)(rest / neq);
+    const bool poisoned = *fxflag != 0u;  // (then the threshold and the weight are NaN patterns as well: every coefficient is)
+    reinterpret_cast<unsigned*>(topk_coef)[3] = poisoned ? 0xFFFFFFFFu : topk->threshold_bits;
+    topk_coef[4] = poisoned ? __uint_as_float(0x7FC00000u) : (float)ce_fg_weight;
+    topk_coef[5] = topk_coef[6] = topk_coef[7] = 0.f;
+  }
   *loss = (float)total;
 }
 extern "C" int vsseg_dice_finalize(const double* pred_sums, const double* att_sums, int32_t n, int32_t nlevels, float* loss, float* coef, void* stream) {
   VSSEG_CHECK(pred_sums && loss && coef && (nlevels == 0 || att_sums), "vsseg_dice_finalize: bad arguments");
   VSSEG_FX_FLAG(fxflag, "vsseg_dice_finalize");
-  hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(64), 0, as_stream(stream), pred_sums, att_sums, n, nlevels, loss, coef, fxflag, (const double*)nullptr, 0.0, 0.0, 0.0, (float*)nullptr);
+  hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(64), 0, as_stream(stream), pred_sums, att_sums, n, nlevels, loss, coef, fxflag, (const double*)nullptr, 0.0, 0.0, 0.0, (float*)nullptr, (const TopkRec*)nullptr, (float*)nullptr);
   VSSEG_LAUNCH_CHECK("vsseg_dice_finalize");
   return VSSEG_OK;
 }
@@ -415,8 +431,18 @@ extern "C" int vsseg_dice_ce_finalize(const double* pred_sums, const double* att
   VSSEG_CHECK(pred_sums && loss && coef && (nlevels == 0 || att_sums) && ce_sums && ce_coef && n >= 1 && nvox >= 1, "vsseg_dice_ce_finalize: bad arguments");
   VSSEG_CHECK(ce_weight >= 0.0 && ce_weight < INFINITY && ce_foreground_weight > 0.0 && ce_foreground_weight < INFINITY, "vsseg_dice_ce_finalize: ce_weight must be finite and >= 0, ce_foreground_weight finite and > 0");
   VSSEG_FX_FLAG(fxflag, "vsseg_dice_ce_finalize");
-  hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(64), 0, as_stream(stream), pred_sums, att_sums, n, nlevels, loss, coef, fxflag, ce_sums, (double)n * (double)nvox, ce_weight, ce_foreground_weight, ce_coef);
+  hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(64), 0, as_stream(stream), pred_sums, att_sums, n, nlevels, loss, coef, fxflag, ce_sums, (double)n * (double)nvox, ce_weight, ce_foreground_weight, ce_coef, (const TopkRec*)nullptr, (float*)nullptr);
   VSSEG_LAUNCH_CHECK("vsseg_dice_ce_finalize");
+  return VSSEG_OK;
+}
+extern "C" int vsseg_dice_ce_topk_finalize(const double* pred_sums, const double* att_sums, int32_t n, int32_t nlevels, const void* topk_scratch, double ce_weight, double ce_foreground_weight, float* loss, float* coef,
+                                           float* topk_coef, void* stream) {
+  VSSEG_CHECK(pred_sums && loss && coef && (nlevels == 0 || att_sums) && topk_scratch && topk_coef && n >= 1, "vsseg_dice_ce_topk_finalize: bad arguments");
+  VSSEG_CHECK(ce_weight >= 0.0 && ce_weight < INFINITY && ce_foreground_weight > 0.0 && ce_foreground_weight < INFINITY, "vsseg_dice_ce_topk_finalize: ce_weight must be finite and >= 0, ce_foreground_weight finite and > 0");
+  VSSEG_FX_FLAG(fxflag, "vsseg_dice_ce_topk_finalize");
+  hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(64), 0, as_stream(stream), pred_sums, att_sums, n, nlevels, loss, coef, fxflag, (const double*)nullptr, 0.0, ce_weight, ce_foreground_weight, (float*)nullptr,
+                     reinterpret_cast<const TopkRec*>(topk_scratch), topk_coef);
+  VSSEG_LAUNCH_CHECK("vsseg_dice_ce_topk_finalize");
   return VSSEG_OK;
 }
 
@@ -450,7 +476,18 @@ template <bool CE> __device__ __forceinline__ float2 dice_pred_grad(float l0, fl
 // 3: fp32, any pitch (channels >= 2 are not touched).  1-3 are the layouts the training plan stages the gradient in (vsseg_dice_pred_bwd_to): written here, the
 // fp32 tensor and the cast pass over it (0.3 GB read + written per step at 4 x 384x128x128) do not exist.  Same values: the cast was the same round-to-nearest-even.
 // CE: the cross-entropy gradient is formed here as well (vsseg_dice_ce_pred_bwd / _to) and the sum is stored once — a second pass would round the bf16 operand twice.
-template <int OUT, bool CE> __global__ __launch_bounds__(256) void dice_pred_bwd_kernel(const float* __restrict__ logits, int pitch, const float* __restrict__ label, int64_t nvox, int hardness, const float* __restrict__ coef,
+// CE 2 (the top-k term, vsseg_dice_ce_topk_pred_bwd / _to): the voxel's cross-entropy gradient times c = 1 above the threshold, the tie share at it, 0 below it — its value
+// is recomputed by the one function of topk.h and its KEY is compared with the threshold's bits, as the select counted it.
+template <int CE> __device__ __forceinline__ float2 dice_pred_grad_of(float l0, float l1, float lab, int hardness, float A0, float B0, float A1, float B1, float kbg, float kfg, float share, unsigned tbits, float wfg) {
+  if constexpr (CE == 2) {
+    const unsigned u = topk_key(ce_topk_value(l0, l1, lab, wfg));
+    const float c = u > tbits ? 1.f : (u == tbits ? share : 0.f);
+    return dice_pred_grad<true>(l0, l1, lab, hardness, A0, B0, A1, B1, kbg * c, kfg * c);
+  } else {
+    return dice_pred_grad<CE != 0>(l0, l1, lab, hardness, A0, B0, A1, B1, kbg, kfg);
+  }
+}
+template <int OUT, int CE> __global__ __launch_bounds__(256) void dice_pred_bwd_kernel(const float* __restrict__ logits, int pitch, const float* __restrict__ label, int64_t nvox, int hardness, const float* __restrict__ coef,
                                                                                           const float* __restrict__ gscale, void* __restrict__ dst, int dpitch, const float* __restrict__ ce_coef) {
   const int b = blockIdx.y;
   const float* lg = logits + (int64_t)b * nvox * pitch;
@@ -458,7 +495,10 @@ template <int OUT, bool CE> __global__ __launch_bounds__(256) void dice_pred_bwd
   const float gs = gscale ? *gscale : 1.f;
   const float A0 = coef[(b * 2 + 0) * 2] * gs, B0 = coef[(b * 2 + 0) * 2 + 1] * gs, A1 = coef[(b * 2 + 1) * 2] * gs, B1 = coef[(b * 2 + 1) * 2 + 1] * gs;
   float kbg = 0.f, kfg = 0.f;
-  if constexpr (CE) { kbg = ce_coef[0] * gs; kfg = ce_coef[1] * gs; }
+  float share = 0.f, wfg = 1.f;
+  unsigned tbits = 0u;
+  if constexpr (CE != 0) { kbg = ce_coef[0] * gs; kfg = ce_coef[1] * gs; }
+  if constexpr (CE == 2) { share = ce_coef[2]; tbits = reinterpret_cast<const unsigned*>(ce_coef)[3]; wfg = ce_coef[4]; }  // (vsseg_dice_ce_topk_finalize's topk_coef)
   const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
   auto store = [&](int64_t v, float2 g) {
     const int64_t e = ((int64_t)b * nvox + v) * dpitch;
@@ -471,8 +511,8 @@ template <int OUT, bool CE> __global__ __launch_bounds__(256) void dice_pred_bwd
     const float4* lb4 = reinterpret_cast<const float4*>(lb);
     for (int64_t i = tid; i < (nvox >> 2); i += nthr) {
       const float4 a = lg4[2 * i], c = lg4[2 * i + 1], g = lb4[i];
-      const float2 r0 = dice_pred_grad<CE>(a.x, a.y, g.x, hardness, A0, B0, A1, B1, kbg, kfg), r1 = dice_pred_grad<CE>(a.z, a.w, g.y, hardness, A0, B0, A1, B1, kbg, kfg);
-      const float2 r2 = dice_pred_grad<CE>(c.x, c.y, g.z, hardness, A0, B0, A1, B1, kbg, kfg), r3 = dice_pred_grad<CE>(c.z, c.w, g.w, hardness, A0, B0, A1, B1, kbg, kfg);
+      const float2 r0 = dice_pred_grad_of<CE>(a.x, a.y, g.x, hardness, A0, B0, A1, B1, kbg, kfg, share, tbits, wfg), r1 = dice_pred_grad_of<CE>(a.z, a.w, g.y, hardness, A0, B0, A1, B1, kbg, kfg, share, tbits, wfg);
+      const float2 r2 = dice_pred_grad_of<CE>(c.x, c.y, g.z, hardness, A0, B0, A1, B1, kbg, kfg, share, tbits, wfg), r3 = dice_pred_grad_of<CE>(c.z, c.w, g.w, hardness, A0, B0, A1, B1, kbg, kfg, share, tbits, wfg);
       if constexpr (OUT == 0) {
         float4* o = reinterpret_cast<float4*>(reinterpret_cast<float*>(dst) + ((int64_t)b * nvox + 4 * i) * 2);
         o[0] = make_float4(r0.x, r0.y, r1.x, r1.y);
@@ -486,11 +526,11 @@ template <int OUT, bool CE> __global__ __launch_bounds__(256) void dice_pred_bwd
   } else {
     for (int64_t v = tid; v < nvox; v += nthr) {
       const float2 l = *reinterpret_cast<const float2*>(lg + v * pitch);
-      store(v, dice_pred_grad<CE>(l.x, l.y, lb[v], hardness, A0, B0, A1, B1, kbg, kfg));
+      store(v, dice_pred_grad_of<CE>(l.x, l.y, lb[v], hardness, A0, B0, A1, B1, kbg, kfg, share, tbits, wfg));
     }
   }
 }
-template <bool CE>
+template <int CE>
 static int dice_pred_bwd_launch(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* ce_coef, const float* gscale, void* dst, int out, int dpitch,
                                 void* stream, const char* who) {
   VSSEG_CHECK(logits && label && coef && dst && pitch >= 2 && pitch % 2 == 0 && n >= 1 && (!CE || ce_coef), "%s: bad arguments", who);
@@ -516,22 +556,32 @@ static int dice_pred_bwd_layout(const vsseg_tensor& dst, int32_t n, int64_t nvox
   return -1;
 }
 extern "C" int vsseg_dice_pred_bwd(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* gscale, float* dlogits, void* stream) {
-  return dice_pred_bwd_launch<false>(logits, pitch, label, n, nvox, hardness, coef, nullptr, gscale, dlogits, 0, 2, stream, "vsseg_dice_pred_bwd");
+  return dice_pred_bwd_launch<0>(logits, pitch, label, n, nvox, hardness, coef, nullptr, gscale, dlogits, 0, 2, stream, "vsseg_dice_pred_bwd");
 }
 extern "C" int vsseg_dice_pred_bwd_to(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* gscale, vsseg_tensor dst, void* stream) {
   const int out = dice_pred_bwd_layout(dst, n, nvox, "vsseg_dice_pred_bwd_to");
   if (out < 0) return VSSEG_EINVAL;
-  return dice_pred_bwd_launch<false>(logits, pitch, label, n, nvox, hardness, coef, nullptr, gscale, dst.ptr, out, dst.pitch, stream, "vsseg_dice_pred_bwd_to");
+  return dice_pred_bwd_launch<0>(logits, pitch, label, n, nvox, hardness, coef, nullptr, gscale, dst.ptr, out, dst.pitch, stream, "vsseg_dice_pred_bwd_to");
 }
 extern "C" int vsseg_dice_ce_pred_bwd(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* ce_coef, const float* gscale, float* dlogits,
                                       void* stream) {
-  return dice_pred_bwd_launch<true>(logits, pitch, label, n, nvox, hardness, coef, ce_coef, gscale, dlogits, 0, 2, stream, "vsseg_dice_ce_pred_bwd");
+  return dice_pred_bwd_launch<1>(logits, pitch, label, n, nvox, hardness, coef, ce_coef, gscale, dlogits, 0, 2, stream, "vsseg_dice_ce_pred_bwd");
 }
 extern "C" int vsseg_dice_ce_pred_bwd_to(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* ce_coef, const float* gscale, vsseg_tensor dst,
                                          void* stream) {
   const int out = dice_pred_bwd_layout(dst, n, nvox, "vsseg_dice_ce_pred_bwd_to");
   if (out < 0) return VSSEG_EINVAL;
-  return dice_pred_bwd_launch<true>(logits, pitch, label, n, nvox, hardness, coef, ce_coef, gscale, dst.ptr, out, dst.pitch, stream, "vsseg_dice_ce_pred_bwd_to");
+  return dice_pred_bwd_launch<1>(logits, pitch, label, n, nvox, hardness, coef, ce_coef, gscale, dst.ptr, out, dst.pitch, stream, "vsseg_dice_ce_pred_bwd_to");
+}
+extern "C" int vsseg_dice_ce_topk_pred_bwd(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* topk_coef, const float* gscale, float* dlogits,
+                                           void* stream) {
+  return dice_pred_bwd_launch<2>(logits, pitch, label, n, nvox, hardness, coef, topk_coef, gscale, dlogits, 0, 2, stream, "vsseg_dice_ce_topk_pred_bwd");
+}
+extern "C" int vsseg_dice_ce_topk_pred_bwd_to(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* topk_coef, const float* gscale,
+                                              vsseg_tensor dst, void* stream) {
+  const int out = dice_pred_bwd_layout(dst, n, nvox, "vsseg_dice_ce_topk_pred_bwd_to");
+  if (out < 0) return VSSEG_EINVAL;
+  return dice_pred_bwd_launch<2>(logits, pitch, label, n, nvox, hardness, coef, topk_coef, gscale, dst.ptr, out, dst.pitch, stream, "vsseg_dice_ce_topk_pred_bwd_to");
 }
 
 __global__ void dice_att_bwd_kernel(const float* __restrict__ label, int64_t nvox, const float* __restrict__ coef, const float* __restrict__ gscale, float* __restrict__ datt) {

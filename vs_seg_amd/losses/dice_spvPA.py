@@ -10,6 +10,9 @@ logits and one per supervised attention map.  Returns a 0-dim tensor supporting 
 Beyond the reference: `ce_weight` adds a voxel-wise cross-entropy term on the final logits (MONAI's DiceCELoss, nnU-Net's default loss),
 loss += ce_weight * F.cross_entropy(logits, target == 1, weight=[1, ce_foreground_weight]) — one more reduction pass forward, its gradient
 formed inside the Dice backward kernel (include/vsseg_hip.h).  0 (the default) issues exactly the launches of the plain Dice loss.
+`ce_topk` = P > 0 averages that term over the hardest P percent of the voxels of the batch only (nnU-Net's Dice + TopK loss, DC_and_topk_loss with k = 10):
+loss += ce_weight * F.cross_entropy(..., reduction='none').flatten().topk(K).values.mean(), K = max(1, floor(N * P / 100)) — divided by K, not by the class-weight sum.
+The K voxels are found by a radix select on the GPU (csrc/topk.hip); the backward compares each voxel's value with the threshold the select left in device memory.
 """
 from __future__ import annotations
 
@@ -38,6 +41,25 @@ def check_ce(ce_weight: float, ce_foreground_weight: float = 1.0) -> Tuple[float
     return lam, wfg
 
 
+def check_ce_topk(ce_topk: float, ce_weight: float) -> float:
+    """The percentage of the top-k cross-entropy term as a float, or ValueError: finite and in [0, 100] (0: off, the mean over every voxel), and not a percentage
+    without the term (ce_weight > 0) — a flag that would silently do nothing."""
+    try:
+        pct, lam = float(ce_topk), float(ce_weight)
+    except (TypeError, ValueError):
+        raise ValueError(f"ce_topk and ce_weight must be numbers (got {ce_topk!r}, {ce_weight!r})") from None
+    if not math.isfinite(pct) or pct < 0 or pct > 100:
+        raise ValueError(f"ce_topk must be a percentage in [0, 100] (got {ce_topk!r})")
+    if pct > 0 and not lam > 0:
+        raise ValueError(f"ce_topk = {ce_topk!r} has no effect without the cross-entropy term: give ce_weight > 0 as well")
+    return pct
+
+
+def topk_count(voxels: int, ce_topk: float) -> int:
+    """K = max(1, floor(N * P / 100)): how many of the N voxels of a batch the top-k term averages over (nnU-Net: int(num_voxels * k / 100))."""
+    return min(int(voxels), max(1, int(math.floor(int(voxels) * float(ce_topk) / 100.0))))
+
+
 def _cl_logits(x: torch.Tensor) -> torch.Tensor:
     """[B,2,X,Y,Z] -> contiguous channels-last [B,X,Y,Z,2] fp32 (zero-copy when the tensor came from vs_seg_amd's network)."""
     v = x.detach().permute(0, 2, 3, 4, 1)
@@ -55,11 +77,12 @@ def _c1(x: torch.Tensor) -> torch.Tensor:
 
 class _State:
     """What the forward leaves for the backward: channels-last logits, labels (full resolution + the pyramid), the coefficients of vsseg_dice_finalize
-    (and, with the cross-entropy term, the two of vsseg_dice_ce_finalize; None without it)."""
-    __slots__ = ("lg", "lab", "labels", "coef", "ce_coef", "hardness", "nl", "shape", "att_shapes", "loss")
+    (and, with the cross-entropy term, the two of vsseg_dice_ce_finalize or, with ce_topk, the eight of vsseg_dice_ce_topk_finalize; None without it).
+    topk_rec: with ce_topk, the first 32 bytes of the select's record as four int64 on the device (threshold_bits | passes_done << 32, n_gt, n_eq, K)."""
+    __slots__ = ("lg", "lab", "labels", "coef", "ce_coef", "topk", "topk_rec", "hardness", "nl", "shape", "att_shapes", "loss")
 
 
-def _dice_forward(logits, target, supervised, hardness, atts, ce=(0.0, 1.0)) -> _State:
+def _dice_forward(logits, target, supervised, hardness, atts, ce=(0.0, 1.0), ce_topk=0.0) -> _State:
     lib = L.lib()
     stream = torch.cuda.current_stream().cuda_stream
     dev = logits.device
@@ -72,8 +95,10 @@ def _dice_forward(logits, target, supervised, hardness, atts, ce=(0.0, 1.0)) -> 
     nvox = X * Y * Z
     nl = len(atts) if supervised else 0
     ce_on = ce[0] > 0
+    topk_on = ce_on and ce_topk > 0
     nsums = B * 6 + max(nl, 1) * B * 3
-    sums = torch.empty(nsums + (3 if ce_on else 0), dtype=torch.float64, device=dev)  # [pred | att levels | CE], zeroed through the C ABI (no ATen fill kernels on the step)
+    nce = (L.topk_scratch_bytes() // 8 if topk_on else 3) if ce_on else 0  # the three sums of the plain term, or the record and histograms of the select
+    sums = torch.empty(nsums + nce, dtype=torch.float64, device=dev)  # [pred | att levels | CE], zeroed through the C ABI (no ATen fill kernels on the step)
     L.check(lib.vsseg_memset_zero(sums.data_ptr(), sums.numel() * 8, stream), "memset_zero")
     pred_sums, att_sums, ce_sums = sums[: B * 6], sums[B * 6 : nsums], sums[nsums:]
     labels: List[torch.Tensor] = []
@@ -122,7 +147,13 @@ def _dice_forward(logits, target, supervised, hardness, atts, ce=(0.0, 1.0)) -> 
     loss = torch.empty((), dtype=torch.float32, device=dev)  # vsseg_dice_finalize assigns the loss and every coefficient it is asked for
     coef = torch.empty(B * 4 + max(nl, 1) * B * 2, dtype=torch.float32, device=dev)
     st = _State()
-    if ce_on:  # one more pass over logits and label; the finalize decodes its three sums too and leaves the two gradient coefficients on the device
+    st.topk, st.topk_rec = topk_on, None
+    if topk_on:  # three histogram passes over logits and label leave the threshold, the counts and the sum in ce_sums; the finalize leaves the backward's coefficients
+        L.check(lib.vsseg_ce_topk_select(lg.data_ptr(), 2, lab.data_ptr(), B, nvox, ce[1], topk_count(B * nvox, ce_topk), ce_sums.data_ptr(), stream), "ce_topk_select")
+        st.ce_coef = torch.empty(8, dtype=torch.float32, device=dev)
+        L.check(lib.vsseg_dice_ce_topk_finalize(pred_sums.data_ptr(), att_sums.data_ptr(), B, nl, ce_sums.data_ptr(), ce[0], ce[1], loss.data_ptr(), coef.data_ptr(), st.ce_coef.data_ptr(), stream), "dice_ce_topk_finalize")
+        st.topk_rec = ce_sums[:4].view(torch.int64)
+    elif ce_on:  # one more pass over logits and label; the finalize decodes its three sums too and leaves the two gradient coefficients on the device
         L.check(lib.vsseg_ce_sums(lg.data_ptr(), 2, lab.data_ptr(), B, nvox, ce_sums.data_ptr(), stream), "ce_sums")
         st.ce_coef = torch.empty(2, dtype=torch.float32, device=dev)
         L.check(lib.vsseg_dice_ce_finalize(pred_sums.data_ptr(), att_sums.data_ptr(), B, nl, ce_sums.data_ptr(), nvox, ce[0], ce[1], loss.data_ptr(), coef.data_ptr(), st.ce_coef.data_ptr(), stream), "dice_ce_finalize")
@@ -163,8 +194,9 @@ def _att_backward(st: _State, level: int, gs_ptr, dst: torch.Tensor):
 
 class _DiceFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, target, supervised, hardness, ce, *atts):
-        ctx.st = st = _dice_forward(logits, target, supervised, hardness, atts, ce)
+    def forward(ctx, logits, target, supervised, hardness, ce, owner, *atts):
+        ctx.st = st = _dice_forward(logits, target, supervised, hardness, atts, ce[:2], ce[2])
+        owner.topk_record = st.topk_rec  # (the Dice_spvPA object: the record of its last call, None without ce_topk)
         return st.loss
 
     @staticmethod
@@ -178,6 +210,8 @@ class _DiceFn(torch.autograd.Function):
         dlog = torch.empty((B, X, Y, Z, 2), dtype=torch.float32, device=dev)
         if st.ce_coef is None:
             L.check(lib.vsseg_dice_pred_bwd(st.lg.data_ptr(), 2, st.lab.data_ptr(), B, X * Y * Z, st.hardness, st.coef.data_ptr(), gs.data_ptr(), dlog.data_ptr(), stream), "dice_pred_bwd")
+        elif st.topk:
+            L.check(lib.vsseg_dice_ce_topk_pred_bwd(st.lg.data_ptr(), 2, st.lab.data_ptr(), B, X * Y * Z, st.hardness, st.coef.data_ptr(), st.ce_coef.data_ptr(), gs.data_ptr(), dlog.data_ptr(), stream), "dice_ce_topk_pred_bwd")
         else:
             L.check(lib.vsseg_dice_ce_pred_bwd(st.lg.data_ptr(), 2, st.lab.data_ptr(), B, X * Y * Z, st.hardness, st.coef.data_ptr(), st.ce_coef.data_ptr(), gs.data_ptr(), dlog.data_ptr(), stream), "dice_ce_pred_bwd")
         datts: List[Optional[torch.Tensor]] = [None] * len(st.att_shapes)
@@ -186,18 +220,21 @@ class _DiceFn(torch.autograd.Function):
             d = torch.empty(st.att_shapes[i], dtype=torch.float32, device=dev)
             _att_backward(st, level, gs.data_ptr(), d)
             datts[i] = d
-        return (dlog.permute(0, 4, 1, 2, 3), None, None, None, None, *datts)
+        return (dlog.permute(0, 4, 1, 2, 3), None, None, None, None, None, *datts)
 
 
 class Dice_spvPA(_Loss):
     def __init__(self, include_background: bool = True, to_onehot_y: bool = False, sigmoid: bool = False, softmax: bool = False, other_act=None, squared_pred: bool = False,
-                 jaccard: bool = False, reduction="mean", supervised_attention=True, hardness_weighting=True, ce_weight: float = 0.0, ce_foreground_weight: float = 1.0) -> None:
+                 jaccard: bool = False, reduction="mean", supervised_attention=True, hardness_weighting=True, ce_weight: float = 0.0, ce_foreground_weight: float = 1.0,
+                 ce_topk: float = 0.0) -> None:
         super().__init__(reduction=getattr(reduction, "value", reduction))
         if other_act is not None and not callable(other_act):
             raise TypeError(f"other_act must be None or callable but is {type(other_act).__name__}.")
         if int(sigmoid) + int(softmax) + int(other_act is not None) > 1:
             raise ValueError("Incompatible values: more than 1 of [sigmoid=True, softmax=True, other_act is not None].")
         self.ce_weight, self.ce_foreground_weight = check_ce(ce_weight, ce_foreground_weight)  # beyond the reference: + ce_weight * cross-entropy on the final logits
+        self.ce_topk = check_ce_topk(ce_topk, self.ce_weight)  # ... over the hardest ce_topk percent of the voxels only (0: over all of them)
+        self.topk_record = None  # with ce_topk: the select's record of the last call (device tensor of four int64: threshold_bits | passes_done << 32, n_gt, n_eq, K)
         # the reference's Dice_spvPA.forward ignores every option except the two below (it builds its inner Dice objects with fixed options)
         self.include_background, self.to_onehot_y, self.sigmoid, self.softmax = include_background, to_onehot_y, sigmoid, softmax
         self.other_act, self.squared_pred, self.jaccard = other_act, squared_pred, jaccard
@@ -211,7 +248,7 @@ class Dice_spvPA(_Loss):
         if smooth != 1e-5:
             raise NotImplementedError("smooth is fixed at 1e-5 (the value the reference always uses)")
         atts: Sequence[torch.Tensor] = list(att_maps) if self.supervised_attention else []
-        return _DiceFn.apply(x, target, bool(self.supervised_attention), bool(self.hardness_weighting), (self.ce_weight, self.ce_foreground_weight), *atts)
+        return _DiceFn.apply(x, target, bool(self.supervised_attention), bool(self.hardness_weighting), (self.ce_weight, self.ce_foreground_weight, self.ce_topk), self, *atts)
 
     def forward_backward_into(self, input, target: torch.Tensor, landing):
         """The loss AND its gradients in one call, outside autograd (the fused train step of vs_seg_amd.parallel.DataParallelTrainer): d(loss)/d(logits) and
@@ -225,11 +262,14 @@ class Dice_spvPA(_Loss):
         atts: Sequence[torch.Tensor] = list(att_maps) if self.supervised_attention else []
         glogits_dst, gatt_bufs = landing
         with torch.no_grad():
-            st = _dice_forward(x, target, bool(self.supervised_attention), bool(self.hardness_weighting), atts, (self.ce_weight, self.ce_foreground_weight))
+            st = _dice_forward(x, target, bool(self.supervised_attention), bool(self.hardness_weighting), atts, (self.ce_weight, self.ce_foreground_weight), self.ce_topk)
+            self.topk_record = st.topk_rec
             B, X, Y, Z = st.shape
             stream = torch.cuda.current_stream().cuda_stream
             if st.ce_coef is None:
                 L.check(L.lib().vsseg_dice_pred_bwd_to(st.lg.data_ptr(), 2, st.lab.data_ptr(), B, X * Y * Z, st.hardness, st.coef.data_ptr(), None, glogits_dst, stream), "dice_pred_bwd_to")
+            elif st.topk:
+                L.check(L.lib().vsseg_dice_ce_topk_pred_bwd_to(st.lg.data_ptr(), 2, st.lab.data_ptr(), B, X * Y * Z, st.hardness, st.coef.data_ptr(), st.ce_coef.data_ptr(), None, glogits_dst, stream), "dice_ce_topk_pred_bwd_to")
             else:
                 L.check(L.lib().vsseg_dice_ce_pred_bwd_to(st.lg.data_ptr(), 2, st.lab.data_ptr(), B, X * Y * Z, st.hardness, st.coef.data_ptr(), st.ce_coef.data_ptr(), None, glogits_dst, stream), "dice_ce_pred_bwd_to")
             written, coarse = [], []
