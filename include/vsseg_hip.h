@@ -665,6 +665,32 @@ int vsseg_components_label(const float* logits, int32_t pitch, const int32_t dim
 int vsseg_keep_largest_component(const float* logits, int32_t pitch, const int32_t dims[3], int32_t connectivity, void* scratch, int64_t scratch_bytes, float* out,
                                  int64_t* stats /* may be NULL */, void* stream);
 
+/* Size and position of the argmax prediction P = (logits[v][1] > logits[v][0]) (the rule of vsseg_argmax2: ties and NaN are background) and of the label
+   G = ((int)label[v] == 1) (the rule of vsseg_hard_dice_counts) (ABI version 17; beyond the reference, which reports the hard Dice only).  One volume [X][Y][Z] per call:
+   logits [X][Y][Z][2] fp32 (pitch 2, 8-byte aligned), label [X][Y][Z] fp32 or NULL, spacing = mm per voxel along x, y, z.  out: nine fp64 in device memory (8-byte aligned):
+     [0], [1]  voxels_pred, voxels_label              |P|, |G|: exact integers
+     [2], [3]  volume_pred_mm3, volume_label_mm3      count * (sx * sy * sz), the product formed in fp64 from the fp32 spacing
+     [4]       centroid_distance_mm                   Euclidean distance between the two centres of mass (fp64, from exact integer sums of the voxel indices); NaN when
+                                                      either mask is empty
+     [5], [6]  max_diameter_pred_mm, _label_mm        the largest distance between the centres of two voxels of the mask (the 3-D Feret diameter; pyradiomics'
+                                                      Maximum3DDiameter taken between voxel centres); a single voxel: 0, an empty mask: NaN
+     [7], [8]  max_axial_diameter_pred_mm, _label_mm  the same over pairs of voxels with equal z: the largest in-plane diameter over the axial slices; a single voxel: 0,
+                                                      an empty mask: NaN
+   label == NULL: every label field and [4] are NaN.  The squared distance of a pair, (sx dx)^2 + (sy dy)^2 + (sz dz)^2, is formed in fp32 from exact integer differences
+   (FMA contraction allowed: a relative error of a few 2^-24; exact at unit spacing and extents below 2048); the maximum is taken over the fp32 values and its square root
+   once, in fp64.  The farthest pair is searched among the two x extremes of every (y, z) column of the mask (with dy and dz fixed a pair whose x extent can grow is not
+   the farthest), restricted to the mask's (y, z) bounding box; that search is quadratic in the occupied columns, hence the
+   domain: dims 1 .. 8192 on every axis and Y * Z <= 2^18 (512 x 512 in-plane in any orientation); anything else returns VSSEG_EINVAL with a message that names dims.
+   A sequence of launches on `stream` (init, one streaming pass of 12 B per voxel - 8 B without a label -, the pair stage, finalize) without host synchronisation or
+   allocation; no kernel waits for another workgroup and the grids depend on dims alone.  Only integer atomics (64-bit sums, min / max of indices and of the bit patterns
+   of non-negative floats) combine workgroups, so a call is bit-identical from run to run.  scratch: device memory of vsseg_measure_scratch_bytes(dims) bytes (a record
+   and 16 B per (y, z) column), 256-byte aligned, overwritten (a call on another stream needs its own).
+   Argument checks, before anything is launched: logits / spacing / scratch / out not null, alignment, pitch == 2, dims in the domain, spacing positive and finite,
+   scratch_bytes large enough. */
+int64_t vsseg_measure_scratch_bytes(const int32_t dims[3]); /* bytes of scratch, or VSSEG_EINVAL */
+int vsseg_measurements(const float* logits, int32_t pitch, const float* label /* may be NULL */, const int32_t dims[3], const float spacing[3], void* scratch,
+                       int64_t scratch_bytes, double* out /* 9 fp64, device */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

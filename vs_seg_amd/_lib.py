@@ -238,6 +238,7 @@ SYMBOLS = [
     "vsseg_adam", "vsseg_swi_accumulate", "vsseg_swi_finalize", "vsseg_swi_finalize_mirrored", "vsseg_hard_dice_counts", "vsseg_argmax2",
     "vsseg_surface_scratch_bytes", "vsseg_surface_distances",
     "vsseg_components_scratch_bytes", "vsseg_components_label", "vsseg_keep_largest_component",
+    "vsseg_measure_scratch_bytes", "vsseg_measurements",
     "vsseg_grad_norm_scratch_bytes", "vsseg_grad_norm", "vsseg_sgd", "vsseg_adam_clipped",
     "vsseg_topk_scratch_bytes", "vsseg_topk_select", "vsseg_ce_topk_select", "vsseg_dice_ce_topk_finalize", "vsseg_dice_ce_topk_pred_bwd", "vsseg_dice_ce_topk_pred_bwd_to",
 ]  # fmt: skip
@@ -330,6 +331,8 @@ def lib():
         L.vsseg_components_scratch_bytes.argtypes, L.vsseg_components_scratch_bytes.restype = [I3], i64
         L.vsseg_components_label.argtypes = [vp, i32, I3, i32, vp, i64, vp, vp, vp]
         L.vsseg_keep_largest_component.argtypes = [vp, i32, I3, i32, vp, i64, vp, vp, vp]
+        L.vsseg_measure_scratch_bytes.argtypes, L.vsseg_measure_scratch_bytes.restype = [I3], i64
+        L.vsseg_measurements.argtypes = [vp, i32, vp, I3, C.POINTER(C.c_float), vp, i64, vp, vp]
         L.vsseg_grad_norm_scratch_bytes.argtypes, L.vsseg_grad_norm_scratch_bytes.restype = [i64], i64
         L.vsseg_grad_norm.argtypes = [vp, i64, f32, f64, vp, i64, vp, vp]
         L.vsseg_sgd.argtypes = [vp, vp, vp, i64, f32, f32, f32, i32, f32, vp, vp]

@@ -19,6 +19,10 @@ from . import _lib as L
 from .inferers import _as_cl
 
 _SCRATCH_CACHE: Dict[tuple, torch.Tensor] = {}  # (device, dims, stream) -> scratch of vsseg_surface_distances
+_MEASURE_SCRATCH_CACHE: Dict[tuple, torch.Tensor] = {}  # ... of vsseg_measurements
+
+MEASUREMENT_FIELDS = ("voxels_pred", "voxels_label", "volume_pred_mm3", "volume_label_mm3", "centroid_distance_mm", "max_diameter_pred_mm", "max_diameter_label_mm",
+                      "max_axial_diameter_pred_mm", "max_axial_diameter_label_mm")  # the nine outputs of vsseg_measurements, in order
 
 
 def voxel_spacing(affine) -> Tuple[float, float, float]:
@@ -29,18 +33,30 @@ def voxel_spacing(affine) -> Tuple[float, float, float]:
     return tuple(float(v) for v in np.linalg.norm(a[:3, :3], axis=0))
 
 
-def _scratch(device, dims, stream) -> torch.Tensor:
+def _scratch(device, dims, stream, cache=_SCRATCH_CACHE, what="surface_scratch_bytes") -> torch.Tensor:
     key = (str(device), tuple(dims), stream)
-    buf = _SCRATCH_CACHE.get(key)
+    buf = cache.get(key)
     if buf is None:
-        nbytes = int(L.lib().vsseg_surface_scratch_bytes(L.i3(dims)))
+        nbytes = int(getattr(L.lib(), "vsseg_" + what)(L.i3(dims)))
         if nbytes < 0:
-            L.check(nbytes, "surface_scratch_bytes")
-        while len(_SCRATCH_CACHE) >= 4:
-            _SCRATCH_CACHE.pop(next(iter(_SCRATCH_CACHE)))
+            L.check(nbytes, what)
+        while len(cache) >= 4:
+            cache.pop(next(iter(cache)))
         buf = torch.empty(nbytes, dtype=torch.uint8, device=device)  # (the caching allocator's blocks are 512-byte aligned)
-        _SCRATCH_CACHE[key] = buf
+        cache[key] = buf
     return buf
+
+
+def _spacing3(spacing) -> Tuple[float, float, float]:
+    if spacing is None:
+        return (1.0, 1.0, 1.0)
+    try:
+        spacing = tuple(float(s) for s in spacing)
+    except (TypeError, ValueError):
+        raise ValueError(f"spacing must be three positive numbers (mm) or None, got {spacing!r}") from None
+    if len(spacing) != 3 or not all(math.isfinite(s) and s > 0 for s in spacing):
+        raise ValueError(f"spacing must be three positive finite numbers (mm) or None, got {spacing!r}")
+    return spacing
 
 
 def compute_surface_distances(predicted_probabilities: torch.Tensor, label: torch.Tensor, spacing: Optional[Sequence[float]] = None,
@@ -56,14 +72,7 @@ def compute_surface_distances(predicted_probabilities: torch.Tensor, label: torc
         raise ValueError(f"percentile must be a number in [0, 100] or None, got {percentile!r}") from None
     if not 0.0 <= percentile <= 100.0:
         raise ValueError(f"percentile must be in [0, 100], got {percentile}")
-    if spacing is None:
-        spacing = (1.0, 1.0, 1.0)
-    try:
-        spacing = tuple(float(s) for s in spacing)
-    except (TypeError, ValueError):
-        raise ValueError(f"spacing must be three positive numbers (mm) or None, got {spacing!r}") from None
-    if len(spacing) != 3 or not all(math.isfinite(s) and s > 0 for s in spacing):
-        raise ValueError(f"spacing must be three positive finite numbers (mm) or None, got {spacing!r}")
+    spacing = _spacing3(spacing)
     if predicted_probabilities.dim() != 5 or predicted_probabilities.shape[1] != 2:
         raise ValueError(f"expected predicted_probabilities [B,2,X,Y,Z], got {tuple(predicted_probabilities.shape)}")
     B, _, X, Y, Z = predicted_probabilities.shape
@@ -87,4 +96,40 @@ def compute_surface_distances(predicted_probabilities: torch.Tensor, label: torc
     for b in range(B):
         L.check(lib.vsseg_surface_distances(lg.data_ptr() + 8 * b * nv, 2, lab.data_ptr() + 4 * b * nv, L.i3(dims), sp, percentile, scratch.data_ptr(), scratch.numel(),
                                             out.data_ptr() + 8 * b, stream), "surface_distances")
+    return out
+
+
+def compute_measurements(predicted_probabilities: torch.Tensor, label: Optional[torch.Tensor] = None, spacing: Optional[Sequence[float]] = None) -> torch.Tensor:
+    """[B,9] fp64 on the device, the columns named by MEASUREMENT_FIELDS: voxel counts, volumes (mm^3), the distance between the centres of mass, the
+    largest 3-D diameter and the largest diameter within an axial (equal z) slice, each of the argmax prediction and of the label, for voxel extents
+    `spacing` (x, y, z in mm; None: voxel units).  `predicted_probabilities` [B,2,X,Y,Z] logits or probabilities in any layout, `label` [B,1,X,Y,Z] or
+    None (the label columns and the centroid distance are then NaN).  Empty mask: its diameters and the centroid distance are NaN.  Y * Z <= 2^18.
+    No host synchronisation (vsseg_measurements, csrc/measure.hip)."""
+    spacing = _spacing3(spacing)
+    if predicted_probabilities.dim() != 5 or predicted_probabilities.shape[1] != 2:
+        raise ValueError(f"expected predicted_probabilities [B,2,X,Y,Z], got {tuple(predicted_probabilities.shape)}")
+    B, _, X, Y, Z = predicted_probabilities.shape
+    if label is not None and tuple(label.shape) != (B, 1, X, Y, Z):
+        raise ValueError(f"expected label [B,1,X,Y,Z] = {(B, 1, X, Y, Z)}, got {tuple(label.shape)}")
+    if not (predicted_probabilities.is_cuda and (label is None or label.is_cuda)):
+        raise RuntimeError("vs_seg_amd.compute_measurements runs on an MI355X only; there is no CPU fallback")
+    if label is not None and label.device != predicted_probabilities.device:
+        raise ValueError(f"predicted_probabilities on {predicted_probabilities.device}, label on {label.device}")
+    lib = L.lib()
+    stream = torch.cuda.current_stream(predicted_probabilities.device).cuda_stream
+    lg = _as_cl(predicted_probabilities)  # [B,X,Y,Z,2] fp32
+    lab = None
+    if label is not None:
+        lab = label.detach()
+        if lab.dtype != torch.float32 or not lab.is_contiguous():
+            lab = lab.to(torch.float32).contiguous()
+    dims = (int(X), int(Y), int(Z))
+    nv = dims[0] * dims[1] * dims[2]
+    scratch = _scratch(lg.device, dims, stream, _MEASURE_SCRATCH_CACHE, "measure_scratch_bytes")
+    sp = (ctypes.c_float * 3)(*spacing)
+    n = len(MEASUREMENT_FIELDS)
+    out = torch.empty((B, n), dtype=torch.float64, device=lg.device)
+    for b in range(B):
+        L.check(lib.vsseg_measurements(lg.data_ptr() + 8 * b * nv, 2, None if lab is None else lab.data_ptr() + 4 * b * nv, L.i3(dims), sp, scratch.data_ptr(), scratch.numel(),
+                                       out.data_ptr() + 8 * n * b, stream), "measurements")
     return out

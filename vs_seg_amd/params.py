@@ -29,7 +29,7 @@ import torch
 from . import SGD, Adam, AdamW, Dice_spvPA, UNet2d5_spvPA, check_ce, check_ce_topk, check_optimizer, compute_dice_score, poly_lr, sliding_window_inference
 from .optim import DEFAULT_WEIGHT_DECAY, LR_SCHEDULES, OPTIMIZERS
 from .inferers import argmax_segmentation, tta_masks
-from .metrics import compute_surface_distances, voxel_spacing
+from .metrics import MEASUREMENT_FIELDS, compute_measurements, compute_surface_distances, voxel_spacing
 from .postprocess import keep_largest_component
 from . import parallel as DP
 from .data import nifti
@@ -96,6 +96,7 @@ class VSparams:
         parser.add_argument("--num_epochs", type=int, default=None)
         parser.add_argument("--surface_metrics", action="store_true", help="run_inference also reports HD95 and ASSD per test case (mm, on the GPU) and writes figures/test_surface_metrics.csv")
         parser.add_argument("--keep_largest_component", action="store_true", help="run_inference keeps only the largest connected component of each predicted segmentation (on the GPU) before the Dice, the surface metrics and the NIfTI export, and writes figures/test_postprocessing.csv")
+        parser.add_argument("--measurements", action="store_true", help="run_inference also reports per test case the volume (mm^3), the largest 3-D diameter and the largest diameter within an axial slice (mm) of the predicted and of the manual segmentation and the distance between their centres of mass (on the GPU), and writes figures/test_measurements.csv")
         parser.add_argument("--component_connectivity", type=int, default=26, choices=[6, 18, 26], help="voxel connectivity of --keep_largest_component (26: MONAI's KeepLargestConnectedComponent)")
         parser.add_argument("--tta_flips", type=int, nargs="*", choices=[0, 1, 2], default=None, metavar="AXIS", help="run_inference predicts every case on mirrored copies as well (spatial axes 0 1 2 = X Y Z: one pass per subset of the given axes) and averages the un-mirrored predictions; training mirrors axis 0")
         parser.add_argument("--tta_average", type=str, default="logits", choices=["logits", "probabilities"], help="what --tta_flips averages: the blended logits, or their softmax over the classes (nnU-Net)")
@@ -155,6 +156,7 @@ class VSparams:
         self.export_inferred_segmentations = True
         self.compute_dtype = args.compute_dtype
         self.surface_metrics = args.surface_metrics
+        self.measurements = args.measurements
         self.keep_largest_component, self.component_connectivity = args.keep_largest_component, args.component_connectivity
         self.tta_flips, self.tta_average = tuple(args.tta_flips or ()), args.tta_average
         self.aug_rotate_deg, self.aug_scale, self.aug_intensity_scale, self.aug_intensity_shift, self.aug_noise_std = (augment[k] for k in AUGMENT_KEYS)
@@ -194,7 +196,7 @@ class VSparams:
         log("Parameters: ")
         for k in ("dataset", "data_root", "split_csv", "pad_crop_shape", "pad_crop_shape_test", "num_workers", "torch_device_arg", "train_batch_size", "initial_learning_rate",
                   "epochs_with_const_lr", "lr_divisor", "weight_decay", "num_epochs", "val_interval", "model", "sliding_window_inferer_roi_size", "attention", "hardness",
-                  "results_folder_path", "export_inferred_segmentations", "compute_dtype") + (("surface_metrics",) if self.surface_metrics else ()) + (
+                  "results_folder_path", "export_inferred_segmentations", "compute_dtype") + (("surface_metrics",) if self.surface_metrics else ()) + (("measurements",) if self.measurements else ()) + (
                       ("keep_largest_component", "component_connectivity") if self.keep_largest_component else ()) + (("tta_flips", "tta_average") if self.tta_flips else ()) + (
                           tuple("aug_" + k for k in AUGMENT_KEYS) if any(self.augment.values()) else ()) + (
                               ("aug_elastic_mag", "aug_bias_field", "aug_field_spacing") if self.aug_elastic_mag or self.aug_bias_field else ()) + (
@@ -445,6 +447,7 @@ class VSparams:
         surf_dev = torch.zeros((2, n), dtype=torch.float32, device=self.device) if self.surface_metrics else None  # [hd95, assd] per case, mm
         # --keep_largest_component: [raw Dice, foreground voxels, components, kept voxels] per case (fp64: the voxel counts of a full volume are not exact in fp32)
         post_dev = torch.zeros((4, n), dtype=torch.float64, device=self.device) if self.keep_largest_component else None
+        meas_dev = torch.zeros((len(MEASUREMENT_FIELDS), n), dtype=torch.float64, device=self.device) if self.measurements else None  # --measurements: the nine values per case
         predictor = model.segmentation_predictor() if hasattr(model, "segmentation_predictor") else (lambda *a, **k: model(*a, **k)[0])  # model_segmentation, ref:params/VSparams.py:560
         mine = DP.shard_indices(n)  # the unpadded, unshuffled test loader yields exactly these cases, in this order
         with torch.no_grad():
@@ -461,16 +464,20 @@ class VSparams:
                 dice_dev[gi] = self.compute_dice_score(outputs, data["label"]).reshape(())
                 if surf_dev is not None:
                     surf_dev[:, gi] = compute_surface_distances(outputs, data["label"], voxel_spacing(data["label_meta_dict"]["affine"]), 95.0)[0]
+                if meas_dev is not None:
+                    meas_dev[:, gi] = compute_measurements(outputs, data["label"], voxel_spacing(data["label_meta_dict"]["affine"]))[0]
                 if self.export_inferred_segmentations:
                     self.export_segmentation(outputs, data["label_meta_dict"])
-        surf = post = None
-        if surf_dev is not None or post_dev is not None:
-            rows = [dice_dev[None]] + ([surf_dev] if surf_dev is not None else []) + ([post_dev] if post_dev is not None else [])
+        surf = post = meas = None
+        if surf_dev is not None or post_dev is not None or meas_dev is not None:
+            rows = [dice_dev[None]] + [r for r in (surf_dev, post_dev, meas_dev) if r is not None]
             both = torch.cat(rows)  # one all-reduce; a case that is not this rank's is 0 here (NaN / inf + 0 stay NaN / inf)
             both = (DP.allreduce_sum(both) if self.world > 1 else both).double().cpu().numpy()
             dice_scores = both[0]
             if surf_dev is not None:
                 surf = both[1:3]
+            if meas_dev is not None:
+                both, meas = both[:-len(MEASUREMENT_FIELDS)], both[-len(MEASUREMENT_FIELDS):]
             if post_dev is not None:
                 post = both[-4:]
         else:
@@ -483,6 +490,8 @@ class VSparams:
             self._log_postprocessing(dice_scores, *post)
         if surf is not None:
             self._log_surface_metrics(dice_scores, surf[0], surf[1])
+        if meas is not None:
+            self._log_measurements(dice_scores, meas)
         return dice_scores
 
     def _log_postprocessing(self, dice, dice_raw, foreground, components, kept):
@@ -516,6 +525,33 @@ class VSparams:
                 f.write("case,dice,hd95_mm,assd_mm\n")
                 for i, (d, h, a) in enumerate(zip(dice, hd95, assd)):
                     f.write(f"{i},{float(d)!r},{float(h)!r},{float(a)!r}\n")
+
+    def _log_measurements(self, dice, meas):
+        """Per-case volume / centroid / diameter lines of --measurements, the volume and diameter errors over the cases, and figures/test_measurements.csv (rank 0)."""
+        log = self.logger.info
+        m = dict(zip(MEASUREMENT_FIELDS, meas))
+        n = len(dice)
+        vol_err = m["volume_pred_mm3"] - m["volume_label_mm3"]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rel_err = np.where(m["voxels_label"] > 0, np.abs(vol_err) / m["volume_label_mm3"], np.nan)  # NaN: the label is empty
+        for i in range(n):
+            for name in ("volume_pred_mm3", "volume_label_mm3"):
+                log(f"{name}[{i}] = {m[name][i]}")
+            log(f"volume_error_mm3[{i}] = {vol_err[i]}")
+            for name in MEASUREMENT_FIELDS[4:]:
+                log(f"{name}[{i}] = {m[name][i]}")
+        diffs = [("mean_abs_volume_error_mm3", np.abs(vol_err), "non-finite"), ("mean_rel_volume_error", rel_err, "with an empty label")] + [
+            (f"mean_abs_{d}_error_mm", np.abs(m[f"{d}_pred_mm"] - m[f"{d}_label_mm"]), "with an empty mask") for d in ("max_diameter", "max_axial_diameter")]
+        for name, v, why in diffs:
+            fin = v[np.isfinite(v)]
+            mean, sd = (fin.mean(), fin.std()) if len(fin) else (float("nan"), float("nan"))
+            log(f"{name} = {mean} +- {sd} ({n - len(fin)} of {n} cases {why} left out)")
+        if self.rank == 0:
+            os.makedirs(self.figures_path, exist_ok=True)
+            with open(os.path.join(self.figures_path, "test_measurements.csv"), "w") as f:
+                f.write("case,dice," + ",".join(MEASUREMENT_FIELDS) + ",volume_error_mm3,volume_rel_error\n")
+                for i in range(n):
+                    f.write(",".join([str(i), repr(float(dice[i]))] + [repr(float(m[k][i])) for k in MEASUREMENT_FIELDS] + [repr(float(vol_err[i])), repr(float(rel_err[i]))]) + "\n")
 
     def export_segmentation(self, outputs, label_meta):
         """N3: argmax → uint8 NIfTI in the label's original orientation / affine, under
