@@ -6,6 +6,8 @@
 `--surface_metrics` also reports HD95 and ASSD (mm) per test case, computed on the GPU, and writes figures/test_surface_metrics.csv.
 `--keep_largest_component [--component_connectivity 26]` keeps only the largest connected component of each predicted segmentation (on the GPU) before
 the Dice, the surface metrics and the NIfTI export; the raw Dice and the component counts go to the log and figures/test_postprocessing.csv.
+`--fill_holes [--hole_connectivity 6]` fills the holes of each predicted segmentation and `--min_component_mm3 V` drops its connected components below
+V cubic millimetres (both on the GPU, in this order, before --keep_largest_component); their counts are added to the same log and CSV.
 `--measurements` also reports per test case the volume (mm^3), the largest 3-D diameter and the largest diameter within an axial slice (mm) of the
 predicted and of the manual segmentation and the distance between their centres of mass, computed on the GPU (after --keep_largest_component and
 --tta_flips, when given), the volume and diameter errors over the cases, and writes figures/test_measurements.csv.

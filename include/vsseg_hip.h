@@ -665,6 +665,26 @@ int vsseg_components_label(const float* logits, int32_t pitch, const int32_t dim
 int vsseg_keep_largest_component(const float* logits, int32_t pitch, const int32_t dims[3], int32_t connectivity, void* scratch, int64_t scratch_bytes, float* out,
                                  int64_t* stats /* may be NULL */, void* stream);
 
+/* Two more post-transforms on the same foreground, connectivities, domain, scratch (vsseg_components_scratch_bytes) and output format as vsseg_keep_largest_component
+   (ABI version 18; MONAI's FillHoles and RemoveSmallObjects).  out: fp32 [X][Y][Z][2] (8-byte aligned), channel 1 = 1.0 on the result and 0.0 elsewhere, channel 0 =
+   1 - channel 1; logits are never written; stats: four int64 in device memory (8-byte aligned), may be NULL.
+   vsseg_fill_holes: the result is P united with H, the union of the connected components of the COMPLEMENT of P (at `connectivity`, that of the background; 6 is
+   scipy.ndimage.binary_fill_holes' default and the dual of a 26-connected foreground, 26 is what MONAI's FillHoles uses) that contain no voxel on the border of the volume
+   (a voxel with an index equal to 0 or to dim - 1).  A volume with an extent of 1 or 2 along an axis has no holes; a tunnel through a ring is not a hole; an empty P
+   gives an empty result.  stats: [0] |P|, [1] number of holes, [2] |H|, [3] |P| + |H|.  Launches: init, one pass that reads the logits and leaves |P| and the bounding
+   box of P (8 B per voxel), the tile labelling / merge / flatten of the components above on the complement of P inside that box only, a count, and one pass that writes
+   the result (8 B per voxel).  A background component of the box without a voxel on a face of the box is a hole, every other one is not (components.hip states why).
+   vsseg_remove_small_components: the result is the union of the components of P (at `connectivity`) with at least min_voxels voxels (strictly smaller ones are
+   removed: skimage.morphology.remove_small_objects' rule); min_voxels <= 1 keeps P; min_voxels is a host argument, nothing is read back.  stats: [0] |P|, [1] number
+   of components of P, [2] kept voxels, [3] kept components.  The launches of vsseg_keep_largest_component with its selection replaced by a count.
+   Both: a sequence of launches on `stream` without host synchronisation or allocation, bit-identical from run to run (only integer atomics decide anything), no kernel
+   waits for another workgroup.  Argument checks, before anything is launched: logits / scratch / out not null, alignment (logits, out, stats 8 B, scratch 256 B),
+   pitch == 2, dims in the domain, connectivity 6 / 18 / 26, min_voxels >= 0, scratch_bytes large enough. */
+int vsseg_fill_holes(const float* logits, int32_t pitch, const int32_t dims[3], int32_t connectivity, void* scratch, int64_t scratch_bytes, float* out,
+                     int64_t* stats /* may be NULL */, void* stream);
+int vsseg_remove_small_components(const float* logits, int32_t pitch, const int32_t dims[3], int32_t connectivity, int64_t min_voxels, void* scratch, int64_t scratch_bytes,
+                                  float* out, int64_t* stats /* may be NULL */, void* stream);
+
 /* Size and position of the argmax prediction P = (logits[v][1] > logits[v][0]) (the rule of vsseg_argmax2: ties and NaN are background) and of the label
    G = ((int)label[v] == 1) (the rule of vsseg_hard_dice_counts) (ABI version 17; beyond the reference, which reports the hard Dice only).  One volume [X][Y][Z] per call:
    logits [X][Y][Z][2] fp32 (pitch 2, 8-byte aligned), label [X][Y][Z] fp32 or NULL, spacing = mm per voxel along x, y, z.  out: nine fp64 in device memory (8-byte aligned):

@@ -20,6 +20,15 @@
 // merge .. select run on grids sized for the volume; workgroups whose tile misses the bounding box (which lives in device memory) exit at once.  No kernel waits for
 // another workgroup: every loop either walks parent links towards strictly smaller indices or retries an atomicMin with a strictly smaller operand.  Only integer
 // atomics decide anything, so the result is a function of the mask alone.
+//
+// Two more routes through the same passes, with the same two properties (vsseg_remove_small_components, vsseg_fill_holes):
+//   remove small  init, local, merge, flatten, sizes as above; `count` (for `select`): the roots, and those with cnt[root] >= min_voxels with their voxels;
+//                 `write`: one-hot of cnt[root] >= min_voxels.  min_voxels is a kernel argument.
+//   fill holes    init; `scan`: the logits of the whole volume once (8 B per voxel), leaving |P| and the bounding box of P; then local (on the COMPLEMENT of P inside
+//                 the box, the logits of the box read again), merge and a flatten that also marks the roots with a voxel on a face of the box, all confined to the
+//                 box; `count`: unmarked roots (holes) and their voxels; `write`: one-hot of P or unmarked, 8 B per voxel.  Why the box suffices: above fh_scan_kernel.
+//                 Background comes as whole rows, so this route's local pass labels a tile of 32 equal single-run rows without a union, and its merge pass makes
+//                 one union per lane and neighbour tile, not one per row (cc_unite); neither changes a label.
 #include <limits.h>
 #include "common.h"
 
@@ -34,6 +43,7 @@ struct CompRec {
   unsigned long long best;  // max over roots of (size << 32) | (0xFFFFFFFF - label); 0: P is empty
   unsigned ncomp;           // number of roots
   int bmin[3], bmax[3];     // bounding box of P; bmax = -1: empty
+  unsigned nkept;           // remove_small: the roots that pass the threshold (best: their voxels); fill_holes: ncomp = holes, best = |H|
 };
 
 struct CompLayout {
@@ -100,6 +110,7 @@ __global__ __launch_bounds__(256) void cc_init_kernel(CompRec* rec) {
     rec->fg = 0;
     rec->best = 0;
     rec->ncomp = 0;
+    rec->nkept = 0;
   }
   if (threadIdx.x < 3) {
     rec->bmin[threadIdx.x] = INT_MAX;
@@ -107,24 +118,38 @@ __global__ __launch_bounds__(256) void cc_init_kernel(CompRec* rec) {
   }
 }
 
-__global__ __launch_bounds__(256) void cc_local_kernel(const float* __restrict__ logits, int X, int Y, int Z, int conn, int* __restrict__ parent, CompRec* __restrict__ rec) {
+// HOLES: the mask is the COMPLEMENT of P inside the bounding box of P, which an earlier pass (fh_scan_kernel) has left in the record: background voxels of the box get
+// a parent and a zeroed mark in cnt, everything else of the tile -1.  Tiles within one voxel of the box are written too (all -1 when they miss the box itself), so
+// that the merge pass, which looks one voxel beyond the voxels it unites, reads nothing that this launch has not written; other tiles exit at once.
+template <bool HOLES>
+__global__ __launch_bounds__(256) void cc_local_kernel(const float* __restrict__ logits, int X, int Y, int Z, int conn, int* __restrict__ parent, unsigned* __restrict__ cnt,
+                                                      CompRec* __restrict__ rec) {
   __shared__ unsigned long long rowmask[CT_ROWS];
   __shared__ int L[CT_ROWS * CT_Z];
   const int z0 = blockIdx.x * CT_Z, y0 = blockIdx.y * CT_Y, x0 = blockIdx.z * CT_X;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int z = z0 + lane;
+  int b0x = 0, b0y = 0, b0z = 0, b1x = 0, b1y = 0, b1z = 0;
+  if constexpr (HOLES) {
+    b0x = rec->bmin[0], b0y = rec->bmin[1], b0z = rec->bmin[2], b1x = rec->bmax[0], b1y = rec->bmax[1], b1z = rec->bmax[2];
+    // (an empty P has bmin = INT_MAX: every tile leaves here)
+    if (b1x + 1 < x0 || b0x - 1 >= x0 + CT_X || b1y + 1 < y0 || b0y - 1 >= y0 + CT_Y || b1z + 1 < z0 || b0z - 1 >= z0 + CT_Z) return;
+  }
   float2 lg[CT_ROWS / 4];
+  bool in[CT_ROWS / 4];  // HOLES: the voxel lies in the volume and in the box
 #pragma unroll
   for (int k = 0; k < CT_ROWS / 4; ++k) {
     const int r = k * 4 + wave, x = x0 + (r >> 3), y = y0 + (r & 7);
     lg[k] = make_float2(0.f, 0.f);
-    if (x < X && y < Y && z < Z) lg[k] = *reinterpret_cast<const float2*>(logits + 2 * (((int64_t)x * Y + y) * Z + z));
+    in[k] = x < X && y < Y && z < Z;
+    if constexpr (HOLES) in[k] = in[k] && x >= b0x && x <= b1x && y >= b0y && y <= b1y && z >= b0z && z <= b1z;
+    if (in[k]) lg[k] = *reinterpret_cast<const float2*>(logits + 2 * (((int64_t)x * Y + y) * Z + z));
   }
   bool any = false;
 #pragma unroll
   for (int k = 0; k < CT_ROWS / 4; ++k) {
     const int r = k * 4 + wave;
-    const bool m = lg[k].y > lg[k].x;
+    const bool m = HOLES ? in[k] && !(lg[k].y > lg[k].x) : lg[k].y > lg[k].x;
     const unsigned long long bits = __ballot(m);
     if (lane == 0) rowmask[r] = bits;
     const unsigned long long gaps = ~bits & ((1ull << lane) - 1ull);  // background voxels below this one: the run starts behind the highest of them
@@ -138,6 +163,25 @@ __global__ __launch_bounds__(256) void cc_local_kernel(const float* __restrict__
       if (x < X && y < Y && z < Z) parent[((int64_t)x * Y + y) * Z + z] = -1;
     }
     return;
+  }
+  if constexpr (HOLES) {
+    // Background is mostly whole rows.  A tile whose 32 rows all hold the same single run is one component at every connectivity (every row touches the next one
+    // head-on): its root is the first voxel of row 0, and there is nothing to unite.  (The general path would make all of these unions in lane 0, one after another.)
+    const unsigned long long m0 = rowmask[0];
+    const bool one_run = m0 != 0 && ((m0 + (m0 & (~m0 + 1ull))) & m0) == 0;
+    if (one_run && __all(rowmask[lane & (CT_ROWS - 1)] == m0)) {  // (the same in every wave: the barrier above has published the masks)
+      const int root = (int)((((int64_t)x0) * Y + y0) * Z + z0 + __builtin_ctzll(m0));
+#pragma unroll
+      for (int k = 0; k < CT_ROWS / 4; ++k) {
+        const int r = k * 4 + wave, x = x0 + (r >> 3), y = y0 + (r & 7);
+        if (x >= X || y >= Y || z >= Z) continue;  // (no row of such a tile lies outside the volume, but its z range may)
+        const int64_t v = ((int64_t)x * Y + y) * Z + z;
+        const bool m = cc_bit(m0, lane);
+        parent[v] = m ? root : -1;
+        if (m) cnt[v] = 0;
+      }
+      return;
+    }
   }
   for (int k = 0; k < CT_ROWS / 4; ++k) {
     const int r = k * 4 + wave, lx = r >> 3, ly = r & 7;
@@ -169,7 +213,10 @@ __global__ __launch_bounds__(256) void cc_local_kernel(const float* __restrict__
       p = (int)((((int64_t)(x0 + (root >> 9))) * Y + (y0 + ((root >> 6) & 7))) * Z + z0 + (root & 63));
     }
     parent[((int64_t)x * Y + y) * Z + z] = p;
+    if constexpr (HOLES)
+      if (p >= 0) cnt[((int64_t)x * Y + y) * Z + z] = 0;  // the mark of a root that touches a face of the box (fh_flatten_kernel); only a root's is ever read
   }
+  if constexpr (HOLES) return;  // |P| and the box are there already
   if (wave == 0) {  // lanes 0 .. 31: one row each
     const unsigned long long bits = lane < CT_ROWS ? rowmask[lane & (CT_ROWS - 1)] : 0ull;
     const bool has = bits != 0;
@@ -187,11 +234,28 @@ __global__ __launch_bounds__(256) void cc_local_kernel(const float* __restrict__
   }
 }
 
+// MEMO (the fill-holes route, whose mask is mostly whole rows of background): a union is made between the two voxels' current parents - their tile-local roots as `local`
+// left them, or a smaller ancestor since - and a lane skips the union whose pair of parents is the pair of its previous one: the rows of a tile that face the same
+// neighbour tile then cost one union per lane that makes them, not one per row.  The labels do not change: uniting ancestors unites the voxels.
+template <bool MEMO>
+__device__ __forceinline__ void cc_unite(int* parent, int va, int vb, int& last_a, int& last_b) {
+  if constexpr (MEMO) {
+    const int a = __hip_atomic_load(parent + va, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), b = __hip_atomic_load(parent + vb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // both >= 0: mask voxels
+    if (a == last_a && b == last_b) return;
+    last_a = a, last_b = b;
+    cc_union<true>(parent, a, b);
+  } else {
+    cc_union<true>(parent, va, vb);
+  }
+}
+
+template <bool MEMO>
 __global__ __launch_bounds__(256) void cc_merge_kernel(const CompRec* __restrict__ rec, int X, int Y, int Z, int conn, int* parent) {
   const int z0 = blockIdx.x * CT_Z, y0 = blockIdx.y * CT_Y, x0 = blockIdx.z * CT_X;
   if (cc_tile_outside_box(rec, x0, y0, z0)) return;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int z = z0 + lane;
+  int last_a = -1, last_b = -1;  // MEMO: the pair of this lane's previous union
   for (int k = 0; k < CT_ROWS / 4; ++k) {
     const int r = k * 4 + wave, lx = r >> 3, ly = r & 7, x = x0 + lx, y = y0 + ly;
     if (x >= X || y >= Y) continue;  // (the same in every lane of the wave)
@@ -226,10 +290,10 @@ __global__ __launch_bounds__(256) void cc_merge_kernel(const CompRec* __restrict
       const int64_t row2 = ((int64_t)xn * Y + yn) * Z;
       const bool q0 = cc_bit(nb[n], lane);
       // head-on: the first voxel of the overlap of the two runs makes the union for all of it
-      if (s > 0 && other_xy && q0 && !(me_m && cc_bit(nb[n], lane - 1))) cc_union<true>(parent, v, (int)(row2 + z));
+      if (s > 0 && other_xy && q0 && !(me_m && cc_bit(nb[n], lane - 1))) cc_unite<MEMO>(parent, v, (int)(row2 + z), last_a, last_b);
       // a diagonal neighbour counts when it lies in another tile; inside the z range of this tile it is already joined through a head-on contact if there is one
-      if (s > 0 && s + 1 <= conn && qm[n] && (lane == 0 || (other_xy && !q0 && !me_m))) cc_union<true>(parent, v, (int)(row2 + z - 1));
-      if ((s == 0 || s + 1 <= conn) && qp[n] && (lane == 63 || (other_xy && !q0 && !me_p))) cc_union<true>(parent, v, (int)(row2 + z + 1));
+      if (s > 0 && s + 1 <= conn && qm[n] && (lane == 0 || (other_xy && !q0 && !me_m))) cc_unite<MEMO>(parent, v, (int)(row2 + z - 1), last_a, last_b);
+      if ((s == 0 || s + 1 <= conn) && qp[n] && (lane == 63 || (other_xy && !q0 && !me_p))) cc_unite<MEMO>(parent, v, (int)(row2 + z + 1), last_a, last_b);
     }
   }
 }
@@ -347,6 +411,144 @@ __global__ __launch_bounds__(256) void cc_write_kernel(const CompRec* __restrict
   }
 }
 
+// ---- remove small components: the passes up to `sizes` as above, then a count of the roots that pass the threshold and a write that tests cnt[root] ----
+
+__global__ __launch_bounds__(256) void rs_count_kernel(CompRec* __restrict__ rec, int X, int Y, int Z, const int* __restrict__ parent, const unsigned* __restrict__ cnt,
+                                                      unsigned long long min_voxels) {
+  const int z0 = blockIdx.x * CT_Z, y0 = blockIdx.y * CT_Y, x0 = blockIdx.z * CT_X;
+  if (cc_tile_outside_box(rec, x0, y0, z0)) return;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int z = z0 + lane;
+  unsigned long long kept_voxels = 0;
+  unsigned roots = 0, kept = 0;
+  for (int k = 0; k < CT_ROWS / 4; ++k) {
+    const int r = k * 4 + wave, x = x0 + (r >> 3), y = y0 + (r & 7);
+    if (x >= X || y >= Y || z >= Z) continue;
+    const int v = (int)(((int64_t)x * Y + y) * Z + z);
+    if (parent[v] != v) continue;
+    const unsigned c = cnt[v];
+    ++roots;
+    if ((unsigned long long)c >= min_voxels) ++kept, kept_voxels += c;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    kept_voxels += __shfl_xor(kept_voxels, o, 64);
+    roots += __shfl_xor(roots, o, 64);
+    kept += __shfl_xor(kept, o, 64);
+  }
+  if (lane == 0 && roots) {  // integer sums: the order does not matter
+    atomicAdd(&rec->ncomp, roots);
+    if (kept) atomicAdd(&rec->nkept, kept), atomicAdd(&rec->best, kept_voxels);
+  }
+}
+
+// ---- fill holes: |P| and its box first, then the labelling above on the complement of P inside the box ----
+// A hole is a connected component of the complement of P without a voxel on the border of the volume.  Every hole lies inside the box of P (a background voxel
+// outside the box reaches the border along a straight line that never enters the box), and a path that leaves the box passes a voxel on one of its faces (a step
+// changes every index by at most 1).  So a background component OF THE BOX without a voxel on a face of the box is a component of the whole complement, and it holds
+// no border voxel (a border voxel inside the box lies on a face of the box): a hole.  One with a background voxel on a face is not: that face lies on the border of
+// the volume, or the voxel's straight neighbour beyond the face starts such a line, and a straight step is allowed at every connectivity.
+
+__global__ __launch_bounds__(256) void fh_scan_kernel(const float* __restrict__ logits, int Y, int Z, int64_t nvox, CompRec* __restrict__ rec) {
+  unsigned n = 0;
+  int lo0 = INT_MAX, lo1 = INT_MAX, lo2 = INT_MAX, hi0 = -1, hi1 = -1, hi2 = -1;
+  for (unsigned v = blockIdx.x * 256u + threadIdx.x; v < (unsigned)nvox; v += gridDim.x * 256u) {  // (nvox < 2^31 and the stride < 2^24: no wrap)
+    const float2 lg = reinterpret_cast<const float2*>(logits)[v];
+    if (!(lg.y > lg.x)) continue;
+    const unsigned xy = v / (unsigned)Z, x = xy / (unsigned)Y;
+    const int z = (int)(v - xy * (unsigned)Z), y = (int)(xy - x * (unsigned)Y);
+    ++n;
+    lo0 = min(lo0, (int)x), lo1 = min(lo1, y), lo2 = min(lo2, z);
+    hi0 = max(hi0, (int)x), hi1 = max(hi1, y), hi2 = max(hi2, z);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+  if (!n) return;  // (the same in every lane of the wave)
+  lo0 = cc_wave_min(lo0), lo1 = cc_wave_min(lo1), lo2 = cc_wave_min(lo2);
+  hi0 = cc_wave_max(hi0), hi1 = cc_wave_max(hi1), hi2 = cc_wave_max(hi2);
+  if ((threadIdx.x & 63) == 0) {
+    atomicAdd(&rec->fg, (unsigned long long)n);
+    // the box only ever grows, so a bound that a (possibly stale) look already shows as reached needs no atomic: an all-foreground volume would otherwise queue
+    // six atomics per wave on six addresses
+    const int lo[3] = {lo0, lo1, lo2}, hi[3] = {hi0, hi1, hi2};
+    for (int a = 0; a < 3; ++a) {
+      if (lo[a] < __hip_atomic_load(&rec->bmin[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&rec->bmin[a], lo[a]);
+      if (hi[a] > __hip_atomic_load(&rec->bmax[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&rec->bmax[a], hi[a]);
+    }
+  }
+}
+
+// parent[v] = root(v), and a background voxel on a face of the box marks its root (cnt[root] = 1; fh local zeroed every mark, and every marker stores the same value)
+__global__ __launch_bounds__(256) void fh_flatten_kernel(const CompRec* __restrict__ rec, int X, int Y, int Z, int* parent, unsigned* __restrict__ cnt) {
+  const int z0 = blockIdx.x * CT_Z, y0 = blockIdx.y * CT_Y, x0 = blockIdx.z * CT_X;
+  if (cc_tile_outside_box(rec, x0, y0, z0)) return;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int z = z0 + lane;
+  if (z >= Z) return;
+  const int b0x = rec->bmin[0], b0y = rec->bmin[1], b0z = rec->bmin[2], b1x = rec->bmax[0], b1y = rec->bmax[1], b1z = rec->bmax[2];
+  for (int k = 0; k < CT_ROWS / 4; ++k) {
+    const int r = k * 4 + wave, x = x0 + (r >> 3), y = y0 + (r & 7);
+    if (x >= X || y >= Y) continue;
+    const int v = (int)(((int64_t)x * Y + y) * Z + z);
+    if (parent[v] < 0) continue;  // (a voxel with a parent lies in the box)
+    const int root = cc_find<true>(parent, v);
+    parent[v] = root;
+    if (x == b0x || x == b1x || y == b0y || y == b1y || z == b0z || z == b1z) cnt[root] = 1;
+  }
+}
+
+// holes = roots without a mark, |H| = their voxels
+__global__ __launch_bounds__(256) void fh_count_kernel(CompRec* __restrict__ rec, int X, int Y, int Z, const int* __restrict__ parent, const unsigned* __restrict__ cnt) {
+  const int z0 = blockIdx.x * CT_Z, y0 = blockIdx.y * CT_Y, x0 = blockIdx.z * CT_X;
+  if (cc_tile_outside_box(rec, x0, y0, z0)) return;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int z = z0 + lane;
+  unsigned holes = 0, filled = 0;
+  for (int k = 0; k < CT_ROWS / 4; ++k) {
+    const int r = k * 4 + wave, x = x0 + (r >> 3), y = y0 + (r & 7);
+    if (x >= X || y >= Y || z >= Z) continue;
+    const int v = (int)(((int64_t)x * Y + y) * Z + z);
+    const int p = parent[v];
+    if (p < 0 || cnt[p]) continue;
+    ++filled;
+    holes += p == v;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    holes += __shfl_xor(holes, o, 64);
+    filled += __shfl_xor(filled, o, 64);
+  }
+  if (lane == 0 && filled) {
+    atomicAdd(&rec->best, (unsigned long long)filled);
+    if (holes) atomicAdd(&rec->ncomp, holes);
+  }
+}
+
+// The one-hot fp32 result of the two routes over the whole volume; parents (and the counter of a voxel's root) are read inside the box only.
+// HOLES: 1 on P (in the box: no parent) and on the background components without a mark; otherwise 1 on the components of P with at least min_voxels voxels.
+template <bool HOLES>
+__global__ __launch_bounds__(256) void morph_write_kernel(const CompRec* __restrict__ rec, int Y, int Z, int64_t nvox, const int* __restrict__ parent, const unsigned* __restrict__ cnt,
+                                                         unsigned long long min_voxels, float2* __restrict__ out, long long* __restrict__ stats) {
+  if (stats && blockIdx.x == 0 && threadIdx.x == 0) {
+    stats[0] = (long long)rec->fg;
+    stats[1] = (long long)rec->ncomp;
+    stats[2] = (long long)rec->best;
+    stats[3] = HOLES ? (long long)(rec->fg + rec->best) : (long long)rec->nkept;
+  }
+  const int b0x = rec->bmin[0], b0y = rec->bmin[1], b0z = rec->bmin[2], b1x = rec->bmax[0], b1y = rec->bmax[1], b1z = rec->bmax[2];
+  for (unsigned v = blockIdx.x * 256u + threadIdx.x; v < (unsigned)nvox; v += gridDim.x * 256u) {  // (nvox < 2^31 and the stride < 2^24: no wrap)
+    const unsigned xy = v / (unsigned)Z, x = xy / (unsigned)Y;
+    const int z = (int)(v - xy * (unsigned)Z), y = (int)(xy - x * (unsigned)Y);
+    float f = 0.f;
+    if ((int)x >= b0x && (int)x <= b1x && y >= b0y && y <= b1y && z >= b0z && z <= b1z) {
+      const int p = parent[v];
+      if (HOLES) f = (p < 0 || cnt[p] == 0) ? 1.f : 0.f;
+      else f = (p >= 0 && (unsigned long long)cnt[p] >= min_voxels) ? 1.f : 0.f;
+    }
+    out[v] = make_float2(1.f - f, f);
+  }
+}
+
 bool cc_dims_ok(const int32_t* dims) {
   if (!dims) return false;
   for (int a = 0; a < 3; ++a)
@@ -354,14 +556,19 @@ bool cc_dims_ok(const int32_t* dims) {
   return true;
 }
 
-int cc_run(const char* name, const float* logits, int32_t pitch, const int32_t* dims, int32_t connectivity, void* scratch, int64_t scratch_bytes, void* out, int out_align, bool labels,
-           int64_t* stats, bool stats_required, void* stream) {
-  VSSEG_CHECK(logits && scratch && out && (stats || !stats_required), "%s: null pointer (logits, scratch, %s)", name, labels ? "labels, stats" : "out");
+enum CompRoute { CC_LABELS, CC_LARGEST, CC_SMALL, CC_HOLES };
+
+int cc_run(const char* name, CompRoute route, const float* logits, int32_t pitch, const int32_t* dims, int32_t connectivity, int64_t min_voxels, void* scratch, int64_t scratch_bytes,
+           void* out, int64_t* stats, void* stream) {
+  const bool labels = route == CC_LABELS;
+  const int out_align = labels ? 4 : 8;
+  VSSEG_CHECK(logits && scratch && out && (stats || !labels), "%s: null pointer (logits, scratch, %s)", name, labels ? "labels, stats" : "out");
   VSSEG_CHECK(pitch == 2, "%s: pitch must be 2 (channels-last two-class logits), got %d", name, pitch);
   VSSEG_CHECK(cc_dims_ok(dims), "%s: dims must be 1 .. %d on every axis", name, CC_MAX_EXTENT);
   const int64_t nvox = (int64_t)dims[0] * dims[1] * dims[2];
   VSSEG_CHECK(nvox < (int64_t)INT32_MAX, "%s: dims %d x %d x %d hold %lld voxels, the int32 labels allow fewer than 2^31 - 1", name, dims[0], dims[1], dims[2], (long long)nvox);
   VSSEG_CHECK(connectivity == 6 || connectivity == 18 || connectivity == 26, "%s: connectivity must be 6, 18 or 26, got %d", name, connectivity);
+  VSSEG_CHECK(min_voxels >= 0, "%s: min_voxels must not be negative, got %lld", name, (long long)min_voxels);
   VSSEG_CHECK((reinterpret_cast<uintptr_t>(logits) & 7) == 0 && (reinterpret_cast<uintptr_t>(out) & (uintptr_t)(out_align - 1)) == 0 && (reinterpret_cast<uintptr_t>(stats) & 7) == 0 &&
                   (reinterpret_cast<uintptr_t>(scratch) & 255) == 0,
               "%s: misaligned operand (logits / stats 8 B, %s, scratch 256 B)", name, labels ? "labels 4 B" : "out 8 B");
@@ -374,16 +581,33 @@ int cc_run(const char* name, const float* logits, int32_t pitch, const int32_t* 
   CompRec* rec = reinterpret_cast<CompRec*>(base);
   int* parent = reinterpret_cast<int*>(base + l.parent);
   unsigned* cnt = reinterpret_cast<unsigned*>(base + l.cnt);
+  long long* st = reinterpret_cast<long long*>(stats);
+  const unsigned long long minv = (unsigned long long)min_voxels;
   const dim3 tiles((Z + CT_Z - 1) / CT_Z, (Y + CT_Y - 1) / CT_Y, (X + CT_X - 1) / CT_X);
+  const int wg = grid_for(nvox, 256, 256 * 32);
   hipLaunchKernelGGL(cc_init_kernel, dim3(1), dim3(64), 0, s, rec);
-  hipLaunchKernelGGL(cc_local_kernel, tiles, dim3(256), 0, s, logits, X, Y, Z, conn, parent, rec);
-  hipLaunchKernelGGL(cc_merge_kernel, tiles, dim3(256), 0, s, (const CompRec*)rec, X, Y, Z, conn, parent);
+  if (route == CC_HOLES) {
+    hipLaunchKernelGGL(fh_scan_kernel, dim3(wg), dim3(256), 0, s, logits, Y, Z, nvox, rec);
+    hipLaunchKernelGGL(cc_local_kernel<true>, tiles, dim3(256), 0, s, logits, X, Y, Z, conn, parent, cnt, rec);
+    hipLaunchKernelGGL(cc_merge_kernel<true>, tiles, dim3(256), 0, s, (const CompRec*)rec, X, Y, Z, conn, parent);
+    hipLaunchKernelGGL(fh_flatten_kernel, tiles, dim3(256), 0, s, (const CompRec*)rec, X, Y, Z, parent, cnt);
+    hipLaunchKernelGGL(fh_count_kernel, tiles, dim3(256), 0, s, rec, X, Y, Z, (const int*)parent, (const unsigned*)cnt);
+    hipLaunchKernelGGL(morph_write_kernel<true>, dim3(wg), dim3(256), 0, s, (const CompRec*)rec, Y, Z, nvox, (const int*)parent, (const unsigned*)cnt, 0ull, static_cast<float2*>(out), st);
+    VSSEG_LAUNCH_CHECK(name);
+    return VSSEG_OK;
+  }
+  hipLaunchKernelGGL(cc_local_kernel<false>, tiles, dim3(256), 0, s, logits, X, Y, Z, conn, parent, cnt, rec);
+  hipLaunchKernelGGL(cc_merge_kernel<false>, tiles, dim3(256), 0, s, (const CompRec*)rec, X, Y, Z, conn, parent);
   hipLaunchKernelGGL(cc_flatten_kernel, tiles, dim3(256), 0, s, (const CompRec*)rec, X, Y, Z, parent, cnt);
   hipLaunchKernelGGL(cc_sizes_kernel, tiles, dim3(256), 0, s, (const CompRec*)rec, X, Y, Z, (const int*)parent, cnt);
-  hipLaunchKernelGGL(cc_select_kernel, tiles, dim3(256), 0, s, rec, X, Y, Z, (const int*)parent, (const unsigned*)cnt);
-  const int wg = grid_for(nvox, 256, 256 * 32);
-  if (labels) hipLaunchKernelGGL(cc_write_kernel<true>, dim3(wg), dim3(256), 0, s, (const CompRec*)rec, Y, Z, nvox, (const int*)parent, out, reinterpret_cast<long long*>(stats));
-  else hipLaunchKernelGGL(cc_write_kernel<false>, dim3(wg), dim3(256), 0, s, (const CompRec*)rec, Y, Z, nvox, (const int*)parent, out, reinterpret_cast<long long*>(stats));
+  if (route == CC_SMALL) {
+    hipLaunchKernelGGL(rs_count_kernel, tiles, dim3(256), 0, s, rec, X, Y, Z, (const int*)parent, (const unsigned*)cnt, minv);
+    hipLaunchKernelGGL(morph_write_kernel<false>, dim3(wg), dim3(256), 0, s, (const CompRec*)rec, Y, Z, nvox, (const int*)parent, (const unsigned*)cnt, minv, static_cast<float2*>(out), st);
+  } else {
+    hipLaunchKernelGGL(cc_select_kernel, tiles, dim3(256), 0, s, rec, X, Y, Z, (const int*)parent, (const unsigned*)cnt);
+    if (labels) hipLaunchKernelGGL(cc_write_kernel<true>, dim3(wg), dim3(256), 0, s, (const CompRec*)rec, Y, Z, nvox, (const int*)parent, out, st);
+    else hipLaunchKernelGGL(cc_write_kernel<false>, dim3(wg), dim3(256), 0, s, (const CompRec*)rec, Y, Z, nvox, (const int*)parent, out, st);
+  }
   VSSEG_LAUNCH_CHECK(name);
   return VSSEG_OK;
 }
@@ -400,10 +624,20 @@ extern "C" int64_t vsseg_components_scratch_bytes(const int32_t dims[3]) {
 
 extern "C" int vsseg_components_label(const float* logits, int32_t pitch, const int32_t dims[3], int32_t connectivity, void* scratch, int64_t scratch_bytes, int32_t* labels,
                                       int64_t* stats, void* stream) {
-  return cc_run("vsseg_components_label", logits, pitch, dims, connectivity, scratch, scratch_bytes, labels, 4, true, stats, true, stream);
+  return cc_run("vsseg_components_label", CC_LABELS, logits, pitch, dims, connectivity, 0, scratch, scratch_bytes, labels, stats, stream);
 }
 
 extern "C" int vsseg_keep_largest_component(const float* logits, int32_t pitch, const int32_t dims[3], int32_t connectivity, void* scratch, int64_t scratch_bytes, float* out,
                                             int64_t* stats, void* stream) {
-  return cc_run("vsseg_keep_largest_component", logits, pitch, dims, connectivity, scratch, scratch_bytes, out, 8, false, stats, false, stream);
+  return cc_run("vsseg_keep_largest_component", CC_LARGEST, logits, pitch, dims, connectivity, 0, scratch, scratch_bytes, out, stats, stream);
+}
+
+extern "C" int vsseg_fill_holes(const float* logits, int32_t pitch, const int32_t dims[3], int32_t connectivity, void* scratch, int64_t scratch_bytes, float* out, int64_t* stats,
+                                void* stream) {
+  return cc_run("vsseg_fill_holes", CC_HOLES, logits, pitch, dims, connectivity, 0, scratch, scratch_bytes, out, stats, stream);
+}
+
+extern "C" int vsseg_remove_small_components(const float* logits, int32_t pitch, const int32_t dims[3], int32_t connectivity, int64_t min_voxels, void* scratch, int64_t scratch_bytes,
+                                             float* out, int64_t* stats, void* stream) {
+  return cc_run("vsseg_remove_small_components", CC_SMALL, logits, pitch, dims, connectivity, min_voxels, scratch, scratch_bytes, out, stats, stream);
 }

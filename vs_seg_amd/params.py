@@ -30,7 +30,7 @@ from . import SGD, Adam, AdamW, Dice_spvPA, UNet2d5_spvPA, check_ce, check_ce_to
 from .optim import DEFAULT_WEIGHT_DECAY, LR_SCHEDULES, OPTIMIZERS
 from .inferers import argmax_segmentation, tta_masks
 from .metrics import MEASUREMENT_FIELDS, compute_measurements, compute_surface_distances, voxel_spacing
-from .postprocess import keep_largest_component
+from .postprocess import connected_components, fill_holes, keep_largest_component, min_component_voxels, remove_small_components
 from . import parallel as DP
 from .data import nifti
 from .data.transforms import APPEARANCE_KEYS, AUGMENT_KEYS, FIELD_KEYS, PatchSampler, check_appearance_augment, check_augment, check_field_augment, epoch_batches, load_case
@@ -41,6 +41,11 @@ HP = dict(
     kernel_sizes=((3, 3, 1), (3, 3, 1), (3, 3, 3), (3, 3, 3), (3, 3, 3), (3, 3, 3)),
     sample_kernel_sizes=((3, 3, 1), (3, 3, 1), (3, 3, 3), (3, 3, 3), (3, 3, 3)),
 )
+
+
+def postprocessing_csv_header(fill_holes: bool, min_component: bool) -> str:
+    """Columns of figures/test_postprocessing.csv: the six of --keep_largest_component, then those of --fill_holes and of --min_component_mm3 as switched on."""
+    return "case,dice_raw,dice,components,foreground_voxels,kept_voxels" + (",holes,filled_voxels" if fill_holes else "") + (",small_components,small_voxels" if min_component else "")
 
 
 class CachedLoader:
@@ -97,7 +102,10 @@ class VSparams:
         parser.add_argument("--surface_metrics", action="store_true", help="run_inference also reports HD95 and ASSD per test case (mm, on the GPU) and writes figures/test_surface_metrics.csv")
         parser.add_argument("--keep_largest_component", action="store_true", help="run_inference keeps only the largest connected component of each predicted segmentation (on the GPU) before the Dice, the surface metrics and the NIfTI export, and writes figures/test_postprocessing.csv")
         parser.add_argument("--measurements", action="store_true", help="run_inference also reports per test case the volume (mm^3), the largest 3-D diameter and the largest diameter within an axial slice (mm) of the predicted and of the manual segmentation and the distance between their centres of mass (on the GPU), and writes figures/test_measurements.csv")
-        parser.add_argument("--component_connectivity", type=int, default=26, choices=[6, 18, 26], help="voxel connectivity of --keep_largest_component (26: MONAI's KeepLargestConnectedComponent)")
+        parser.add_argument("--component_connectivity", type=int, default=26, choices=[6, 18, 26], help="voxel connectivity of --keep_largest_component and --min_component_mm3 (26: MONAI's KeepLargestConnectedComponent)")
+        parser.add_argument("--fill_holes", action="store_true", help="run_inference fills the holes of each predicted segmentation (background enclosed by foreground, e.g. the missed fluid of a cystic tumour; on the GPU, before --min_component_mm3 and --keep_largest_component) and adds holes,filled_voxels to figures/test_postprocessing.csv (MONAI's FillHoles)")
+        parser.add_argument("--hole_connectivity", type=int, default=6, choices=[6, 18, 26], help="voxel connectivity of the BACKGROUND for --fill_holes (6: scipy.ndimage.binary_fill_holes, the dual of a 26-connected foreground; 26: MONAI's FillHoles)")
+        parser.add_argument("--min_component_mm3", type=float, default=0.0, metavar="V", help="run_inference drops every connected component of a predicted segmentation that is smaller than V cubic millimetres (ceil(V / voxel volume) voxels per case; on the GPU, at --component_connectivity) and adds small_components,small_voxels to figures/test_postprocessing.csv (MONAI's RemoveSmallObjects; 0: off)")
         parser.add_argument("--tta_flips", type=int, nargs="*", choices=[0, 1, 2], default=None, metavar="AXIS", help="run_inference predicts every case on mirrored copies as well (spatial axes 0 1 2 = X Y Z: one pass per subset of the given axes) and averages the un-mirrored predictions; training mirrors axis 0")
         parser.add_argument("--tta_average", type=str, default="logits", choices=["logits", "probabilities"], help="what --tta_flips averages: the blended logits, or their softmax over the classes (nnU-Net)")
         parser.add_argument("--aug_rotate_deg", type=float, default=0.0, metavar="DEG", help="training augmentation: rotate every training patch about the z axis by an angle drawn from [-DEG, DEG] (0: off)")
@@ -132,6 +140,7 @@ class VSparams:
             augment = check_augment(*(getattr(args, "aug_" + k) for k in AUGMENT_KEYS))
             field = check_field_augment(args.aug_elastic_mag, args.aug_bias_field, args.aug_field_spacing)
             appearance = check_appearance_augment(*(getattr(args, "aug_" + k) for k in APPEARANCE_KEYS))
+            min_component_voxels(args.min_component_mm3, (1.0, 1.0, 1.0))  # a finite value >= 0
         except ValueError as e:
             parser.error(str(e))
 
@@ -158,6 +167,7 @@ class VSparams:
         self.surface_metrics = args.surface_metrics
         self.measurements = args.measurements
         self.keep_largest_component, self.component_connectivity = args.keep_largest_component, args.component_connectivity
+        self.fill_holes, self.hole_connectivity, self.min_component_mm3 = args.fill_holes, args.hole_connectivity, float(args.min_component_mm3)
         self.tta_flips, self.tta_average = tuple(args.tta_flips or ()), args.tta_average
         self.aug_rotate_deg, self.aug_scale, self.aug_intensity_scale, self.aug_intensity_shift, self.aug_noise_std = (augment[k] for k in AUGMENT_KEYS)
         self.aug_elastic_mag, self.aug_bias_field, self.aug_field_spacing = (field[k] for k in FIELD_KEYS)
@@ -197,7 +207,8 @@ class VSparams:
         for k in ("dataset", "data_root", "split_csv", "pad_crop_shape", "pad_crop_shape_test", "num_workers", "torch_device_arg", "train_batch_size", "initial_learning_rate",
                   "epochs_with_const_lr", "lr_divisor", "weight_decay", "num_epochs", "val_interval", "model", "sliding_window_inferer_roi_size", "attention", "hardness",
                   "results_folder_path", "export_inferred_segmentations", "compute_dtype") + (("surface_metrics",) if self.surface_metrics else ()) + (("measurements",) if self.measurements else ()) + (
-                      ("keep_largest_component", "component_connectivity") if self.keep_largest_component else ()) + (("tta_flips", "tta_average") if self.tta_flips else ()) + (
+                      ("fill_holes", "hole_connectivity") if self.fill_holes else ()) + (("min_component_mm3",) if self.min_component_mm3 > 0 else ()) + (
+                      ("keep_largest_component", "component_connectivity") if self.keep_largest_component else ("component_connectivity",) if self.min_component_mm3 > 0 else ()) + (("tta_flips", "tta_average") if self.tta_flips else ()) + (
                           tuple("aug_" + k for k in AUGMENT_KEYS) if any(self.augment.values()) else ()) + (
                               ("aug_elastic_mag", "aug_bias_field", "aug_field_spacing") if self.aug_elastic_mag or self.aug_bias_field else ()) + (
                                   tuple("aug_" + k for k in APPEARANCE_KEYS) if self._appearance_on else ()) + (("ce_weight", "ce_foreground_weight") if self.ce_weight > 0 else ()) + (("ce_topk",) if self.ce_topk > 0 else ()) + (
@@ -445,8 +456,11 @@ class VSparams:
         n = len(data_loader)
         dice_dev = torch.zeros(n, dtype=torch.float32, device=self.device)
         surf_dev = torch.zeros((2, n), dtype=torch.float32, device=self.device) if self.surface_metrics else None  # [hd95, assd] per case, mm
-        # --keep_largest_component: [raw Dice, foreground voxels, components, kept voxels] per case (fp64: the voxel counts of a full volume are not exact in fp32)
-        post_dev = torch.zeros((4, n), dtype=torch.float64, device=self.device) if self.keep_largest_component else None
+        # --fill_holes / --min_component_mm3 / --keep_largest_component: [raw Dice, foreground voxels, components, kept voxels] per case, then [holes, filled voxels] and
+        # [small components, small voxels] for the first two (fp64: the voxel counts of a full volume are not exact in fp32)
+        small = self.min_component_mm3 > 0
+        post_rows = 4 + 2 * self.fill_holes + 2 * small if (self.fill_holes or small or self.keep_largest_component) else 0
+        post_dev = torch.zeros((post_rows, n), dtype=torch.float64, device=self.device) if post_rows else None
         meas_dev = torch.zeros((len(MEASUREMENT_FIELDS), n), dtype=torch.float64, device=self.device) if self.measurements else None  # --measurements: the nine values per case
         predictor = model.segmentation_predictor() if hasattr(model, "segmentation_predictor") else (lambda *a, **k: model(*a, **k)[0])  # model_segmentation, ref:params/VSparams.py:560
         mine = DP.shard_indices(n)  # the unpadded, unshuffled test loader yields exactly these cases, in this order
@@ -459,8 +473,7 @@ class VSparams:
                 gi = mine[i]
                 if post_dev is not None:  # everything below describes the filtered prediction; the raw Dice is kept beside it
                     post_dev[0, gi] = self.compute_dice_score(outputs, data["label"]).reshape(())
-                    outputs, stats = keep_largest_component(outputs, self.component_connectivity, return_stats=True)
-                    post_dev[1:, gi] = stats[0, :3]
+                    outputs, post_dev[1:, gi] = self._postprocess(outputs, voxel_spacing(data["label_meta_dict"]["affine"]))
                 dice_dev[gi] = self.compute_dice_score(outputs, data["label"]).reshape(())
                 if surf_dev is not None:
                     surf_dev[:, gi] = compute_surface_distances(outputs, data["label"], voxel_spacing(data["label_meta_dict"]["affine"]), 95.0)[0]
@@ -479,7 +492,7 @@ class VSparams:
             if meas_dev is not None:
                 both, meas = both[:-len(MEASUREMENT_FIELDS)], both[-len(MEASUREMENT_FIELDS):]
             if post_dev is not None:
-                post = both[-4:]
+                post = both[-post_rows:]
         else:
             dice_scores = DP.allreduce_sum(dice_dev).double().cpu().numpy() if self.world > 1 else dice_dev.double().cpu().numpy()
         for i, v in enumerate(dice_scores):
@@ -494,20 +507,54 @@ class VSparams:
             self._log_measurements(dice_scores, meas)
         return dice_scores
 
-    def _log_postprocessing(self, dice, dice_raw, foreground, components, kept):
-        """Per-case lines of --keep_largest_component beside the (filtered) dice_score lines, and figures/test_postprocessing.csv (rank 0)."""
+    def _postprocess(self, outputs, spacing):
+        """The post-processing steps that are switched on, each on the output of the previous one: fill holes, remove small components, keep the largest.  Returns the
+        final one-hot prediction and the rows of the case for the all-reduce, all on the device: foreground voxels of the raw prediction, components of the prediction
+        that enters the first component filter (with --fill_holes alone: of the filled prediction), voxels of the final prediction, then [holes, filled voxels] and
+        [small components, small voxels] as switched on."""
+        foreground = components = None
+        extra = []
+        if self.fill_holes:
+            outputs, st = fill_holes(outputs, self.hole_connectivity, return_stats=True)
+            foreground, kept = st[0, 0], st[0, 3]
+            extra += [st[0, 1], st[0, 2]]
+        if self.min_component_mm3 > 0:
+            outputs, st = remove_small_components(outputs, min_component_voxels(self.min_component_mm3, spacing), self.component_connectivity, return_stats=True)
+            foreground, components, kept = st[0, 0] if foreground is None else foreground, st[0, 1], st[0, 2]
+            extra += [st[0, 1] - st[0, 3], st[0, 0] - st[0, 2]]
+        if self.keep_largest_component:
+            outputs, st = keep_largest_component(outputs, self.component_connectivity, return_stats=True)
+            foreground, components, kept = st[0, 0] if foreground is None else foreground, st[0, 1] if components is None else components, st[0, 2]
+        if components is None:  # --fill_holes alone
+            components = connected_components(outputs, self.component_connectivity)[1][0, 1]
+        return outputs, torch.stack([foreground, components, kept] + extra).double()
+
+    def _log_postprocessing(self, dice, dice_raw, foreground, components, kept, *extra):
+        """Per-case lines of --fill_holes / --min_component_mm3 / --keep_largest_component beside the (post-processed) dice_score lines, and
+        figures/test_postprocessing.csv (rank 0).  extra: [holes, filled voxels] with --fill_holes, then [small components, small voxels] with --min_component_mm3."""
         log = self.logger.info
+        extra = list(extra)
+        holes, filled = (extra.pop(0), extra.pop(0)) if self.fill_holes else (None, None)
+        small_components, small_voxels = (extra.pop(0), extra.pop(0)) if self.min_component_mm3 > 0 else (None, None)
         for i, (d, f, c, k) in enumerate(zip(dice_raw, foreground, components, kept)):
             log(f"dice_score_raw[{i}] = {d}")
+            if holes is not None:
+                log(f"holes[{i}] = {int(holes[i])}")
+                log(f"filled_voxels[{i}] = {int(filled[i])}")
             log(f"components[{i}] = {int(c)}")
-            log(f"removed_voxels[{i}] = {int(f) - int(k)}")
+            if small_components is not None:
+                log(f"small_components_removed[{i}] = {int(small_components[i])}")
+                log(f"small_voxels_removed[{i}] = {int(small_voxels[i])}")
+            if self.keep_largest_component or small_components is not None:  # what the component filters took away
+                log(f"removed_voxels[{i}] = {int(f) + (int(filled[i]) if filled is not None else 0) - int(k)}")
         log(f"mean_dice_score_raw = {dice_raw.mean()} +- {dice_raw.std()}")
         if self.rank == 0:
             os.makedirs(self.figures_path, exist_ok=True)
             with open(os.path.join(self.figures_path, "test_postprocessing.csv"), "w") as f:
-                f.write("case,dice_raw,dice,components,foreground_voxels,kept_voxels\n")
+                f.write(postprocessing_csv_header(self.fill_holes, self.min_component_mm3 > 0) + "\n")
                 for i, (r, d, c, fg, k) in enumerate(zip(dice_raw, dice, components, foreground, kept)):
-                    f.write(f"{i},{float(r)!r},{float(d)!r},{int(c)},{int(fg)},{int(k)}\n")
+                    more = ([holes[i], filled[i]] if holes is not None else []) + ([small_components[i], small_voxels[i]] if small_components is not None else [])
+                    f.write(f"{i},{float(r)!r},{float(d)!r},{int(c)},{int(fg)},{int(k)}" + "".join(f",{int(v)}" for v in more) + "\n")
 
     def _log_surface_metrics(self, dice, hd95, assd):
         """Per-case HD95 / ASSD lines, their mean +- std over the finite cases, and figures/test_surface_metrics.csv (rank 0)."""
