@@ -100,11 +100,14 @@ def run_lattice_op(kind, w, x_cl, out_cl, stride, **epi):
     return keep
 
 
-def run_wgrad(transposed, wshape, kernel, stride, p_cl, h_cl, cp_valid, ch_valid, hgroup=0, single_buffer=0, march_tile=None, dbias=None, h_gate=None, compute=0, blocks=None):
+def run_wgrad(transposed, wshape, kernel, stride, p_cl, h_cl, cp_valid, ch_valid, hgroup=0, single_buffer=0, march_tile=None, dbias=None, h_gate=None, compute=0, blocks=None, dw0=None, dbias0=None, scratch_elems=None):
+    """dw0: the weight gradient to accumulate into (default zeros); dbias0: value `dbias` is filled with before the launch; scratch_elems: floats of scratch
+    the launch is told it has (default 8 Mi, 48 Mi for the compute kernel) — the buffer carries a guard band behind them that must come back untouched."""
     lib = L.lib()
     es = p_cl.element_size()
     wp = P.plan_wgrad(transposed, wshape, kernel, stride, tuple(p_cl.shape[1:4]), es)
-    dw = torch.zeros(int(np.prod(wshape)), dtype=torch.float32, device="cuda")
+    dw = torch.zeros(int(np.prod(wshape)), dtype=torch.float32, device="cuda") if dw0 is None else dw0.detach().to(torch.float32).reshape(-1).contiguous().cuda().clone()
+    assert dw.numel() == int(np.prod(wshape))
     d = L.WgradDesc()
     d.p, d.h, d.cp_valid, d.ch_valid = tdesc(p_cl), (two_part(*h_cl) if isinstance(h_cl, tuple) else tdesc(h_cl)), cp_valid, ch_valid
     fill_wgrad_desc(d, wp)
@@ -118,11 +121,15 @@ def run_wgrad(transposed, wshape, kernel, stride, p_cl, h_cl, cp_valid, ch_valid
     if blocks is not None:
         d.persistent_blocks = blocks
     if dbias is not None:
+        if dbias0 is not None:
+            dbias.fill_(dbias0)
         d.dbias_p = dbias.data_ptr()
     if h_gate is not None:
         d.h_gate = h_gate.data_ptr()
-    scr = torch.zeros((48 if compute else 8) * 1024 * 1024, dtype=torch.float32, device="cuda")
-    d.scratch, d.scratch_elems = scr.data_ptr(), scr.numel()
+    guard = 0 if scratch_elems is None else 4096
+    scr = torch.zeros(((48 if compute else 8) * 1024 * 1024 if scratch_elems is None else int(scratch_elems)) + guard, dtype=torch.float32, device="cuda")
+    d.scratch, d.scratch_elems = scr.data_ptr(), scr.numel() - guard
     L.check(lib.vsseg_wgrad(C.byref(d), stream()), "wgrad")
     torch.cuda.synchronize()
+    assert not guard or not bool(scr[-guard:].any()), "the launch wrote behind the scratch it was given"
     return dw.cpu().reshape(wshape)
