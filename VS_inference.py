@@ -4,6 +4,8 @@
     python VS_inference.py --results_folder_name run1 [--dataset T2] [--no_attention] [--debug]
 
 `--surface_metrics` also reports HD95 and ASSD (mm) per test case, computed on the GPU, and writes figures/test_surface_metrics.csv.
+`--surface_dice_mm TAU [TAU ...]` also reports the normalised surface Dice, the surface precision and recall at each tolerance (mm) and the mean of the two
+directed mean surface distances per test case, from the same GPU call, and writes figures/test_surface_dice.csv.
 `--keep_largest_component [--component_connectivity 26]` keeps only the largest connected component of each predicted segmentation (on the GPU) before
 the Dice, the surface metrics and the NIfTI export; the raw Dice and the component counts go to the log and figures/test_postprocessing.csv.
 `--fill_holes [--hole_connectivity 6]` fills the holes of each predicted segmentation and `--min_component_mm3 V` drops its connected components below

@@ -235,7 +235,7 @@ int vsseg_fork_event_destroy(void* ev);
 int vsseg_fork_arm(void* ev);
 int vsseg_fork_disarm(void);
 int vsseg_stream_wait_event(void* stream, void* ev);
-int vsseg_version(void); /* 16: + vsseg_topk_scratch_bytes, vsseg_topk_select, vsseg_ce_topk_select, vsseg_dice_ce_topk_finalize, vsseg_dice_ce_topk_pred_bwd, vsseg_dice_ce_topk_pred_bwd_to; 15: + vsseg_grad_norm_scratch_bytes, vsseg_grad_norm, vsseg_sgd, vsseg_adam_clipped, vsseg_clip_record; 14: + vsseg_ce_sums, vsseg_dice_ce_finalize, vsseg_dice_ce_pred_bwd, vsseg_dice_ce_pred_bwd_to; 13: + vsseg_patch_filter, vsseg_patch_tone; 12: + vsseg_crop_field, vsseg_field_job; 11: + vsseg_crop_affine, vsseg_affine_job; 10: + vsseg_swi_finalize_mirrored, vsseg_crop_job.flip is a three-axis mirror mask (was flip_x); 9: + vsseg_components_scratch_bytes, vsseg_components_label, vsseg_keep_largest_component; 8: + vsseg_surface_distances, vsseg_surface_scratch_bytes; 7: + vsseg_dice_pred_bwd_to, vsseg_dice_level_sums, vsseg_dice_tail_sums, vsseg_dice_att_bwd_levels, vsseg_fork_*, vsseg_stream_wait_event; 6: + launch plans with depth -8 (transition kernel) and -9 (gathering marching kernel); 5: vsseg_wgrad march = 2 (compute weight-gradient kernel), + vsseg_conv_to1, vsseg_conv_chain_desc without h_out (the training variant measured no gain and was deleted); 4: + vsseg_conv_chain; 3: the BatchNorm-block-on-load fields (in_bn_*, keep_*, x_bn_*: round-4 experiment, measured a loss, deleted) left the descriptors, depth -7 plans;
+int vsseg_version(void); /* 19: + vsseg_surface_metrics; 18: + vsseg_fill_holes, vsseg_remove_small_components; 17: + vsseg_measure_scratch_bytes, vsseg_measurements; 16: + vsseg_topk_scratch_bytes, vsseg_topk_select, vsseg_ce_topk_select, vsseg_dice_ce_topk_finalize, vsseg_dice_ce_topk_pred_bwd, vsseg_dice_ce_topk_pred_bwd_to; 15: + vsseg_grad_norm_scratch_bytes, vsseg_grad_norm, vsseg_sgd, vsseg_adam_clipped, vsseg_clip_record; 14: + vsseg_ce_sums, vsseg_dice_ce_finalize, vsseg_dice_ce_pred_bwd, vsseg_dice_ce_pred_bwd_to; 13: + vsseg_patch_filter, vsseg_patch_tone; 12: + vsseg_crop_field, vsseg_field_job; 11: + vsseg_crop_affine, vsseg_affine_job; 10: + vsseg_swi_finalize_mirrored, vsseg_crop_job.flip is a three-axis mirror mask (was flip_x); 9: + vsseg_components_scratch_bytes, vsseg_components_label, vsseg_keep_largest_component; 8: + vsseg_surface_distances, vsseg_surface_scratch_bytes; 7: + vsseg_dice_pred_bwd_to, vsseg_dice_level_sums, vsseg_dice_tail_sums, vsseg_dice_att_bwd_levels, vsseg_fork_*, vsseg_stream_wait_event; 6: + launch plans with depth -8 (transition kernel) and -9 (gathering marching kernel); 5: vsseg_wgrad march = 2 (compute weight-gradient kernel), + vsseg_conv_to1, vsseg_conv_chain_desc without h_out (the training variant measured no gain and was deleted); 4: + vsseg_conv_chain; 3: the BatchNorm-block-on-load fields (in_bn_*, keep_*, x_bn_*: round-4 experiment, measured a loss, deleted) left the descriptors, depth -7 plans;
                             * 2: fixed-point accumulators documented + vsseg_fx_status; 1: the buffers below were described as plain doubles */
 
 /* ---- Accumulator buffers are 64-bit FIXED-POINT integers, not doubles ------------------------------------------------------------------
@@ -644,6 +644,24 @@ int vsseg_argmax2(const float* logits, int32_t pitch, int64_t nvox, uint8_t* dst
 int64_t vsseg_surface_scratch_bytes(const int32_t dims[3]); /* bytes of scratch, or VSSEG_EINVAL */
 int vsseg_surface_distances(const float* logits, int32_t pitch, const float* label, const int32_t dims[3], const float spacing[3] /* mm per voxel along x, y, z */,
                             double percentile /* 0 .. 100 */, void* scratch, int64_t scratch_bytes, float* out, void* stream);
+/* vsseg_surface_distances plus the normalised surface Dice (NSD) at tolerances in mm, from the same edge pass and the same distance transform (ABI version 19; the
+   metric of the Medical Segmentation Decathlon and Metrics Reloaded, MONAI's compute_surface_dice without sub-voxels).  Masks, edges, d(P->G), d(G->P), operands, scratch,
+   stream and determinism as above: one volume per call, launches on `stream` only, no host read, no allocation, bit-identical from call to call; the same number of
+   launches and no pass over the volume or the bounding box beyond those of vsseg_surface_distances (the counting rides on the first histogram pass).
+   tolerances_mm: ntol (0 .. 8) finite values >= 0 in HOST memory, read before the call returns; may be NULL when ntol = 0.  out: 3 + 3 * ntol fp32 in device memory:
+     out[0] = hd, out[1] = assd: the same bits vsseg_surface_distances writes for the same arguments;
+     out[2] = masd = (mean d(P->G) + mean d(G->P)) / 2, formed in fp64 from the two per-direction sums;
+     for tolerance t: out[3+3t] = nsd = (nP + nG) / (|E(P)| + |E(G)|), out[4+3t] = nP / |E(P)| (surface precision), out[5+3t] = nG / |E(G)| (surface recall), where nP
+     counts the voxels of E(P) within tau_t of E(G) and nG those of E(G) within tau_t of E(P): exact integer counts (integer atomics), each quotient formed once in fp64
+     and rounded once to fp32.
+   "Within tau" is decided on the squared distance field, never on a square root: a voxel counts when f <= t2, f the fp32 value the distance transform left for that voxel
+   and direction and t2 = (float)((double)tau * (double)tau); a tie counts, f = +inf never does.  Where the field is exact (unit spacing: integers below 2^24; spacings
+   such as 0.5 / 1.5: dyadic rationals) so is the result.
+   Empty masks (MONAI): both edge sets empty: every output NaN; exactly one empty: hd, assd, masd = +inf, every nsd = 0, the fraction over the empty set NaN, the other 0.
+   Checked before anything is launched: everything vsseg_surface_distances checks, ntol in 0 .. 8, tolerances_mm non-null when ntol > 0, every tolerance finite and >= 0. */
+int vsseg_surface_metrics(const float* logits, int32_t pitch, const float* label, const int32_t dims[3], const float spacing[3] /* mm per voxel along x, y, z */,
+                          double percentile /* 0 .. 100 */, const float* tolerances_mm /* host, ntol values */, int32_t ntol /* 0 .. 8 */, void* scratch, int64_t scratch_bytes,
+                          float* out /* 3 + 3 * ntol fp32, device */, void* stream);
 
 /* Connected components of the foreground of a two-class prediction and the prediction filtered to the largest of them (ABI version 9; the post-transform that MONAI
    spells AsDiscrete + KeepLargestConnectedComponent; beyond the reference, which reports and exports the raw argmax).  One volume [X][Y][Z] per call: logits

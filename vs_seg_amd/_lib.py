@@ -236,7 +236,7 @@ SYMBOLS = [
     "vsseg_dropout_mask", "vsseg_att_apply_fwd", "vsseg_att_apply_bwd", "vsseg_channel_sum", "vsseg_add_inplace", "vsseg_copy_cast",
     "vsseg_maxpool_label", "vsseg_dice_pred_sums", "vsseg_dice_att_sums", "vsseg_dice_finalize", "vsseg_dice_pred_bwd", "vsseg_dice_pred_bwd_to", "vsseg_dice_att_bwd", "vsseg_dice_level_sums", "vsseg_dice_tail_sums", "vsseg_dice_att_bwd_levels", "vsseg_ce_sums", "vsseg_dice_ce_finalize", "vsseg_dice_ce_pred_bwd", "vsseg_dice_ce_pred_bwd_to", "vsseg_fork_event_create", "vsseg_fork_event_destroy", "vsseg_fork_arm", "vsseg_fork_disarm", "vsseg_stream_wait_event",
     "vsseg_adam", "vsseg_swi_accumulate", "vsseg_swi_finalize", "vsseg_swi_finalize_mirrored", "vsseg_hard_dice_counts", "vsseg_argmax2",
-    "vsseg_surface_scratch_bytes", "vsseg_surface_distances",
+    "vsseg_surface_scratch_bytes", "vsseg_surface_distances", "vsseg_surface_metrics",
     "vsseg_components_scratch_bytes", "vsseg_components_label", "vsseg_keep_largest_component", "vsseg_fill_holes", "vsseg_remove_small_components",
     "vsseg_measure_scratch_bytes", "vsseg_measurements",
     "vsseg_grad_norm_scratch_bytes", "vsseg_grad_norm", "vsseg_sgd", "vsseg_adam_clipped",
@@ -328,6 +328,7 @@ def lib():
         L.vsseg_argmax2.argtypes = [vp, i32, i64, vp, vp]
         L.vsseg_surface_scratch_bytes.argtypes, L.vsseg_surface_scratch_bytes.restype = [I3], i64
         L.vsseg_surface_distances.argtypes = [vp, i32, vp, I3, C.POINTER(C.c_float), f64, vp, i64, vp, vp]
+        L.vsseg_surface_metrics.argtypes = [vp, i32, vp, I3, C.POINTER(C.c_float), f64, C.POINTER(C.c_float), i32, vp, i64, vp, vp]
         L.vsseg_components_scratch_bytes.argtypes, L.vsseg_components_scratch_bytes.restype = [I3], i64
         L.vsseg_components_label.argtypes = [vp, i32, I3, i32, vp, i64, vp, vp, vp]
         L.vsseg_keep_largest_component.argtypes = [vp, i32, I3, i32, vp, i64, vp, vp, vp]

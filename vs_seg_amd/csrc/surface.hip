@@ -13,6 +13,11 @@
 //             uint32 bits), both directions and both order statistics of the percentile at once; the first histogram pass also forms each
 //             workgroup's partial sums of the distances (combined in a fixed order: the result does not depend on workgroup timing).
 //   finalize  [hd, assd] as numpy.percentile (linear) and the mean over both edge sets; empty masks: NaN (both) / +inf (one).
+//
+// vsseg_surface_metrics is the same sequence with two additions, neither of which costs a launch or a byte of traffic: its first histogram pass,
+// which already holds every edge voxel's squared field value, also counts per direction and tolerance the edge voxels with field <= tau^2 (integer
+// atomics: LDS per workgroup, then one 64-bit add per non-zero counter), and its finalize also writes masd from the two per-direction sums and the
+// normalised surface Dice, surface precision and surface recall of every tolerance.  vsseg_surface_distances runs the kernels it always ran.
 #include <limits.h>
 #include <math.h>
 #include "common.h"
@@ -24,6 +29,7 @@ constexpr int ET_Y = 16, ET_Z = 64, ET_X = 16;    // edge pass: a workgroup owns
 constexpr int EW_Y = ET_Y + 2, EW_Z = ET_Z + 2;   // ... and stages each plane with a one-voxel halo
 constexpr int EDT_J = 4;                          // distance-transform outputs per thread and sweep over a line
 constexpr int SURF_MAX_EXTENT = 8192;             // a line of the transform fits 64 KiB of LDS
+constexpr int SURF_MAX_TOL = 8;                   // tolerances of one vsseg_surface_metrics call
 
 struct SurfRec {
   unsigned long long cnt[2];   // |E(P)|, |E(G)|
@@ -32,6 +38,12 @@ struct SurfRec {
   unsigned prefix[4];          // ... bits of the selected value found so far, most significant byte first
   double gamma[2];             // interpolation weight between the two order statistics of a direction
   unsigned hist[4][4][256];    // radix pass, selection, bin
+  unsigned long long within[2][SURF_MAX_TOL];  // direction, tolerance: edge voxels whose squared distance to the other edge set is <= tau^2
+};
+
+struct SurfTol {  // the tolerances of a call, by value in the kernel arguments
+  int n;
+  float t2[SURF_MAX_TOL];  // (float)(tau * tau), the product in fp64
 };
 
 struct SurfLayout {
@@ -208,11 +220,16 @@ __global__ __launch_bounds__(256) void surf_edt_kernel(const SurfRec* __restrict
 // Histogram pass `pass` (0: bits 31..24, ..., 3: bits 7..0) of the radix select over the distances at the edge voxels: d(P->G) = sqrt(field.x) at
 // E(P), d(G->P) = sqrt(field.y) at E(G).  A value counts for selection s when its higher bits equal the prefix found so far.  One wave per box row
 // (x, y), lanes along z; the row -> wave assignment depends on the box only, so pass 0's per-workgroup partial sums are reproducible.
+// TOL (pass 0 of vsseg_surface_metrics only): also count, per direction and tolerance, the values whose SQUARED distance, the field value itself, is
+// <= tol.t2 (a tie counts, +inf never does).  Edge voxels are a few thousand per volume, so the counts go through LDS atomics.
+template <bool TOL>
 __global__ __launch_bounds__(256) void surf_hist_kernel(SurfRec* __restrict__ rec, const uint8_t* __restrict__ edges, const float2* __restrict__ field, int Y, int Z, int pass,
-                                                       double* __restrict__ partial) {
+                                                       double* __restrict__ partial, SurfTol tol) {
   __shared__ unsigned h[4][256];
   __shared__ double red[4][2];
+  __shared__ unsigned within[2][SURF_MAX_TOL];
   for (int i = threadIdx.x; i < 4 * 256; i += 256) (&h[0][0])[i] = 0;
+  if (TOL && threadIdx.x < 2 * SURF_MAX_TOL) (&within[0][0])[threadIdx.x] = 0;
   __syncthreads();
   const int bx = rec->bmax[0] - rec->bmin[0] + 1, by = rec->bmax[1] - rec->bmin[1] + 1, bz = rec->bmax[2] - rec->bmin[2] + 1;
   const int shift = 24 - 8 * pass;
@@ -236,8 +253,12 @@ __global__ __launch_bounds__(256) void surf_hist_kernel(SurfRec* __restrict__ re
 #pragma unroll
       for (int d = 0; d < 2; ++d) {
         if (!((e >> d) & 1u)) continue;
-        const float v = sqrtf(d ? f.y : f.x);
+        const float f2 = d ? f.y : f.x;
+        const float v = sqrtf(f2);
         if (pass == 0) sum[d] += v;
+        if (TOL && f2 < __builtin_inff())
+          for (int t = 0; t < tol.n; ++t)
+            if (f2 <= tol.t2[t]) atomicAdd(&within[d][t], 1u);
         const unsigned u = __float_as_uint(v);
 #pragma unroll
         for (int t = 0; t < 2; ++t)
@@ -253,6 +274,10 @@ __global__ __launch_bounds__(256) void surf_hist_kernel(SurfRec* __restrict__ re
     for (int i = threadIdx.x; i < 4 * 256; i += 256) {
       const unsigned c = (&h[0][0])[i];
       if (c) atomicAdd(&rec->hist[pass][0][0] + i, c);
+    }
+    if (TOL && threadIdx.x < 2 * SURF_MAX_TOL) {  // (after the barrier above: every LDS count is final)
+      const unsigned c = (&within[0][0])[threadIdx.x];
+      if (c) atomicAdd(&rec->within[0][0] + threadIdx.x, (unsigned long long)c);
     }
   }
   if (pass == 0 && threadIdx.x < 2) partial[2 * blockIdx.x + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
@@ -310,7 +335,8 @@ __device__ __forceinline__ double surf_lerp(double a, double b, double t) {  // 
   return t >= 0.5 ? b - d * (1.0 - t) : a + d * t;
 }
 
-__global__ __launch_bounds__(256) void surf_finalize_kernel(const SurfRec* __restrict__ rec, const double* __restrict__ partial, float* __restrict__ out) {
+// ntol < 0: out = [hd, assd] (vsseg_surface_distances).  ntol >= 0: out = [hd, assd, masd] and [nsd, precision, recall] per tolerance.
+__global__ __launch_bounds__(256) void surf_finalize_kernel(const SurfRec* __restrict__ rec, const double* __restrict__ partial, float* __restrict__ out, int ntol) {
   __shared__ double red[2][256];
   const int t = threadIdx.x;
   double a = 0.0, b = 0.0;
@@ -336,6 +362,19 @@ __global__ __launch_bounds__(256) void surf_finalize_kernel(const SurfRec* __res
     }
     out[0] = hd;
     out[1] = assd;
+    if (ntol >= 0) {
+      const float NaN = __builtin_nanf("");
+      const bool both = n0 && n1;
+      // mean of the two directed means; one edge set empty: +inf like hd and assd, both empty: NaN
+      out[2] = both ? (float)((red[0][0] / (double)n0 + red[1][0] / (double)n1) * 0.5) : hd;
+      for (int k = 0; k < ntol; ++k) {
+        // one empty edge set: no voxel of the other is within any tolerance of it (the field there is +inf), so the counts are 0 already
+        const unsigned long long wp = both ? rec->within[0][k] : 0ull, wg = both ? rec->within[1][k] : 0ull;
+        out[3 + 3 * k] = (n0 + n1) ? (float)((double)(wp + wg) / (double)(n0 + n1)) : NaN;
+        out[4 + 3 * k] = n0 ? (float)((double)wp / (double)n0) : NaN;
+        out[5 + 3 * k] = n1 ? (float)((double)wg / (double)n1) : NaN;
+      }
+    }
   }
 }
 
@@ -359,25 +398,29 @@ extern "C" int64_t vsseg_surface_scratch_bytes(const int32_t dims[3]) {
   return surf_layout((int64_t)dims[0] * dims[1] * dims[2]).total;
 }
 
-extern "C" int vsseg_surface_distances(const float* logits, int32_t pitch, const float* label, const int32_t dims[3], const float spacing[3], double percentile, void* scratch,
-                                       int64_t scratch_bytes, float* out, void* stream) {
-  VSSEG_CHECK(logits && label && scratch && out && spacing, "vsseg_surface_distances: null pointer");
-  VSSEG_CHECK(pitch == 2, "vsseg_surface_distances: pitch must be 2 (channels-last two-class logits), got %d", pitch);
-  VSSEG_CHECK(surf_dims_ok(dims), "vsseg_surface_distances: dims must be 1 .. %d on every axis", SURF_MAX_EXTENT);
-  for (int a = 0; a < 3; ++a) VSSEG_CHECK(spacing[a] > 0.f && spacing[a] < __builtin_inff(), "vsseg_surface_distances: spacing[%d] = %g is not a positive finite value", a, (double)spacing[a]);
-  VSSEG_CHECK(percentile >= 0.0 && percentile <= 100.0, "vsseg_surface_distances: percentile %g outside [0, 100]", percentile);
+namespace {
+
+// The launch sequence of both entry points.  tol == nullptr: vsseg_surface_distances (two outputs, no counting); otherwise vsseg_surface_metrics.
+int surf_launch(const char* who, const float* logits, int32_t pitch, const float* label, const int32_t dims[3], const float spacing[3], double percentile, const SurfTol* tol,
+                void* scratch, int64_t scratch_bytes, float* out, void* stream) {
+  VSSEG_CHECK(logits && label && scratch && out && spacing, "%s: null pointer", who);
+  VSSEG_CHECK(pitch == 2, "%s: pitch must be 2 (channels-last two-class logits), got %d", who, pitch);
+  VSSEG_CHECK(surf_dims_ok(dims), "%s: dims must be 1 .. %d on every axis", who, SURF_MAX_EXTENT);
+  for (int a = 0; a < 3; ++a) VSSEG_CHECK(spacing[a] > 0.f && spacing[a] < __builtin_inff(), "%s: spacing[%d] = %g is not a positive finite value", who, a, (double)spacing[a]);
+  VSSEG_CHECK(percentile >= 0.0 && percentile <= 100.0, "%s: percentile %g outside [0, 100]", who, percentile);
   VSSEG_CHECK((reinterpret_cast<uintptr_t>(logits) & 7) == 0 && (reinterpret_cast<uintptr_t>(label) & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0 &&
                   (reinterpret_cast<uintptr_t>(scratch) & 255) == 0,
-              "vsseg_surface_distances: misaligned operand (logits 8 B, label / out 4 B, scratch 256 B)");
+              "%s: misaligned operand (logits 8 B, label / out 4 B, scratch 256 B)", who);
   const int X = dims[0], Y = dims[1], Z = dims[2];
   const SurfLayout l = surf_layout((int64_t)X * Y * Z);
-  VSSEG_CHECK(scratch_bytes >= l.total, "vsseg_surface_distances: %lld bytes of scratch, %lld needed (vsseg_surface_scratch_bytes)", (long long)scratch_bytes, (long long)l.total);
+  VSSEG_CHECK(scratch_bytes >= l.total, "%s: %lld bytes of scratch, %lld needed (vsseg_surface_scratch_bytes)", who, (long long)scratch_bytes, (long long)l.total);
   hipStream_t s = as_stream(stream);
   char* base = static_cast<char*>(scratch);
   SurfRec* rec = reinterpret_cast<SurfRec*>(base);
   double* partial = reinterpret_cast<double*>(base + l.partial);
   uint8_t* edges = reinterpret_cast<uint8_t*>(base + l.edges);
   float2* field = reinterpret_cast<float2*>(base + l.field);
+  const SurfTol none = {};
   hipLaunchKernelGGL(surf_init_kernel, dim3(1), dim3(256), 0, s, rec);
   hipLaunchKernelGGL(surf_edge_kernel, dim3((Z + ET_Z - 1) / ET_Z, (Y + ET_Y - 1) / ET_Y, (X + ET_X - 1) / ET_X), dim3(256), 0, s, logits, label, X, Y, Z, edges, rec);
   const int pz = surf_pt_log2(Z), py = surf_pt_log2(Y), px = surf_pt_log2(X);
@@ -385,10 +428,34 @@ extern "C" int vsseg_surface_distances(const float* logits, int32_t pitch, const
   hipLaunchKernelGGL(surf_edt_kernel<1>, dim3((Z + (1 << py) - 1) >> py, X), dim3(256), (size_t)Y * (8 << py), s, rec, edges, Y, Z, field, spacing[1], py);
   hipLaunchKernelGGL(surf_edt_kernel<0>, dim3((Z + (1 << px) - 1) >> px, Y), dim3(256), (size_t)X * (8 << px), s, rec, edges, Y, Z, field, spacing[0], px);
   for (int pass = 0; pass < 4; ++pass) {
-    hipLaunchKernelGGL(surf_hist_kernel, dim3(SURF_RB), dim3(256), 0, s, rec, edges, (const float2*)field, Y, Z, pass, partial);
+    if (pass == 0 && tol && tol->n > 0)
+      hipLaunchKernelGGL(surf_hist_kernel<true>, dim3(SURF_RB), dim3(256), 0, s, rec, edges, (const float2*)field, Y, Z, pass, partial, *tol);
+    else
+      hipLaunchKernelGGL(surf_hist_kernel<false>, dim3(SURF_RB), dim3(256), 0, s, rec, edges, (const float2*)field, Y, Z, pass, partial, none);
     hipLaunchKernelGGL(surf_select_kernel, dim3(1), dim3(256), 0, s, rec, pass, percentile / 100.0);
   }
-  hipLaunchKernelGGL(surf_finalize_kernel, dim3(1), dim3(256), 0, s, (const SurfRec*)rec, (const double*)partial, out);
-  VSSEG_LAUNCH_CHECK("vsseg_surface_distances");
+  hipLaunchKernelGGL(surf_finalize_kernel, dim3(1), dim3(256), 0, s, (const SurfRec*)rec, (const double*)partial, out, tol ? tol->n : -1);
+  VSSEG_LAUNCH_CHECK(who);
   return VSSEG_OK;
+}
+
+}  // namespace
+
+extern "C" int vsseg_surface_distances(const float* logits, int32_t pitch, const float* label, const int32_t dims[3], const float spacing[3], double percentile, void* scratch,
+                                       int64_t scratch_bytes, float* out, void* stream) {
+  return surf_launch("vsseg_surface_distances", logits, pitch, label, dims, spacing, percentile, nullptr, scratch, scratch_bytes, out, stream);
+}
+
+extern "C" int vsseg_surface_metrics(const float* logits, int32_t pitch, const float* label, const int32_t dims[3], const float spacing[3], double percentile,
+                                     const float* tolerances_mm, int32_t ntol, void* scratch, int64_t scratch_bytes, float* out, void* stream) {
+  VSSEG_CHECK(ntol >= 0 && ntol <= SURF_MAX_TOL, "vsseg_surface_metrics: ntol = %d outside 0 .. %d", ntol, SURF_MAX_TOL);
+  VSSEG_CHECK(ntol == 0 || tolerances_mm, "vsseg_surface_metrics: tolerances_mm is a null pointer with ntol = %d", ntol);
+  SurfTol tol = {};
+  tol.n = ntol;
+  for (int t = 0; t < ntol; ++t) {
+    const float tau = tolerances_mm[t];
+    VSSEG_CHECK(tau >= 0.f && tau < __builtin_inff(), "vsseg_surface_metrics: tolerances_mm[%d] = %g is not a finite value >= 0", t, (double)tau);
+    tol.t2[t] = (float)((double)tau * (double)tau);
+  }
+  return surf_launch("vsseg_surface_metrics", logits, pitch, label, dims, spacing, percentile, &tol, scratch, scratch_bytes, out, stream);
 }

@@ -29,7 +29,7 @@ import torch
 from . import SGD, Adam, AdamW, Dice_spvPA, UNet2d5_spvPA, check_ce, check_ce_topk, check_optimizer, compute_dice_score, poly_lr, sliding_window_inference
 from .optim import DEFAULT_WEIGHT_DECAY, LR_SCHEDULES, OPTIMIZERS
 from .inferers import argmax_segmentation, tta_masks
-from .metrics import MEASUREMENT_FIELDS, compute_measurements, compute_surface_distances, voxel_spacing
+from .metrics import MEASUREMENT_FIELDS, check_tolerances, compute_measurements, compute_surface_distances, compute_surface_metrics, surface_metric_fields, voxel_spacing
 from .postprocess import connected_components, fill_holes, keep_largest_component, min_component_voxels, remove_small_components
 from . import parallel as DP
 from .data import nifti
@@ -46,6 +46,11 @@ HP = dict(
 def postprocessing_csv_header(fill_holes: bool, min_component: bool) -> str:
     """Columns of figures/test_postprocessing.csv: the six of --keep_largest_component, then those of --fill_holes and of --min_component_mm3 as switched on."""
     return "case,dice_raw,dice,components,foreground_voxels,kept_voxels" + (",holes,filled_voxels" if fill_holes else "") + (",small_components,small_voxels" if min_component else "")
+
+
+def surface_dice_csv_header(tolerances) -> str:
+    """Columns of figures/test_surface_dice.csv: case, dice, masd_mm, then nsd, surface precision and surface recall per tolerance of --surface_dice_mm."""
+    return "case,dice,masd_mm," + ",".join(surface_metric_fields(tolerances)[3:])
 
 
 class CachedLoader:
@@ -100,6 +105,7 @@ class VSparams:
         parser.add_argument("--compute_dtype", type=str, default="bf16", choices=["bf16", "fp32"], help="bf16 MFMA (benchmark) or exact-fp32 MFMA (parity)")
         parser.add_argument("--num_epochs", type=int, default=None)
         parser.add_argument("--surface_metrics", action="store_true", help="run_inference also reports HD95 and ASSD per test case (mm, on the GPU) and writes figures/test_surface_metrics.csv")
+        parser.add_argument("--surface_dice_mm", type=float, nargs="+", default=None, metavar="TAU", help="run_inference also reports per test case the normalised surface Dice (the share of the two boundaries within TAU mm of the other one), the surface precision and recall at each of 1 to 8 distinct tolerances and the mean of the two directed mean surface distances (on the GPU, from the one edge pass and distance transform that also serve --surface_metrics), and writes figures/test_surface_dice.csv")
         parser.add_argument("--keep_largest_component", action="store_true", help="run_inference keeps only the largest connected component of each predicted segmentation (on the GPU) before the Dice, the surface metrics and the NIfTI export, and writes figures/test_postprocessing.csv")
         parser.add_argument("--measurements", action="store_true", help="run_inference also reports per test case the volume (mm^3), the largest 3-D diameter and the largest diameter within an axial slice (mm) of the predicted and of the manual segmentation and the distance between their centres of mass (on the GPU), and writes figures/test_measurements.csv")
         parser.add_argument("--component_connectivity", type=int, default=26, choices=[6, 18, 26], help="voxel connectivity of --keep_largest_component and --min_component_mm3 (26: MONAI's KeepLargestConnectedComponent)")
@@ -141,6 +147,7 @@ class VSparams:
             field = check_field_augment(args.aug_elastic_mag, args.aug_bias_field, args.aug_field_spacing)
             appearance = check_appearance_augment(*(getattr(args, "aug_" + k) for k in APPEARANCE_KEYS))
             min_component_voxels(args.min_component_mm3, (1.0, 1.0, 1.0))  # a finite value >= 0
+            surface_dice_mm = tuple(sorted(check_tolerances(args.surface_dice_mm or (), "--surface_dice_mm", distinct=True)))
         except ValueError as e:
             parser.error(str(e))
 
@@ -165,6 +172,7 @@ class VSparams:
         self.export_inferred_segmentations = True
         self.compute_dtype = args.compute_dtype
         self.surface_metrics = args.surface_metrics
+        self.surface_dice_mm = surface_dice_mm  # () = off
         self.measurements = args.measurements
         self.keep_largest_component, self.component_connectivity = args.keep_largest_component, args.component_connectivity
         self.fill_holes, self.hole_connectivity, self.min_component_mm3 = args.fill_holes, args.hole_connectivity, float(args.min_component_mm3)
@@ -206,7 +214,7 @@ class VSparams:
         log("Parameters: ")
         for k in ("dataset", "data_root", "split_csv", "pad_crop_shape", "pad_crop_shape_test", "num_workers", "torch_device_arg", "train_batch_size", "initial_learning_rate",
                   "epochs_with_const_lr", "lr_divisor", "weight_decay", "num_epochs", "val_interval", "model", "sliding_window_inferer_roi_size", "attention", "hardness",
-                  "results_folder_path", "export_inferred_segmentations", "compute_dtype") + (("surface_metrics",) if self.surface_metrics else ()) + (("measurements",) if self.measurements else ()) + (
+                  "results_folder_path", "export_inferred_segmentations", "compute_dtype") + (("surface_metrics",) if self.surface_metrics else ()) + (("surface_dice_mm",) if self.surface_dice_mm else ()) + (("measurements",) if self.measurements else ()) + (
                       ("fill_holes", "hole_connectivity") if self.fill_holes else ()) + (("min_component_mm3",) if self.min_component_mm3 > 0 else ()) + (
                       ("keep_largest_component", "component_connectivity") if self.keep_largest_component else ("component_connectivity",) if self.min_component_mm3 > 0 else ()) + (("tta_flips", "tta_average") if self.tta_flips else ()) + (
                           tuple("aug_" + k for k in AUGMENT_KEYS) if any(self.augment.values()) else ()) + (
@@ -462,6 +470,8 @@ class VSparams:
         post_rows = 4 + 2 * self.fill_holes + 2 * small if (self.fill_holes or small or self.keep_largest_component) else 0
         post_dev = torch.zeros((post_rows, n), dtype=torch.float64, device=self.device) if post_rows else None
         meas_dev = torch.zeros((len(MEASUREMENT_FIELDS), n), dtype=torch.float64, device=self.device) if self.measurements else None  # --measurements: the nine values per case
+        # --surface_dice_mm: [masd, then nsd, surface precision, surface recall per tolerance] per case
+        sdice_dev = torch.zeros((1 + 3 * len(self.surface_dice_mm), n), dtype=torch.float32, device=self.device) if self.surface_dice_mm else None
         predictor = model.segmentation_predictor() if hasattr(model, "segmentation_predictor") else (lambda *a, **k: model(*a, **k)[0])  # model_segmentation, ref:params/VSparams.py:560
         mine = DP.shard_indices(n)  # the unpadded, unshuffled test loader yields exactly these cases, in this order
         with torch.no_grad():
@@ -475,18 +485,25 @@ class VSparams:
                     post_dev[0, gi] = self.compute_dice_score(outputs, data["label"]).reshape(())
                     outputs, post_dev[1:, gi] = self._postprocess(outputs, voxel_spacing(data["label_meta_dict"]["affine"]))
                 dice_dev[gi] = self.compute_dice_score(outputs, data["label"]).reshape(())
-                if surf_dev is not None:
+                if sdice_dev is not None:  # one call: its first two columns are the bits compute_surface_distances returns
+                    sm = compute_surface_metrics(outputs, data["label"], voxel_spacing(data["label_meta_dict"]["affine"]), 95.0, self.surface_dice_mm)[0]
+                    sdice_dev[:, gi] = sm[2:]
+                    if surf_dev is not None:
+                        surf_dev[:, gi] = sm[:2]
+                elif surf_dev is not None:
                     surf_dev[:, gi] = compute_surface_distances(outputs, data["label"], voxel_spacing(data["label_meta_dict"]["affine"]), 95.0)[0]
                 if meas_dev is not None:
                     meas_dev[:, gi] = compute_measurements(outputs, data["label"], voxel_spacing(data["label_meta_dict"]["affine"]))[0]
                 if self.export_inferred_segmentations:
                     self.export_segmentation(outputs, data["label_meta_dict"])
-        surf = post = meas = None
-        if surf_dev is not None or post_dev is not None or meas_dev is not None:
-            rows = [dice_dev[None]] + [r for r in (surf_dev, post_dev, meas_dev) if r is not None]
+        surf = post = meas = sdice = None
+        if surf_dev is not None or post_dev is not None or meas_dev is not None or sdice_dev is not None:
+            rows = [dice_dev[None]] + [r for r in (surf_dev, post_dev, meas_dev, sdice_dev) if r is not None]
             both = torch.cat(rows)  # one all-reduce; a case that is not this rank's is 0 here (NaN / inf + 0 stay NaN / inf)
             both = (DP.allreduce_sum(both) if self.world > 1 else both).double().cpu().numpy()
             dice_scores = both[0]
+            if sdice_dev is not None:
+                both, sdice = both[:-len(sdice_dev)], both[-len(sdice_dev):]
             if surf_dev is not None:
                 surf = both[1:3]
             if meas_dev is not None:
@@ -503,6 +520,8 @@ class VSparams:
             self._log_postprocessing(dice_scores, *post)
         if surf is not None:
             self._log_surface_metrics(dice_scores, surf[0], surf[1])
+        if sdice is not None:
+            self._log_surface_dice(dice_scores, sdice)
         if meas is not None:
             self._log_measurements(dice_scores, meas)
         return dice_scores
@@ -572,6 +591,25 @@ class VSparams:
                 f.write("case,dice,hd95_mm,assd_mm\n")
                 for i, (d, h, a) in enumerate(zip(dice, hd95, assd)):
                     f.write(f"{i},{float(d)!r},{float(h)!r},{float(a)!r}\n")
+
+    def _log_surface_dice(self, dice, rows):
+        """Per-case lines of --surface_dice_mm (masd, then nsd / surface precision / surface recall per tolerance), their mean +- std over the finite cases, and
+        figures/test_surface_dice.csv (rank 0)."""
+        log = self.logger.info
+        names = ("masd_mm",) + surface_metric_fields(self.surface_dice_mm)[3:]
+        for i in range(len(dice)):
+            for name, v in zip(names, rows):
+                log(f"{name}[{i}] = {v[i]}")
+        for name, v in zip(names, rows):
+            fin = v[np.isfinite(v)]
+            m, sd = (fin.mean(), fin.std()) if len(fin) else (float("nan"), float("nan"))
+            log(f"mean_{name} = {m} +- {sd} ({len(v) - len(fin)} of {len(v)} cases non-finite)")
+        if self.rank == 0:
+            os.makedirs(self.figures_path, exist_ok=True)
+            with open(os.path.join(self.figures_path, "test_surface_dice.csv"), "w") as f:
+                f.write(surface_dice_csv_header(self.surface_dice_mm) + "\n")
+                for i, d in enumerate(dice):
+                    f.write(",".join([str(i), repr(float(d))] + [repr(float(v[i])) for v in rows]) + "\n")
 
     def _log_measurements(self, dice, meas):
         """Per-case volume / centroid / diameter lines of --measurements, the volume and diameter errors over the cases, and figures/test_measurements.csv (rank 0)."""
