@@ -106,7 +106,7 @@ __global__ __launch_bounds__(DICE_THREADS) void dice_pred_sums_kernel(const floa
   block_reduce_add(acc, 6, sums + (int64_t)b * 6, VSSEG_FX_DICE, fxflag);
 }
 extern "C" int vsseg_dice_pred_sums(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, double* sums, void* stream) {
-  VSSEG_CHECK(logits && label && sums && pitch >= 2 && pitch % 2 == 0 && n >= 1, "vsseg_dice_pred_sums: bad arguments");
+  VSSEG_CHECK(logits && label && sums && pitch >= 2 && pitch % 2 == 0 && n >= 1 && nvox >= 1, "vsseg_dice_pred_sums: bad arguments");
   dim3 g(dice_blocks(nvox / 4, n), n);
   VSSEG_FX_FLAG(fxflag, "vsseg_dice_pred_sums");
   hipLaunchKernelGGL(dice_pred_sums_kernel, g, dim3(DICE_THREADS), 0, as_stream(stream), logits, pitch, label, nvox, hardness, sums, fxflag);
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(DICE_THREADS) void dice_att_sums_kernel(const float
   block_reduce_add(acc, 3, sums + (int64_t)b * 3, VSSEG_FX_DICE, fxflag);
 }
 extern "C" int vsseg_dice_att_sums(const float* att, const float* label, int32_t n, int64_t nvox, double* sums, void* stream) {
-  VSSEG_CHECK(att && label && sums && n >= 1, "vsseg_dice_att_sums: bad arguments");
+  VSSEG_CHECK(att && label && sums && n >= 1 && nvox >= 1, "vsseg_dice_att_sums: bad arguments");
   dim3 g(dice_blocks(nvox / 4, n), n);
   VSSEG_FX_FLAG(fxflag, "vsseg_dice_att_sums");
   hipLaunchKernelGGL(dice_att_sums_kernel, g, dim3(DICE_THREADS), 0, as_stream(stream), att, label, nvox, sums, fxflag);
@@ -533,7 +533,7 @@ template <int OUT, int CE> __global__ __launch_bounds__(256) void dice_pred_bwd_
 template <int CE>
 static int dice_pred_bwd_launch(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* ce_coef, const float* gscale, void* dst, int out, int dpitch,
                                 void* stream, const char* who) {
-  VSSEG_CHECK(logits && label && coef && dst && pitch >= 2 && pitch % 2 == 0 && n >= 1 && (!CE || ce_coef), "%s: bad arguments", who);
+  VSSEG_CHECK(logits && label && coef && dst && pitch >= 2 && pitch % 2 == 0 && n >= 1 && nvox >= 1 && (!CE || ce_coef), "%s: bad arguments", who);
   dim3 g(grid_for((nvox + 3) / 4, 256, 2048), n), t(256);
   hipStream_t s = as_stream(stream);
   if (out == 0) hipLaunchKernelGGL((dice_pred_bwd_kernel<0, CE>), g, t, 0, s, logits, pitch, label, nvox, hardness, coef, gscale, dst, 2, ce_coef);
@@ -602,7 +602,7 @@ __global__ void dice_att_bwd_kernel(const float* __restrict__ label, int64_t nvo
 }
 extern "C" int vsseg_dice_att_bwd(const float* label, int32_t n, int64_t nvox, const float* coef, float inv_levels, const float* gscale, float* datt, void* stream) {
   (void)inv_levels;  // the 1/L factor is already folded into coef by vsseg_dice_finalize
-  VSSEG_CHECK(label && coef && datt, "vsseg_dice_att_bwd: bad arguments");
+  VSSEG_CHECK(label && coef && datt && n >= 1 && nvox >= 1, "vsseg_dice_att_bwd: bad arguments");
   dim3 g(grid_for((nvox + 3) / 4, 256, 2048), n);
   hipLaunchKernelGGL(dice_att_bwd_kernel, g, dim3(256), 0, as_stream(stream), label, nvox, coef, gscale, datt);
   VSSEG_LAUNCH_CHECK("vsseg_dice_att_bwd");
