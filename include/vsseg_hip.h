@@ -235,7 +235,7 @@ int vsseg_fork_event_destroy(void* ev);
 int vsseg_fork_arm(void* ev);
 int vsseg_fork_disarm(void);
 int vsseg_stream_wait_event(void* stream, void* ev);
-int vsseg_version(void); /* 19: + vsseg_surface_metrics; 18: + vsseg_fill_holes, vsseg_remove_small_components; 17: + vsseg_measure_scratch_bytes, vsseg_measurements; 16: + vsseg_topk_scratch_bytes, vsseg_topk_select, vsseg_ce_topk_select, vsseg_dice_ce_topk_finalize, vsseg_dice_ce_topk_pred_bwd, vsseg_dice_ce_topk_pred_bwd_to; 15: + vsseg_grad_norm_scratch_bytes, vsseg_grad_norm, vsseg_sgd, vsseg_adam_clipped, vsseg_clip_record; 14: + vsseg_ce_sums, vsseg_dice_ce_finalize, vsseg_dice_ce_pred_bwd, vsseg_dice_ce_pred_bwd_to; 13: + vsseg_patch_filter, vsseg_patch_tone; 12: + vsseg_crop_field, vsseg_field_job; 11: + vsseg_crop_affine, vsseg_affine_job; 10: + vsseg_swi_finalize_mirrored, vsseg_crop_job.flip is a three-axis mirror mask (was flip_x); 9: + vsseg_components_scratch_bytes, vsseg_components_label, vsseg_keep_largest_component; 8: + vsseg_surface_distances, vsseg_surface_scratch_bytes; 7: + vsseg_dice_pred_bwd_to, vsseg_dice_level_sums, vsseg_dice_tail_sums, vsseg_dice_att_bwd_levels, vsseg_fork_*, vsseg_stream_wait_event; 6: + launch plans with depth -8 (transition kernel) and -9 (gathering marching kernel); 5: vsseg_wgrad march = 2 (compute weight-gradient kernel), + vsseg_conv_to1, vsseg_conv_chain_desc without h_out (the training variant measured no gain and was deleted); 4: + vsseg_conv_chain; 3: the BatchNorm-block-on-load fields (in_bn_*, keep_*, x_bn_*: round-4 experiment, measured a loss, deleted) left the descriptors, depth -7 plans;
+int vsseg_version(void); /* 20: + vsseg_loss_opts, vsseg_ce_focal_sums, vsseg_loss_finalize, vsseg_loss_pred_bwd, vsseg_loss_pred_bwd_to; 19: + vsseg_surface_metrics; 18: + vsseg_fill_holes, vsseg_remove_small_components; 17: + vsseg_measure_scratch_bytes, vsseg_measurements; 16: + vsseg_topk_scratch_bytes, vsseg_topk_select, vsseg_ce_topk_select, vsseg_dice_ce_topk_finalize, vsseg_dice_ce_topk_pred_bwd, vsseg_dice_ce_topk_pred_bwd_to; 15: + vsseg_grad_norm_scratch_bytes, vsseg_grad_norm, vsseg_sgd, vsseg_adam_clipped, vsseg_clip_record; 14: + vsseg_ce_sums, vsseg_dice_ce_finalize, vsseg_dice_ce_pred_bwd, vsseg_dice_ce_pred_bwd_to; 13: + vsseg_patch_filter, vsseg_patch_tone; 12: + vsseg_crop_field, vsseg_field_job; 11: + vsseg_crop_affine, vsseg_affine_job; 10: + vsseg_swi_finalize_mirrored, vsseg_crop_job.flip is a three-axis mirror mask (was flip_x); 9: + vsseg_components_scratch_bytes, vsseg_components_label, vsseg_keep_largest_component; 8: + vsseg_surface_distances, vsseg_surface_scratch_bytes; 7: + vsseg_dice_pred_bwd_to, vsseg_dice_level_sums, vsseg_dice_tail_sums, vsseg_dice_att_bwd_levels, vsseg_fork_*, vsseg_stream_wait_event; 6: + launch plans with depth -8 (transition kernel) and -9 (gathering marching kernel); 5: vsseg_wgrad march = 2 (compute weight-gradient kernel), + vsseg_conv_to1, vsseg_conv_chain_desc without h_out (the training variant measured no gain and was deleted); 4: + vsseg_conv_chain; 3: the BatchNorm-block-on-load fields (in_bn_*, keep_*, x_bn_*: round-4 experiment, measured a loss, deleted) left the descriptors, depth -7 plans;
                             * 2: fixed-point accumulators documented + vsseg_fx_status; 1: the buffers below were described as plain doubles */
 
 /* ---- Accumulator buffers are 64-bit FIXED-POINT integers, not doubles ------------------------------------------------------------------
@@ -250,7 +250,7 @@ int vsseg_version(void); /* 19: + vsseg_surface_metrics; 18: + vsseg_fill_holes,
  *     VSSEG_FX_DICE_SCALE  2^32  Dice sums (pred_sums, att_sums)                              per-workgroup partial |v| < 1.0e6
  * (vsseg_hard_dice_counts keeps REAL doubles: its sums are integers, exact in fp64 in any order.)
  * A partial sum outside its range, or a NaN / Inf one, is clamped and sets a sticky per-process device flag; while the flag is set the decoding
- * kernels (vsseg_bn_finalize, vsseg_bn_act_bwd_finalize, vsseg_dice_finalize, vsseg_dice_ce_finalize, vsseg_dice_ce_topk_finalize) return NaN, so a diverging run or an out-of-range loss scale
+ * kernels (vsseg_bn_finalize, vsseg_bn_act_bwd_finalize, vsseg_dice_finalize, vsseg_dice_ce_finalize, vsseg_dice_ce_topk_finalize, vsseg_loss_finalize) return NaN, so a diverging run or an out-of-range loss scale
  * surfaces as NaN in the loss / statistics / gradients instead of as wrapped integers.  vsseg_fx_status reads (and optionally clears) the flag. */
 typedef double vsseg_fx_acc; /* one accumulator slot (reinterpret as int64_t) */
 #define VSSEG_FX_STAT_SCALE 1048576.0
@@ -457,6 +457,57 @@ int vsseg_dice_ce_topk_pred_bwd(const float* logits, int32_t pitch, const float*
                                 void* stream);
 int vsseg_dice_ce_topk_pred_bwd_to(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* topk_coef, const float* gscale, vsseg_tensor dst,
                                    void* stream);
+
+/* Region and focal options of the loss for small lesions (ABI version 20): the Tversky index (Salehi 2017; MONAI's TverskyLoss), its focal variant (Abraham 2019), one
+ * ratio over the pooled sums of the batch (nnU-Net's batch_dice) and the focal cross-entropy (MONAI's DiceFocalLoss) — with the two Tversky terms the "Unified Focal" family
+ * of Yeung 2022.  I, G, P are the three sums of a ratio as above (per sample and class for the logits, hardness-weighted when that is on; per level and sample for the
+ * attention maps), eps = 1e-5, beta = tversky_beta in (0, 1), alpha = 1 - beta, gamma = focal_tversky_gamma in [0.25, 4]:
+ *     T = (2 I + eps) / (2 a_P P + 2 a_G G + eps),   u = 1 - T,   term = u when gamma == 1, max(u, 1e-7)^gamma otherwise
+ *   (a_P, a_G) = (alpha, beta) for the foreground class of the logits and for every attention map: a_P weights the false positives P - I, a_G the false negatives G - I;
+ *   the background class of the logits is mirrored, (a_P, a_G) = (beta, alpha): its false positives are the foreground's false negatives.  beta > 0.5 makes a missed
+ *   tumour voxel cost more than a false positive; beta = 0.5 is the Dice ratio (2 I + eps) / (G + P + eps).
+ *   The floor 1e-7 is part of the definition (with gamma < 1 the derivative gamma u^(gamma - 1) is unbounded at a perfect prediction): below it the term is the constant
+ *   1e-7^gamma and every coefficient of that ratio is 0.
+ *   batch_dice: I, G, P are summed over the n samples of the call before the ratio is formed — one ratio per class, one per level; under data parallelism these are the
+ *   samples of the rank (no collective).  The weights of the terms are unchanged: the mean over the 2 n (or 2 pooled) logits ratios plus 1 / L times the mean over each
+ *   level's ratios.
+ *   coefficients: with `region` the finalize leaves THREE per logits ratio, coef[n][2][3] = (dL/dI, dL/dG, dL/dP), followed by the attention maps' [levels][n][2] =
+ *   (dL/dI, dL/dP) as before — vsseg_dice_att_bwd / _levels serve unchanged, given the slice at coef + 6 n.  Pooled ratios write the same coefficients for every sample.
+ *   With region == 0 the layout is vsseg_dice_finalize's ([n][2][2] + [levels][n][2]) and so are the values.
+ * Focal cross-entropy, gamma_c = ce_focal_gamma in [0, 5] (ce_mode VSSEG_CE_FOCAL), with y, z = x[1-y] - x[y], w and W = N_bg + w_fg N_fg of the plain term above:
+ *     loss += ce_weight * sum_{b,v} w[y] q^gamma_c softplus(z) / W,   q = sigmoid(z) = 1 - p_y        (gamma_c -> 0: the plain term)
+ *   value     q^gamma_c = exp(-gamma_c softplus(-z)) — never log(q) of a rounded probability: finite for every finite logit
+ *   gradient  dz = ce_weight w[y] / W * q^gamma_c * (gamma_c (1 - q) softplus(z) + q) goes to the OTHER class's logit and -dz to the label's own
+ * vsseg_ce_focal_sums — vsseg_ce_sums with the focal factor: the same three slots (S_bg, S_fg, N_fg) at scale VSSEG_FX_STAT_SCALE; q^gamma_c <= 1 bounds the values by
+ *   the plain term's.  A NaN logit sets the sticky flag.
+ * vsseg_loss_finalize — the finalize of every combination: `ce_state` is ce_sums (VSSEG_CE_PLAIN, VSSEG_CE_FOCAL: ce_coef[2] as vsseg_dice_ce_finalize leaves it), the
+ *   select's scratch (VSSEG_CE_TOPK: ce_coef[8] as vsseg_dice_ce_topk_finalize leaves it) or NULL (VSSEG_CE_NONE).  nvox: voxels per sample.
+ * vsseg_loss_pred_bwd / _to — d(loss)/d(logits) of every combination, fp32 tensor / staged layouts (vsseg_dice_pred_bwd_to's).  Per voxel, with g the one-hot label,
+ *   s = d w / d p and t = d(w p) / d p of the hardness weight (0 and 1 without it): d/dp = A g t + B_G g s + B_P t with (A, B_G, B_P) = coef of the ratio.
+ * Every number of the record is checked before anything is launched (VSSEG_EINVAL); nothing is read by the host; while the fixed-point flag is set the loss and all
+ * coefficients are NaN. */
+#define VSSEG_CE_NONE 0
+#define VSSEG_CE_PLAIN 1
+#define VSSEG_CE_TOPK 2
+#define VSSEG_CE_FOCAL 3
+typedef struct {
+  int32_t region;              /* 0: the Dice ratio per sample, two coefficients per ratio (vsseg_dice_finalize); 1: the ratio above, three per logits ratio */
+  int32_t batch_dice;          /* 1: pool the sums of the n samples before the ratio (needs region) */
+  double tversky_beta;         /* in (0, 1)      (read with region) */
+  double focal_tversky_gamma;  /* in [0.25, 4]   (read with region) */
+  int32_t ce_mode;             /* VSSEG_CE_* */
+  int32_t reserved;            /* 0 */
+  double ce_weight;            /* finite, >= 0   (read with ce_mode != VSSEG_CE_NONE, as the two below) */
+  double ce_foreground_weight; /* finite, > 0 */
+  double ce_focal_gamma;       /* in [0, 5]      (read with VSSEG_CE_FOCAL) */
+} vsseg_loss_opts;
+int vsseg_ce_focal_sums(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, double ce_focal_gamma, double* ce_sums /* [3] */, void* stream);
+int vsseg_loss_finalize(const double* pred_sums, const double* att_sums, int32_t n, int32_t nlevels, const void* ce_state, int64_t nvox, const vsseg_loss_opts* opts, float* loss, float* coef, float* ce_coef,
+                        void* stream);
+int vsseg_loss_pred_bwd(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* ce_coef, const vsseg_loss_opts* opts, const float* gscale,
+                        float* dlogits, void* stream);
+int vsseg_loss_pred_bwd_to(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* ce_coef, const vsseg_loss_opts* opts, const float* gscale,
+                           vsseg_tensor dst, void* stream);
 
 /* torch.optim.Adam(lr, weight_decay) over the flat parameter buffer (ref:params/VSparams.py:388-391,462). */
 int vsseg_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float wd, float bc1, float bc2, float gscale, void* stream);

@@ -12,6 +12,12 @@ With --ce_topk PCT as well it times the top-k term (Dice_spvPA(ce_topk=PCT)): th
 in the same process, at the same two shapes, for N(0, 1) logits and for the confident logits of a trained network, and the launches of the top-k term one by one.
 
     python tools/bench_loss.py --ce_weight 1 --ce_topk 10        # profiles/topk_loss_bench.txt
+
+With any of --tversky_beta BETA, --focal_tversky_gamma GAMMA, --batch_dice, --ce_focal_gamma GAMMA it times the region and focal options (Dice_spvPA(tversky_beta=, ...)): the
+loss phase of the plain loss, of the region options alone, of the plain cross-entropy term, of the focal term and of everything together, alternating in one process, at
+the same two shapes, and the focal sums pass and backward beside the plain term's.
+
+    python tools/bench_loss.py --ce_weight 1 --tversky_beta 0.7 --focal_tversky_gamma 0.75 --batch_dice --ce_focal_gamma 2        # profiles/region_loss_bench.txt
 """
 import argparse
 import os
@@ -146,6 +152,78 @@ def bench_topk(lam, wfg, pct, shapes):
             print(f"  vsseg_ce_sums (the plain term's pass) {t:6.1f} us")
 
 
+def bench_region(lam, wfg, region, gc, shapes):
+    """The loss phase of the plain loss, the region options alone, the plain cross-entropy term, the focal term and all together, alternating in one process (three rounds
+    each, the median), and the launches the focal term adds or changes beside the plain term's."""
+    import vs_seg_amd as V
+
+    lib = L.lib()
+    S = torch.cuda.current_stream().cuda_stream
+    ratios = [(2, 2, 1), (2, 2, 1), (2, 2, 2), (2, 2, 2), (2, 2, 2)]
+    rk = dict(tversky_beta=region[0], focal_tversky_gamma=region[1], batch_dice=region[2]) if region else dict(tversky_beta=0.5)
+    gc = gc or 2.0
+    lam = lam or 1.0
+    print(f"loss phase of the fused train step (forward_backward_into, bf16 gradient of the logits): region options {rk}, ce_weight {lam}, ce_foreground_weight {wfg}, ce_focal_gamma {gc}")
+    for B, d0 in shapes:
+        dims = [d0]
+        for r in ratios:
+            dims.append(tuple(x // y for x, y in zip(dims[-1], r)))
+        nvox = d0[0] * d0[1] * d0[2]
+        budget = {(4, (384, 128, 128)): 259.0, (2, (384, 384, 64)): 227.0}.get((B, d0))
+        torch.manual_seed(0)
+        lg = torch.randn(B, *d0, 2, device="cuda")
+        logits = lg.permute(0, 4, 1, 2, 3)  # channels-last storage, as the network hands it out
+        lab = (torch.rand(B, 1, *d0, device="cuda") > 0.999).float()  # about one voxel in a thousand
+        atts = [torch.rand(B, 1, *d, device="cuda") for d in reversed(dims)]
+        dst = torch.empty(B, *d0, 2, device="cuda", dtype=torch.bfloat16)
+        bufs = [torch.empty(B, *a.shape[2:], device="cuda") for a in atts]
+        landing = (L.Tensor(dst.data_ptr(), L.BF16, 2, 2, B, *d0), bufs)
+        mk = lambda **kw: V.Dice_spvPA(to_onehot_y=True, softmax=True, **kw)  # noqa: E731
+        fns = [("plain loss", mk()), ("region options", mk(**rk)), (f"ce_weight {lam:g}", mk(ce_weight=lam, ce_foreground_weight=wfg)),
+               (f"ce_weight {lam:g} focal {gc:g}", mk(ce_weight=lam, ce_foreground_weight=wfg, ce_focal_gamma=gc)),
+               ("region options + focal", mk(ce_weight=lam, ce_foreground_weight=wfg, ce_focal_gamma=gc, **rk))]
+        times = [[] for _ in fns]
+        for _ in range(3):
+            for t, (_, fn) in zip(times, fns):
+                t.append(timed(lambda: fn.forward_backward_into((logits, atts), lab, landing)))
+        med = [sorted(t)[1] for t in times]
+        losses = [float(fn.forward_backward_into((logits, atts), lab, landing)[0]) for _, fn in fns]
+        print(f"batch {B} of {d0[0]}x{d0[1]}x{d0[2]} ({B * nvox / 1e6:.1f} M voxels): losses {', '.join(f'{v:.6f}' for v in losses)}")
+        for (name, _), m, t in zip(fns, med, times):
+            print(f"  loss phase, {name:<28s} {m:8.1f} us   (rounds: {', '.join(f'{x:.1f}' for x in t)})")
+        print(f"  region options against the plain loss    {med[1] - med[0]:8.1f} us")
+        print(f"  focal term against the plain term        {med[3] - med[2]:8.1f} us")
+        print(f"  everything against the plain loss        {med[4] - med[0]:8.1f} us" + (f"   (budget of an optional family: 1 % of the step = {budget:.0f} us)" if budget else ""))
+        sums = torch.zeros(3, dtype=torch.float64, device="cuda")
+        coef = torch.full((B * 6,), 1e-6, device="cuda")
+        cek = torch.full((2,), 1e-8, device="cuda")
+        l2 = lab.reshape(B, *d0)
+        t0 = timed(lambda: lib.vsseg_ce_sums(lg.data_ptr(), 2, l2.data_ptr(), B, nvox, sums.data_ptr(), S))
+        t1 = timed(lambda: lib.vsseg_ce_focal_sums(lg.data_ptr(), 2, l2.data_ptr(), B, nvox, gc, sums.data_ptr(), S))
+        print(f"  vsseg_ce_sums                 {t0:8.1f} us   ({B * nvox * 12 / t0 / 1e6:.2f} TB/s over logits + label)")
+        print(f"  vsseg_ce_focal_sums           {t1:8.1f} us   ({B * nvox * 12 / t1 / 1e6:.2f} TB/s, {t1 - t0:+.1f} us)")
+        o = L.LossOpts()
+        o.ce_mode, o.ce_weight, o.ce_foreground_weight, o.ce_focal_gamma, o.tversky_beta, o.focal_tversky_gamma = L.CE_FOCAL, lam, wfg, gc, rk["tversky_beta"], rk.get("focal_tversky_gamma", 1.0)
+        t0 = timed(lambda: lib.vsseg_dice_ce_pred_bwd_to(lg.data_ptr(), 2, l2.data_ptr(), B, nvox, 1, coef.data_ptr(), cek.data_ptr(), None, landing[0], S))
+        t1 = timed(lambda: L.check(lib.vsseg_loss_pred_bwd_to(lg.data_ptr(), 2, l2.data_ptr(), B, nvox, 1, coef.data_ptr(), cek.data_ptr(), o, None, landing[0], S)))
+        o.region = 1
+        t2 = timed(lambda: L.check(lib.vsseg_loss_pred_bwd_to(lg.data_ptr(), 2, l2.data_ptr(), B, nvox, 1, coef.data_ptr(), cek.data_ptr(), o, None, landing[0], S)))
+        print(f"  vsseg_dice_ce_pred_bwd_to bf16        {t0:8.1f} us")
+        print(f"  vsseg_loss_pred_bwd_to focal          {t1:8.1f} us   ({t1 - t0:+.1f} us)")
+        print(f"  vsseg_loss_pred_bwd_to region + focal {t2:8.1f} us   ({t2 - t0:+.1f} us)")
+        o.ce_mode, o.batch_dice = L.CE_NONE, int(rk.get("batch_dice", False))
+        t0 = timed(lambda: lib.vsseg_dice_pred_bwd_to(lg.data_ptr(), 2, l2.data_ptr(), B, nvox, 1, coef.data_ptr(), None, landing[0], S))
+        t1 = timed(lambda: L.check(lib.vsseg_loss_pred_bwd_to(lg.data_ptr(), 2, l2.data_ptr(), B, nvox, 1, coef.data_ptr(), None, o, None, landing[0], S)))
+        print(f"  vsseg_dice_pred_bwd_to bf16           {t0:8.1f} us")
+        print(f"  vsseg_loss_pred_bwd_to region         {t1:8.1f} us   ({t1 - t0:+.1f} us)")
+        fsums = torch.full((B * 6 + 6 * B * 3,), 3.0, dtype=torch.float64, device="cuda")  # (fixed-point slots: any bit pattern is a value)
+        fout = torch.zeros(1 + B * 6 + 6 * B * 2, device="cuda")
+        t0 = timed(lambda: lib.vsseg_dice_finalize(fsums.data_ptr(), fsums.data_ptr() + 8 * B * 6, B, 6, fout.data_ptr(), fout.data_ptr() + 4, S))
+        t1 = timed(lambda: L.check(lib.vsseg_loss_finalize(fsums.data_ptr(), fsums.data_ptr() + 8 * B * 6, B, 6, None, nvox, o, fout.data_ptr(), fout.data_ptr() + 4, None, S)))
+        print(f"  vsseg_dice_finalize                   {t0:8.1f} us")
+        print(f"  vsseg_loss_finalize region            {t1:8.1f} us   ({t1 - t0:+.1f} us)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=4)
@@ -153,14 +231,22 @@ def main():
     ap.add_argument("--ce_weight", type=float, default=0.0, help="> 0: time the loss phase with and without the cross-entropy term instead (at the benchmark shape and at batch 2 of 384x384x64)")
     ap.add_argument("--ce_foreground_weight", type=float, default=1.0)
     ap.add_argument("--ce_topk", type=float, default=0.0, metavar="PCT", help="> 0 (with --ce_weight): time the loss phase without the term, with the plain term and with the top-k term over the hardest PCT percent")
+    ap.add_argument("--tversky_beta", type=float, default=None, metavar="BETA", help="time the region and focal options: the Tversky ratio with this beta")
+    ap.add_argument("--focal_tversky_gamma", type=float, default=1.0, metavar="GAMMA")
+    ap.add_argument("--batch_dice", action="store_true")
+    ap.add_argument("--ce_focal_gamma", type=float, default=0.0, metavar="GAMMA", help="(with --ce_weight) the exponent of the focal cross-entropy term")
     a = ap.parse_args()
-    from vs_seg_amd import check_ce, check_ce_topk
+    from vs_seg_amd import check_ce, check_ce_topk, check_region
 
     try:
         lam, wfg = check_ce(a.ce_weight, a.ce_foreground_weight)
         pct = check_ce_topk(a.ce_topk, lam)
+        region, gc = check_region(a.tversky_beta, a.focal_tversky_gamma, a.batch_dice, a.ce_focal_gamma, lam, pct)
     except ValueError as e:
         ap.error(str(e))
+    if region is not None or gc > 0:
+        bench_region(lam, wfg, region, gc, [(a.batch, tuple(a.dims)), (2, (384, 384, 64))])
+        return
     if pct > 0:
         bench_topk(lam, wfg, pct, [(a.batch, tuple(a.dims)), (2, (384, 384, 64))])
         return

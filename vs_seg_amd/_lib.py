@@ -143,6 +143,14 @@ class DiceBwdLevelsDesc(C.Structure):  # vsseg_dice_bwd_levels_desc
     ]
 
 
+CE_NONE, CE_PLAIN, CE_TOPK, CE_FOCAL = 0, 1, 2, 3  # VSSEG_CE_*
+
+
+class LossOpts(C.Structure):  # vsseg_loss_opts
+    _fields_ = [("region", C.c_int32), ("batch_dice", C.c_int32), ("tversky_beta", C.c_double), ("focal_tversky_gamma", C.c_double), ("ce_mode", C.c_int32), ("reserved", C.c_int32),
+                ("ce_weight", C.c_double), ("ce_foreground_weight", C.c_double), ("ce_focal_gamma", C.c_double)]
+
+
 class WgradDesc(C.Structure):
     _fields_ = [
         ("p", Tensor),
@@ -241,6 +249,7 @@ SYMBOLS = [
     "vsseg_measure_scratch_bytes", "vsseg_measurements",
     "vsseg_grad_norm_scratch_bytes", "vsseg_grad_norm", "vsseg_sgd", "vsseg_adam_clipped",
     "vsseg_topk_scratch_bytes", "vsseg_topk_select", "vsseg_ce_topk_select", "vsseg_dice_ce_topk_finalize", "vsseg_dice_ce_topk_pred_bwd", "vsseg_dice_ce_topk_pred_bwd_to",
+    "vsseg_ce_focal_sums", "vsseg_loss_finalize", "vsseg_loss_pred_bwd", "vsseg_loss_pred_bwd_to",
 ]  # fmt: skip
 
 _lib = None
@@ -315,6 +324,10 @@ def lib():
         L.vsseg_dice_ce_topk_finalize.argtypes = [vp, vp, i32, i32, vp, f64, f64, vp, vp, vp, vp]
         L.vsseg_dice_ce_topk_pred_bwd.argtypes = [vp, i32, vp, i32, i64, i32, vp, vp, vp, vp, vp]
         L.vsseg_dice_ce_topk_pred_bwd_to.argtypes = [vp, i32, vp, i32, i64, i32, vp, vp, vp, Tensor, vp]
+        L.vsseg_ce_focal_sums.argtypes = [vp, i32, vp, i32, i64, f64, vp, vp]
+        L.vsseg_loss_finalize.argtypes = [vp, vp, i32, i32, vp, i64, C.POINTER(LossOpts), vp, vp, vp, vp]
+        L.vsseg_loss_pred_bwd.argtypes = [vp, i32, vp, i32, i64, i32, vp, vp, C.POINTER(LossOpts), vp, vp, vp]
+        L.vsseg_loss_pred_bwd_to.argtypes = [vp, i32, vp, i32, i64, i32, vp, vp, C.POINTER(LossOpts), vp, Tensor, vp]
         L.vsseg_fork_event_create.argtypes, L.vsseg_fork_event_create.restype = [], vp
         L.vsseg_fork_event_destroy.argtypes = [vp]
         L.vsseg_fork_arm.argtypes = [vp]

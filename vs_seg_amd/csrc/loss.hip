@@ -330,8 +330,32 @@ __device__ __forceinline__ void ce_terms(float l0, float l1, float lab, float* t
   const float v = (z > 0.f ? z : 0.f) + (e < 0x1p-12f ? e * (1.f - 0.5f * e) : __logf(1.f + e));
   t[0] += fg ? 0.f : v; t[1] += fg ? v : 0.f; t[2] += fg ? 1.f : 0.f;
 }
-// dice_pred_sums_kernel's launch shape and its two paths; a thread adds four voxels in fp32 and keeps its running sums in fp64
-__global__ __launch_bounds__(DICE_THREADS) void ce_sums_kernel(const float* __restrict__ logits, int pitch, const float* __restrict__ label, int64_t nvox, double* __restrict__ sums, unsigned* fxflag) {
+// The focal cross-entropy (vsseg_ce_focal_sums; include/vsseg_hip.h states the formulas): a voxel's value is w[y] * q^gamma * softplus(z), q = sigmoid(z) = 1 - p_y.
+// The two parts that the sums pass and the backward share, from z and e = exp(-|z|): sp = softplus(z) as ce_terms forms it and qg = q^gamma = exp(-gamma * softplus(-z))
+// with softplus(-z) = max(-z, 0) + log1p(e) — no log of a rounded probability: at z = -200 the exponent is -200 gamma and qg underflows to 0, at z = +200 it is
+// -gamma e = 0 and qg is 1.  One logarithm and one exponential per voxel beyond the plain term's.  A NaN logit: NaN through both.
+struct CeFocalParts { float sp, qg; };
+__device__ __forceinline__ CeFocalParts ce_focal_parts(float z, float e, float gamma) {
+  const float l1p = e < 0x1p-12f ? e * (1.f - 0.5f * e) : __logf(1.f + e);
+  CeFocalParts r;
+  r.sp = (z > 0.f ? z : 0.f) + l1p;
+  r.qg = __expf(-gamma * ((z < 0.f ? -z : 0.f) + l1p));
+  return r;
+}
+__device__ __forceinline__ void ce_focal_terms(float l0, float l1, float lab, float gamma, float* t) {
+  const bool fg = (int)(long long)lab == 1;
+  const float z = fg ? l0 - l1 : l1 - l0;
+  const CeFocalParts f = ce_focal_parts(z, __expf(-fabsf(z)), gamma);
+  const float v = f.qg * f.sp;
+  t[0] += fg ? 0.f : v; t[1] += fg ? v : 0.f; t[2] += fg ? 1.f : 0.f;
+}
+// dice_pred_sums_kernel's launch shape and its two paths; a thread adds four voxels in fp32 and keeps its running sums in fp64.  FOCAL: the values of ce_focal_terms
+template <bool FOCAL>
+__global__ __launch_bounds__(DICE_THREADS) void ce_sums_kernel(const float* __restrict__ logits, int pitch, const float* __restrict__ label, int64_t nvox, double* __restrict__ sums, unsigned* fxflag, float gamma) {
+  auto ce_terms = [gamma](float l0, float l1, float lab, float* t) {
+    if constexpr (FOCAL) ce_focal_terms(l0, l1, lab, gamma, t);
+    else ::ce_terms(l0, l1, lab, t);
+  };
   const int b = blockIdx.y;
   const float* lg = logits + (int64_t)b * nvox * pitch;
   const float* lb = label + (int64_t)b * nvox;
@@ -365,8 +389,18 @@ extern "C" int vsseg_ce_sums(const float* logits, int32_t pitch, const float* la
   VSSEG_CHECK(logits && label && sums && pitch >= 2 && pitch % 2 == 0 && n >= 1 && nvox >= 1, "vsseg_ce_sums: bad arguments");
   dim3 g(dice_blocks(nvox / 4, n), n);
   VSSEG_FX_FLAG(fxflag, "vsseg_ce_sums");
-  hipLaunchKernelGGL(ce_sums_kernel, g, dim3(DICE_THREADS), 0, as_stream(stream), logits, pitch, label, nvox, sums, fxflag);
+  hipLaunchKernelGGL(ce_sums_kernel<false>, g, dim3(DICE_THREADS), 0, as_stream(stream), logits, pitch, label, nvox, sums, fxflag, 0.f);
   VSSEG_LAUNCH_CHECK("vsseg_ce_sums");
+  return VSSEG_OK;
+}
+static bool ce_focal_gamma_ok(double g) { return g >= 0.0 && g <= 5.0; }  // (a NaN fails both)
+extern "C" int vsseg_ce_focal_sums(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, double ce_focal_gamma, double* sums, void* stream) {
+  VSSEG_CHECK(logits && label && sums && pitch >= 2 && pitch % 2 == 0 && n >= 1 && nvox >= 1, "vsseg_ce_focal_sums: bad arguments");
+  VSSEG_CHECK(ce_focal_gamma_ok(ce_focal_gamma), "vsseg_ce_focal_sums: ce_focal_gamma must be in [0, 5]");
+  dim3 g(dice_blocks(nvox / 4, n), n);
+  VSSEG_FX_FLAG(fxflag, "vsseg_ce_focal_sums");
+  hipLaunchKernelGGL(ce_sums_kernel<true>, g, dim3(DICE_THREADS), 0, as_stream(stream), logits, pitch, label, nvox, sums, fxflag, (float)ce_focal_gamma);
+  VSSEG_LAUNCH_CHECK("vsseg_ce_focal_sums");
   return VSSEG_OK;
 }
 
@@ -375,10 +409,57 @@ extern "C" int vsseg_ce_sums(const float* logits, int32_t pitch, const float* la
 // W = (voxels - N_fg) + w_fg * N_fg — the backward reads the two from device memory: no host read of N_fg.
 // With `topk` (vsseg_dice_ce_topk_finalize; the record of vsseg_ce_topk_select, topk.h): + ce_weight * (S_gt + (K - n_gt) * t) / K, S_gt = s_above + s_tail, and
 // topk_coef = (ce_weight / K, ce_weight * w_fg / K, the tie share (K - n_gt) / n_eq, the threshold's bits, w_fg as the select rounded it) — the division is by K, not by W.
+// With `region` (vsseg_loss_finalize: the Tversky ratio, its focal exponent, pooling over the batch; include/vsseg_hip.h states the formulas) a logits ratio leaves THREE
+// coefficients, coef[b][c][0..2] = d(loss)/d(I, G, P); an attention-map ratio keeps (d/dI, d/dP) — its G is the label.  A pooled ratio writes its coefficients once per sample.
+struct DiceRegionK { int on, pool; double beta, gamma; };
+// one ratio of weight `wgt` from its three sums: its term, and c[0..2] = d(wgt * term)/d(I, G, P)
+__device__ __forceinline__ double region_ratio(double I, double G, double P, double aP, double aG, double gamma, double wgt, double poison, double* c) {
+  const double D = 2.0 * aP * P + 2.0 * aG * G + SMOOTH + poison * 0.0, num = 2.0 * I + SMOOTH;  // (+ NaN when poisoned: the coefficients too)
+  const double u = 1.0 - num / D;
+  double term = u, d = wgt;
+  if (gamma != 1.0) {  // max(u, 1e-7)^gamma: constant below the floor
+    const bool floored = u < 1e-7;
+    term = floored ? pow(1e-7, gamma) : pow(u, gamma);
+    d = floored ? 0.0 : wgt * gamma * pow(u, gamma - 1.0);
+  }
+  c[0] = -2.0 / D * d;
+  c[1] = num * 2.0 * aG / (D * D) * d;
+  c[2] = num * 2.0 * aP / (D * D) * d;
+  return wgt * term;
+}
 __global__ void dice_finalize_kernel(const double* pred_sums, const double* att_sums, int n, int nlevels, float* loss, float* coef, const unsigned* fxflag,
-                                     const double* ce_sums, double voxels, double ce_weight, double ce_fg_weight, float* ce_coef, const TopkRec* topk, float* topk_coef) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+                                     const double* ce_sums, double voxels, double ce_weight, double ce_fg_weight, float* ce_coef, const TopkRec* topk, float* topk_coef, const DiceRegionK region) {
+  if (blockIdx.x != 0) return;
+  __shared__ double region_part[64];  // (every launch of this kernel has 64 threads)
+  if (region.on) {
+    // a ratio per thread — the fp64 powers of the focal exponent, one after the other in one thread, were 10 us of the loss phase — and their terms added in thread order below
+    const double poison = vsseg_fx_poison(fxflag), alpha = 1.0 - region.beta;
+    const int groups = region.pool ? 1 : n, per = region.pool ? n : 1;  // a ratio is formed over `per` samples
+    double part = 0.0;
+    for (int r = threadIdx.x; r < (2 + nlevels) * groups; r += 64) {
+      const bool pred = r < 2 * groups;
+      const int l = pred ? 0 : (r - 2 * groups) / groups, q = pred ? r / 2 : (r - 2 * groups) % groups, c = pred ? r % 2 : 1;  // (an attention map weighs like the foreground class)
+      double s[3] = {0.0, 0.0, 0.0}, k[3];
+      for (int b = q * per; b < (q + 1) * per; ++b)
+        for (int j = 0; j < 3; ++j) s[j] += vsseg_fx_get((pred ? pred_sums + (b * 2 + c) * 3 : att_sums + (l * n + b) * 3) + j, VSSEG_FX_DICE);
+      part += region_ratio(s[0], s[1], s[2], c == 1 ? alpha : region.beta, c == 1 ? region.beta : alpha, region.gamma, 1.0 / ((pred ? 2.0 : (double)nlevels) * groups), poison, k);
+      for (int b = q * per; b < (q + 1) * per; ++b) {
+        if (pred) {
+          for (int j = 0; j < 3; ++j) coef[(b * 2 + c) * 3 + j] = (float)k[j];
+        } else {
+          coef[n * 6 + (l * n + b) * 2 + 0] = (float)k[0];
+          coef[n * 6 + (l * n + b) * 2 + 1] = (float)k[2];
+        }
+      }
+    }
+    region_part[threadIdx.x] = part;
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
   double total = vsseg_fx_poison(fxflag);  // NaN while a partial sum of this process was non-finite / out of range (common.h)
+  if (region.on) {
+    for (int t = 0; t < 64; ++t) total += region_part[t];
+  } else {
   for (int b = 0; b < n; ++b)
     for (int c = 0; c < 2; ++c) {
       const double* sp = pred_sums + (b * 2 + c) * 3;
@@ -397,6 +478,7 @@ __global__ void dice_finalize_kernel(const double* pred_sums, const double* att_
       coef[n * 4 + (l * n + b) * 2 + 0] = (float)(-2.0 / D * wgt);
       coef[n * 4 + (l * n + b) * 2 + 1] = (float)(num / (D * D) * wgt);
     }
+  }
   if (ce_sums) {
     const double sbg = vsseg_fx_get(ce_sums, VSSEG_FX_STAT), sfg = vsseg_fx_get(ce_sums + 1, VSSEG_FX_STAT), nfg = vsseg_fx_get(ce_sums + 2, VSSEG_FX_STAT);
     const double W = (voxels - nfg) + ce_fg_weight * nfg + total * 0.0;  // (+ NaN when poisoned: the coefficients too)
@@ -422,7 +504,7 @@ __global__ void dice_finalize_kernel(const double* pred_sums, const double* att_
 extern "C" int vsseg_dice_finalize(const double* pred_sums, const double* att_sums, int32_t n, int32_t nlevels, float* loss, float* coef, void* stream) {
   VSSEG_CHECK(pred_sums && loss && coef && (nlevels == 0 || att_sums), "vsseg_dice_finalize: bad arguments");
   VSSEG_FX_FLAG(fxflag, "vsseg_dice_finalize");
-  hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(64), 0, as_stream(stream), pred_sums, att_sums, n, nlevels, loss, coef, fxflag, (const double*)nullptr, 0.0, 0.0, 0.0, (float*)nullptr, (const TopkRec*)nullptr, (float*)nullptr);
+  hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(64), 0, as_stream(stream), pred_sums, att_sums, n, nlevels, loss, coef, fxflag, (const double*)nullptr, 0.0, 0.0, 0.0, (float*)nullptr, (const TopkRec*)nullptr, (float*)nullptr, DiceRegionK{0, 0, 0.5, 1.0});
   VSSEG_LAUNCH_CHECK("vsseg_dice_finalize");
   return VSSEG_OK;
 }
@@ -431,7 +513,7 @@ extern "C" int vsseg_dice_ce_finalize(const double* pred_sums, const double* att
   VSSEG_CHECK(pred_sums && loss && coef && (nlevels == 0 || att_sums) && ce_sums && ce_coef && n >= 1 && nvox >= 1, "vsseg_dice_ce_finalize: bad arguments");
   VSSEG_CHECK(ce_weight >= 0.0 && ce_weight < INFINITY && ce_foreground_weight > 0.0 && ce_foreground_weight < INFINITY, "vsseg_dice_ce_finalize: ce_weight must be finite and >= 0, ce_foreground_weight finite and > 0");
   VSSEG_FX_FLAG(fxflag, "vsseg_dice_ce_finalize");
-  hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(64), 0, as_stream(stream), pred_sums, att_sums, n, nlevels, loss, coef, fxflag, ce_sums, (double)n * (double)nvox, ce_weight, ce_foreground_weight, ce_coef, (const TopkRec*)nullptr, (float*)nullptr);
+  hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(64), 0, as_stream(stream), pred_sums, att_sums, n, nlevels, loss, coef, fxflag, ce_sums, (double)n * (double)nvox, ce_weight, ce_foreground_weight, ce_coef, (const TopkRec*)nullptr, (float*)nullptr, DiceRegionK{0, 0, 0.5, 1.0});
   VSSEG_LAUNCH_CHECK("vsseg_dice_ce_finalize");
   return VSSEG_OK;
 }
@@ -441,15 +523,46 @@ extern "C" int vsseg_dice_ce_topk_finalize(const double* pred_sums, const double
   VSSEG_CHECK(ce_weight >= 0.0 && ce_weight < INFINITY && ce_foreground_weight > 0.0 && ce_foreground_weight < INFINITY, "vsseg_dice_ce_topk_finalize: ce_weight must be finite and >= 0, ce_foreground_weight finite and > 0");
   VSSEG_FX_FLAG(fxflag, "vsseg_dice_ce_topk_finalize");
   hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(64), 0, as_stream(stream), pred_sums, att_sums, n, nlevels, loss, coef, fxflag, (const double*)nullptr, 0.0, ce_weight, ce_foreground_weight, (float*)nullptr,
-                     reinterpret_cast<const TopkRec*>(topk_scratch), topk_coef);
+                     reinterpret_cast<const TopkRec*>(topk_scratch), topk_coef, DiceRegionK{0, 0, 0.5, 1.0});
   VSSEG_LAUNCH_CHECK("vsseg_dice_ce_topk_finalize");
+  return VSSEG_OK;
+}
+// the range checks of a vsseg_loss_opts record, before any launch (comparisons that a NaN fails)
+static int loss_opts_check(const vsseg_loss_opts* o, const char* who) {
+  VSSEG_CHECK(o, "%s: no options record", who);
+  VSSEG_CHECK((o->region == 0 || o->region == 1) && (o->batch_dice == 0 || o->batch_dice == 1) && o->reserved == 0, "%s: region and batch_dice are 0 or 1, reserved is 0", who);
+  VSSEG_CHECK(o->region || !o->batch_dice, "%s: batch_dice needs region = 1", who);
+  if (o->region) {
+    VSSEG_CHECK(o->tversky_beta > 0.0 && o->tversky_beta < 1.0, "%s: tversky_beta must be in (0, 1)", who);
+    VSSEG_CHECK(o->focal_tversky_gamma >= 0.25 && o->focal_tversky_gamma <= 4.0, "%s: focal_tversky_gamma must be in [0.25, 4]", who);
+  }
+  VSSEG_CHECK(o->ce_mode >= VSSEG_CE_NONE && o->ce_mode <= VSSEG_CE_FOCAL, "%s: ce_mode %d is none of VSSEG_CE_*", who, o->ce_mode);
+  if (o->ce_mode != VSSEG_CE_NONE)
+    VSSEG_CHECK(o->ce_weight >= 0.0 && o->ce_weight < INFINITY && o->ce_foreground_weight > 0.0 && o->ce_foreground_weight < INFINITY, "%s: ce_weight must be finite and >= 0, ce_foreground_weight finite and > 0", who);
+  if (o->ce_mode == VSSEG_CE_FOCAL) VSSEG_CHECK(ce_focal_gamma_ok(o->ce_focal_gamma), "%s: ce_focal_gamma must be in [0, 5]", who);
+  return VSSEG_OK;
+}
+extern "C" int vsseg_loss_finalize(const double* pred_sums, const double* att_sums, int32_t n, int32_t nlevels, const void* ce_state, int64_t nvox, const vsseg_loss_opts* opts, float* loss, float* coef, float* ce_coef,
+                                   void* stream) {
+  VSSEG_CHECK(pred_sums && loss && coef && (nlevels == 0 || att_sums) && n >= 1 && nlevels >= 0 && nvox >= 1, "vsseg_loss_finalize: bad arguments");
+  if (loss_opts_check(opts, "vsseg_loss_finalize") != VSSEG_OK) return VSSEG_EINVAL;
+  VSSEG_CHECK(opts->ce_mode == VSSEG_CE_NONE || (ce_state && ce_coef), "vsseg_loss_finalize: the cross-entropy term needs its sums (or the select's record) and ce_coef");
+  const bool topk = opts->ce_mode == VSSEG_CE_TOPK, sums = opts->ce_mode == VSSEG_CE_PLAIN || opts->ce_mode == VSSEG_CE_FOCAL;  // (the focal sums decode like the plain ones)
+  VSSEG_FX_FLAG(fxflag, "vsseg_loss_finalize");
+  hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(64), 0, as_stream(stream), pred_sums, att_sums, n, nlevels, loss, coef, fxflag, sums ? reinterpret_cast<const double*>(ce_state) : nullptr,
+                     (double)n * (double)nvox, opts->ce_weight, opts->ce_foreground_weight, sums ? ce_coef : nullptr, topk ? reinterpret_cast<const TopkRec*>(ce_state) : nullptr, topk ? ce_coef : nullptr,
+                     DiceRegionK{opts->region, opts->batch_dice, opts->tversky_beta, opts->focal_tversky_gamma});
+  VSSEG_LAUNCH_CHECK("vsseg_loss_finalize");
   return VSSEG_OK;
 }
 
 // d(loss)/d(logits) of one voxel: through the Dice sums, the (non-detached) hardness weight (ref :279-283) and the softmax
 // CE: + the gradient of the cross-entropy term of the voxel, k * w[y] * (softmax(x) - onehot(y)) with kbg = k * w[0], kfg = k * w[1] (vsseg_dice_ce_finalize's ce_coef),
 // formed from the OTHER class's probability — (+kfg p0, -kfg p0) for y = 1, (-kbg p1, +kbg p1) for y = 0: p_y - 1 cancels once p_y rounds to 1 — and added in fp32
-template <bool CE> __device__ __forceinline__ float2 dice_pred_grad(float l0, float l1, float lab, int hardness, float A0, float B0, float A1, float B1, float kbg, float kfg) {
+// SPLIT (the region options of vsseg_loss_finalize): G and P have coefficients of their own, (B, P) = d(loss)/d(G, P) — A g t + B g s + P t
+// CE 3: the focal cross-entropy — dz = k w[y] q^gamma (gamma (1 - q) softplus(z) + q) to the other class's logit, -dz to the label's own (ce_focal_parts)
+template <int CE, bool SPLIT = false> __device__ __forceinline__ float2 dice_pred_grad(float l0, float l1, float lab, int hardness, float A0, float B0, float A1, float B1, float kbg, float kfg, float P0 = 0.f, float P1 = 0.f,
+                                                                                       float fgamma = 0.f) {
   const float m = fmaxf(l0, l1), e0 = __expf(l0 - m), e1 = __expf(l1 - m), inv = 1.f / (e0 + e1);
   const float p0 = e0 * inv, p1 = e1 * inv;
   const int cls = (int)(long long)lab;
@@ -462,11 +575,24 @@ template <bool CE> __device__ __forceinline__ float2 dice_pred_grad(float l0, fl
     s1 = d1 > 0.f ? 0.6f : (d1 < 0.f ? -0.6f : 0.f);
   }
   const float t0 = w0 + p0 * s0, t1 = w1 + p1 * s1;  // d(w*p)/dp
-  const float dp0 = A0 * g0 * t0 + B0 * (g0 * s0 + t0);
-  const float dp1 = A1 * g1 * t1 + B1 * (g1 * s1 + t1);
+  float dp0, dp1;
+  if constexpr (SPLIT) {
+    dp0 = A0 * g0 * t0 + B0 * g0 * s0 + P0 * t0;
+    dp1 = A1 * g1 * t1 + B1 * g1 * s1 + P1 * t1;
+  } else {
+    dp0 = A0 * g0 * t0 + B0 * (g0 * s0 + t0);
+    dp1 = A1 * g1 * t1 + B1 * (g1 * s1 + t1);
+  }
   const float dot = dp0 * p0 + dp1 * p1;
   float2 r = make_float2(p0 * (dp0 - dot), p1 * (dp1 - dot));
-  if constexpr (CE) {
+  if constexpr (CE == 3) {
+    // q = sigmoid(z) and 1 - q = p_y are the softmax probabilities above, and exp(-|z|) is the smaller of e0, e1 (the other is exp(0) = 1)
+    const CeFocalParts f = ce_focal_parts(cls == 1 ? l0 - l1 : l1 - l0, fminf(e0, e1), fgamma);
+    const float q = cls == 1 ? p0 : p1, py = cls == 1 ? p1 : p0;
+    const float dz = f.qg * (fgamma * py * f.sp + q);
+    const float c = cls == 1 ? kfg * dz : -(kbg * dz);
+    r.x += c; r.y -= c;
+  } else if constexpr (CE != 0) {
     const float c = cls == 1 ? kfg * p0 : -(kbg * p1);
     r.x += c; r.y -= c;
   }
@@ -478,22 +604,27 @@ template <bool CE> __device__ __forceinline__ float2 dice_pred_grad(float l0, fl
 // CE: the cross-entropy gradient is formed here as well (vsseg_dice_ce_pred_bwd / _to) and the sum is stored once — a second pass would round the bf16 operand twice.
 // CE 2 (the top-k term, vsseg_dice_ce_topk_pred_bwd / _to): the voxel's cross-entropy gradient times c = 1 above the threshold, the tie share at it, 0 below it — its value
 // is recomputed by the one function of topk.h and its KEY is compared with the threshold's bits, as the select counted it.
-template <int CE> __device__ __forceinline__ float2 dice_pred_grad_of(float l0, float l1, float lab, int hardness, float A0, float B0, float A1, float B1, float kbg, float kfg, float share, unsigned tbits, float wfg) {
+// CE 3 (the focal term, vsseg_loss_pred_bwd / _to): fgamma is the exponent, a kernel argument.  SPLIT: coef holds three per ratio, (A, B, P) = d(loss)/d(I, G, P).
+template <int CE, bool SPLIT> __device__ __forceinline__ float2 dice_pred_grad_of(float l0, float l1, float lab, int hardness, float A0, float B0, float A1, float B1, float kbg, float kfg, float share, unsigned tbits, float wfg,
+                                                                                  float P0, float P1, float fgamma) {
   if constexpr (CE == 2) {
     const unsigned u = topk_key(ce_topk_value(l0, l1, lab, wfg));
     const float c = u > tbits ? 1.f : (u == tbits ? share : 0.f);
-    return dice_pred_grad<true>(l0, l1, lab, hardness, A0, B0, A1, B1, kbg * c, kfg * c);
+    return dice_pred_grad<1, SPLIT>(l0, l1, lab, hardness, A0, B0, A1, B1, kbg * c, kfg * c, P0, P1);
   } else {
-    return dice_pred_grad<CE != 0>(l0, l1, lab, hardness, A0, B0, A1, B1, kbg, kfg);
+    return dice_pred_grad<CE, SPLIT>(l0, l1, lab, hardness, A0, B0, A1, B1, kbg, kfg, P0, P1, fgamma);
   }
 }
-template <int OUT, int CE> __global__ __launch_bounds__(256) void dice_pred_bwd_kernel(const float* __restrict__ logits, int pitch, const float* __restrict__ label, int64_t nvox, int hardness, const float* __restrict__ coef,
-                                                                                          const float* __restrict__ gscale, void* __restrict__ dst, int dpitch, const float* __restrict__ ce_coef) {
+template <int OUT, int CE, bool SPLIT> __global__ __launch_bounds__(256) void dice_pred_bwd_kernel(const float* __restrict__ logits, int pitch, const float* __restrict__ label, int64_t nvox, int hardness, const float* __restrict__ coef,
+                                                                                                      const float* __restrict__ gscale, void* __restrict__ dst, int dpitch, const float* __restrict__ ce_coef, float fgamma) {
   const int b = blockIdx.y;
   const float* lg = logits + (int64_t)b * nvox * pitch;
   const float* lb = label + (int64_t)b * nvox;
   const float gs = gscale ? *gscale : 1.f;
-  const float A0 = coef[(b * 2 + 0) * 2] * gs, B0 = coef[(b * 2 + 0) * 2 + 1] * gs, A1 = coef[(b * 2 + 1) * 2] * gs, B1 = coef[(b * 2 + 1) * 2 + 1] * gs;
+  constexpr int NC = SPLIT ? 3 : 2;  // coefficients per ratio
+  const float A0 = coef[(b * 2 + 0) * NC] * gs, B0 = coef[(b * 2 + 0) * NC + 1] * gs, A1 = coef[(b * 2 + 1) * NC] * gs, B1 = coef[(b * 2 + 1) * NC + 1] * gs;
+  float P0 = 0.f, P1 = 0.f;
+  if constexpr (SPLIT) { P0 = coef[(b * 2 + 0) * 3 + 2] * gs; P1 = coef[(b * 2 + 1) * 3 + 2] * gs; }
   float kbg = 0.f, kfg = 0.f;
   float share = 0.f, wfg = 1.f;
   unsigned tbits = 0u;
@@ -511,8 +642,8 @@ template <int OUT, int CE> __global__ __launch_bounds__(256) void dice_pred_bwd_
     const float4* lb4 = reinterpret_cast<const float4*>(lb);
     for (int64_t i = tid; i < (nvox >> 2); i += nthr) {
       const float4 a = lg4[2 * i], c = lg4[2 * i + 1], g = lb4[i];
-      const float2 r0 = dice_pred_grad_of<CE>(a.x, a.y, g.x, hardness, A0, B0, A1, B1, kbg, kfg, share, tbits, wfg), r1 = dice_pred_grad_of<CE>(a.z, a.w, g.y, hardness, A0, B0, A1, B1, kbg, kfg, share, tbits, wfg);
-      const float2 r2 = dice_pred_grad_of<CE>(c.x, c.y, g.z, hardness, A0, B0, A1, B1, kbg, kfg, share, tbits, wfg), r3 = dice_pred_grad_of<CE>(c.z, c.w, g.w, hardness, A0, B0, A1, B1, kbg, kfg, share, tbits, wfg);
+      const float2 r0 = dice_pred_grad_of<CE, SPLIT>(a.x, a.y, g.x, hardness, A0, B0, A1, B1, kbg, kfg, share, tbits, wfg, P0, P1, fgamma), r1 = dice_pred_grad_of<CE, SPLIT>(a.z, a.w, g.y, hardness, A0, B0, A1, B1, kbg, kfg, share, tbits, wfg, P0, P1, fgamma);
+      const float2 r2 = dice_pred_grad_of<CE, SPLIT>(c.x, c.y, g.z, hardness, A0, B0, A1, B1, kbg, kfg, share, tbits, wfg, P0, P1, fgamma), r3 = dice_pred_grad_of<CE, SPLIT>(c.z, c.w, g.w, hardness, A0, B0, A1, B1, kbg, kfg, share, tbits, wfg, P0, P1, fgamma);
       if constexpr (OUT == 0) {
         float4* o = reinterpret_cast<float4*>(reinterpret_cast<float*>(dst) + ((int64_t)b * nvox + 4 * i) * 2);
         o[0] = make_float4(r0.x, r0.y, r1.x, r1.y);
@@ -526,20 +657,20 @@ template <int OUT, int CE> __global__ __launch_bounds__(256) void dice_pred_bwd_
   } else {
     for (int64_t v = tid; v < nvox; v += nthr) {
       const float2 l = *reinterpret_cast<const float2*>(lg + v * pitch);
-      store(v, dice_pred_grad_of<CE>(l.x, l.y, lb[v], hardness, A0, B0, A1, B1, kbg, kfg, share, tbits, wfg));
+      store(v, dice_pred_grad_of<CE, SPLIT>(l.x, l.y, lb[v], hardness, A0, B0, A1, B1, kbg, kfg, share, tbits, wfg, P0, P1, fgamma));
     }
   }
 }
-template <int CE>
+template <int CE, bool SPLIT = false>
 static int dice_pred_bwd_launch(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* ce_coef, const float* gscale, void* dst, int out, int dpitch,
-                                void* stream, const char* who) {
+                                void* stream, const char* who, float fgamma = 0.f) {
   VSSEG_CHECK(logits && label && coef && dst && pitch >= 2 && pitch % 2 == 0 && n >= 1 && nvox >= 1 && (!CE || ce_coef), "%s: bad arguments", who);
   dim3 g(grid_for((nvox + 3) / 4, 256, 2048), n), t(256);
   hipStream_t s = as_stream(stream);
-  if (out == 0) hipLaunchKernelGGL((dice_pred_bwd_kernel<0, CE>), g, t, 0, s, logits, pitch, label, nvox, hardness, coef, gscale, dst, 2, ce_coef);
-  else if (out == 1) hipLaunchKernelGGL((dice_pred_bwd_kernel<1, CE>), g, t, 0, s, logits, pitch, label, nvox, hardness, coef, gscale, dst, 2, ce_coef);
-  else if (out == 2) hipLaunchKernelGGL((dice_pred_bwd_kernel<2, CE>), g, t, 0, s, logits, pitch, label, nvox, hardness, coef, gscale, dst, 8, ce_coef);
-  else hipLaunchKernelGGL((dice_pred_bwd_kernel<3, CE>), g, t, 0, s, logits, pitch, label, nvox, hardness, coef, gscale, dst, dpitch, ce_coef);
+  if (out == 0) hipLaunchKernelGGL((dice_pred_bwd_kernel<0, CE, SPLIT>), g, t, 0, s, logits, pitch, label, nvox, hardness, coef, gscale, dst, 2, ce_coef, fgamma);
+  else if (out == 1) hipLaunchKernelGGL((dice_pred_bwd_kernel<1, CE, SPLIT>), g, t, 0, s, logits, pitch, label, nvox, hardness, coef, gscale, dst, 2, ce_coef, fgamma);
+  else if (out == 2) hipLaunchKernelGGL((dice_pred_bwd_kernel<2, CE, SPLIT>), g, t, 0, s, logits, pitch, label, nvox, hardness, coef, gscale, dst, 8, ce_coef, fgamma);
+  else hipLaunchKernelGGL((dice_pred_bwd_kernel<3, CE, SPLIT>), g, t, 0, s, logits, pitch, label, nvox, hardness, coef, gscale, dst, dpitch, ce_coef, fgamma);
   VSSEG_LAUNCH_CHECK(who);
   return VSSEG_OK;
 }
@@ -582,6 +713,36 @@ extern "C" int vsseg_dice_ce_topk_pred_bwd_to(const float* logits, int32_t pitch
   const int out = dice_pred_bwd_layout(dst, n, nvox, "vsseg_dice_ce_topk_pred_bwd_to");
   if (out < 0) return VSSEG_EINVAL;
   return dice_pred_bwd_launch<2>(logits, pitch, label, n, nvox, hardness, coef, topk_coef, gscale, dst.ptr, out, dst.pitch, stream, "vsseg_dice_ce_topk_pred_bwd_to");
+}
+
+// every combination of the region options and the cross-entropy modes (vsseg_loss_opts): the record picks the instantiation
+static int loss_pred_bwd_dispatch(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* ce_coef, const vsseg_loss_opts* o, const float* gscale, void* dst,
+                                  int out, int dpitch, void* stream, const char* who) {
+  const float fg = o->ce_mode == VSSEG_CE_FOCAL ? (float)o->ce_focal_gamma : 0.f;
+#define VSSEG_LOSS_BWD(CE, SPLIT) return dice_pred_bwd_launch<CE, SPLIT>(logits, pitch, label, n, nvox, hardness, coef, ce_coef, gscale, dst, out, dpitch, stream, who, fg)
+  if (o->region) {
+    if (o->ce_mode == VSSEG_CE_NONE) VSSEG_LOSS_BWD(0, true);
+    if (o->ce_mode == VSSEG_CE_PLAIN) VSSEG_LOSS_BWD(1, true);
+    if (o->ce_mode == VSSEG_CE_TOPK) VSSEG_LOSS_BWD(2, true);
+    VSSEG_LOSS_BWD(3, true);
+  }
+  if (o->ce_mode == VSSEG_CE_NONE) VSSEG_LOSS_BWD(0, false);
+  if (o->ce_mode == VSSEG_CE_PLAIN) VSSEG_LOSS_BWD(1, false);
+  if (o->ce_mode == VSSEG_CE_TOPK) VSSEG_LOSS_BWD(2, false);
+  VSSEG_LOSS_BWD(3, false);
+#undef VSSEG_LOSS_BWD
+}
+extern "C" int vsseg_loss_pred_bwd(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* ce_coef, const vsseg_loss_opts* opts, const float* gscale,
+                                   float* dlogits, void* stream) {
+  if (loss_opts_check(opts, "vsseg_loss_pred_bwd") != VSSEG_OK) return VSSEG_EINVAL;
+  return loss_pred_bwd_dispatch(logits, pitch, label, n, nvox, hardness, coef, ce_coef, opts, gscale, dlogits, 0, 2, stream, "vsseg_loss_pred_bwd");
+}
+extern "C" int vsseg_loss_pred_bwd_to(const float* logits, int32_t pitch, const float* label, int32_t n, int64_t nvox, int32_t hardness, const float* coef, const float* ce_coef, const vsseg_loss_opts* opts, const float* gscale,
+                                      vsseg_tensor dst, void* stream) {
+  if (loss_opts_check(opts, "vsseg_loss_pred_bwd_to") != VSSEG_OK) return VSSEG_EINVAL;
+  const int out = dice_pred_bwd_layout(dst, n, nvox, "vsseg_loss_pred_bwd_to");
+  if (out < 0) return VSSEG_EINVAL;
+  return loss_pred_bwd_dispatch(logits, pitch, label, n, nvox, hardness, coef, ce_coef, opts, gscale, dst.ptr, out, dst.pitch, stream, "vsseg_loss_pred_bwd_to");
 }
 
 __global__ void dice_att_bwd_kernel(const float* __restrict__ label, int64_t nvox, const float* __restrict__ coef, const float* __restrict__ gscale, float* __restrict__ datt) {

@@ -13,6 +13,13 @@ formed inside the Dice backward kernel (include/vsseg_hip.h).  0 (the default) i
 `ce_topk` = P > 0 averages that term over the hardest P percent of the voxels of the batch only (nnU-Net's Dice + TopK loss, DC_and_topk_loss with k = 10):
 loss += ce_weight * F.cross_entropy(..., reduction='none').flatten().topk(K).values.mean(), K = max(1, floor(N * P / 100)) — divided by K, not by the class-weight sum.
 The K voxels are found by a radix select on the GPU (csrc/topk.hip); the backward compares each voxel's value with the threshold the select left in device memory.
+
+For small lesions (include/vsseg_hip.h states the formulas): `tversky_beta` = beta replaces every Dice ratio by the Tversky index (2I + eps) / (2 a_P P + 2 a_G G + eps) —
+beta weights the false negatives, 1 - beta the false positives of the foreground and of the attention maps, mirrored for the background class; beta = 0.5 is the Dice ratio
+(Salehi 2017, MONAI's TverskyLoss).  `focal_tversky_gamma` = gamma raises every term to max(1 - T, 1e-7)^gamma (Abraham 2019).  `batch_dice` forms one ratio per class and per
+level over the pooled sums of the batch (nnU-Net's batch_dice; the samples of this rank).  `ce_focal_gamma` = gamma_c > 0 weights every voxel of the cross-entropy term by
+(1 - p_y)^gamma_c (MONAI's DiceFocalLoss; needs ce_weight > 0, not together with ce_topk).  The region options need no pass of their own — the sums are the same — and the
+focal term replaces the plain term's one reduction pass.  With all four at their defaults the launches are exactly those of before.
 """
 from __future__ import annotations
 
@@ -55,6 +62,32 @@ def check_ce_topk(ce_topk: float, ce_weight: float) -> float:
     return pct
 
 
+def check_region(tversky_beta=None, focal_tversky_gamma: float = 1.0, batch_dice: bool = False, ce_focal_gamma: float = 0.0, ce_weight: float = 0.0, ce_topk: float = 0.0):
+    """The options for small lesions as (region, ce_focal_gamma), or ValueError.  region is None when every region option is at its default (the reference's Dice ratio per
+    sample), else (beta, gamma, pooled) with beta = 0.5 where only the exponent or the pooling was asked for.  tversky_beta in (0, 1), focal_tversky_gamma in [0.25, 4],
+    ce_focal_gamma in [0, 5] (0: off), all finite; batch_dice a bool; the focal exponent needs the cross-entropy term (ce_weight > 0) — a flag that would silently do nothing —
+    and is refused together with ce_topk: they are two different selections of the hard voxels."""
+    try:
+        beta = None if tversky_beta is None else float(tversky_beta)
+        gamma, gc, lam, pct = float(focal_tversky_gamma), float(ce_focal_gamma), float(ce_weight), float(ce_topk)
+    except (TypeError, ValueError):
+        raise ValueError(f"tversky_beta, focal_tversky_gamma and ce_focal_gamma must be numbers (got {tversky_beta!r}, {focal_tversky_gamma!r}, {ce_focal_gamma!r})") from None
+    if beta is not None and not (math.isfinite(beta) and 0.0 < beta < 1.0):
+        raise ValueError(f"tversky_beta must be in (0, 1) (got {tversky_beta!r})")
+    if not (math.isfinite(gamma) and 0.25 <= gamma <= 4.0):
+        raise ValueError(f"focal_tversky_gamma must be in [0.25, 4] (got {focal_tversky_gamma!r})")
+    if not isinstance(batch_dice, (bool, int)) or batch_dice not in (0, 1):
+        raise ValueError(f"batch_dice must be True or False (got {batch_dice!r})")
+    if not (math.isfinite(gc) and 0.0 <= gc <= 5.0):
+        raise ValueError(f"ce_focal_gamma must be in [0, 5] (got {ce_focal_gamma!r})")
+    if gc > 0 and not lam > 0:
+        raise ValueError(f"ce_focal_gamma = {ce_focal_gamma!r} has no effect without the cross-entropy term: give ce_weight > 0 as well")
+    if gc > 0 and pct > 0:
+        raise ValueError("ce_focal_gamma and ce_topk are two different selections of the hard voxels: give one of them")
+    on = beta is not None or gamma != 1.0 or bool(batch_dice)
+    return ((0.5 if beta is None else beta, gamma, bool(batch_dice)) if on else None), gc
+
+
 def topk_count(voxels: int, ce_topk: float) -> int:
     """K = max(1, floor(N * P / 100)): how many of the N voxels of a batch the top-k term averages over (nnU-Net: int(num_voxels * k / 100))."""
     return min(int(voxels), max(1, int(math.floor(int(voxels) * float(ce_topk) / 100.0))))
@@ -78,11 +111,13 @@ def _c1(x: torch.Tensor) -> torch.Tensor:
 class _State:
     """What the forward leaves for the backward: channels-last logits, labels (full resolution + the pyramid), the coefficients of vsseg_dice_finalize
     (and, with the cross-entropy term, the two of vsseg_dice_ce_finalize or, with ce_topk, the eight of vsseg_dice_ce_topk_finalize; None without it).
-    topk_rec: with ce_topk, the first 32 bytes of the select's record as four int64 on the device (threshold_bits | passes_done << 32, n_gt, n_eq, K)."""
-    __slots__ = ("lg", "lab", "labels", "coef", "ce_coef", "topk", "topk_rec", "hardness", "nl", "shape", "att_shapes", "loss")
+    topk_rec: with ce_topk, the first 32 bytes of the select's record as four int64 on the device (threshold_bits | passes_done << 32, n_gt, n_eq, K).
+    opts: the vsseg_loss_opts record when a region option or the focal term is on (vsseg_loss_finalize / vsseg_loss_pred_bwd[_to]), else None; npred: the number of
+    logits coefficients in front of the attention maps' (6 per sample with a region option, else 4)."""
+    __slots__ = ("lg", "lab", "labels", "coef", "ce_coef", "topk", "topk_rec", "hardness", "nl", "shape", "att_shapes", "loss", "opts", "npred")
 
 
-def _dice_forward(logits, target, supervised, hardness, atts, ce=(0.0, 1.0), ce_topk=0.0) -> _State:
+def _dice_forward(logits, target, supervised, hardness, atts, ce=(0.0, 1.0), ce_topk=0.0, region=None, ce_focal=0.0) -> _State:
     lib = L.lib()
     stream = torch.cuda.current_stream().cuda_stream
     dev = logits.device
@@ -145,10 +180,28 @@ def _dice_forward(logits, target, supervised, hardness, atts, ce=(0.0, 1.0), ce_
             L.check(lib.vsseg_dice_att_sums(ac.data_ptr(), g.data_ptr(), B, adims[0] * adims[1] * adims[2], att_sums.data_ptr() + 8 * level * B * 3, stream), "dice_att_sums")
             labels.append(g)
     loss = torch.empty((), dtype=torch.float32, device=dev)  # vsseg_dice_finalize assigns the loss and every coefficient it is asked for
-    coef = torch.empty(B * 4 + max(nl, 1) * B * 2, dtype=torch.float32, device=dev)
+    focal_on = ce_on and ce_focal > 0
+    npred = B * 6 if region is not None else B * 4
+    coef = torch.empty(npred + max(nl, 1) * B * 2, dtype=torch.float32, device=dev)
     st = _State()
-    st.topk, st.topk_rec = topk_on, None
-    if topk_on:  # three histogram passes over logits and label leave the threshold, the counts and the sum in ce_sums; the finalize leaves the backward's coefficients
+    st.topk, st.topk_rec, st.opts, st.npred = topk_on, None, None, npred
+    if region is not None or focal_on:  # the record-driven entry points: any combination of the region options with no / the plain / the top-k / the focal cross-entropy term
+        o = st.opts = L.LossOpts()
+        if region is not None:
+            o.region, o.tversky_beta, o.focal_tversky_gamma, o.batch_dice = 1, region[0], region[1], int(region[2])
+        o.ce_mode = (L.CE_FOCAL if focal_on else L.CE_TOPK if topk_on else L.CE_PLAIN) if ce_on else L.CE_NONE
+        o.ce_weight, o.ce_foreground_weight, o.ce_focal_gamma = ce[0], ce[1], (ce_focal if focal_on else 0.0)
+        if focal_on:  # the plain term's pass with the focal factor: the same three sums
+            L.check(lib.vsseg_ce_focal_sums(lg.data_ptr(), 2, lab.data_ptr(), B, nvox, ce_focal, ce_sums.data_ptr(), stream), "ce_focal_sums")
+        elif topk_on:
+            L.check(lib.vsseg_ce_topk_select(lg.data_ptr(), 2, lab.data_ptr(), B, nvox, ce[1], topk_count(B * nvox, ce_topk), ce_sums.data_ptr(), stream), "ce_topk_select")
+            st.topk_rec = ce_sums[:4].view(torch.int64)
+        elif ce_on:
+            L.check(lib.vsseg_ce_sums(lg.data_ptr(), 2, lab.data_ptr(), B, nvox, ce_sums.data_ptr(), stream), "ce_sums")
+        st.ce_coef = torch.empty(8 if topk_on else 2, dtype=torch.float32, device=dev) if ce_on else None
+        L.check(lib.vsseg_loss_finalize(pred_sums.data_ptr(), att_sums.data_ptr(), B, nl, ce_sums.data_ptr() if ce_on else None, nvox, o, loss.data_ptr(), coef.data_ptr(),
+                                        st.ce_coef.data_ptr() if ce_on else None, stream), "loss_finalize")
+    elif topk_on:  # three histogram passes over logits and label leave the threshold, the counts and the sum in ce_sums; the finalize leaves the backward's coefficients
         L.check(lib.vsseg_ce_topk_select(lg.data_ptr(), 2, lab.data_ptr(), B, nvox, ce[1], topk_count(B * nvox, ce_topk), ce_sums.data_ptr(), stream), "ce_topk_select")
         st.ce_coef = torch.empty(8, dtype=torch.float32, device=dev)
         L.check(lib.vsseg_dice_ce_topk_finalize(pred_sums.data_ptr(), att_sums.data_ptr(), B, nl, ce_sums.data_ptr(), ce[0], ce[1], loss.data_ptr(), coef.data_ptr(), st.ce_coef.data_ptr(), stream), "dice_ce_topk_finalize")
@@ -188,14 +241,14 @@ def _fused_plan(B, dims, att_shapes, lg, lab, acs) -> Optional[int]:
 def _att_backward(st: _State, level: int, gs_ptr, dst: torch.Tensor):
     B = st.shape[0]
     shp = st.att_shapes[st.nl - level - 1]
-    L.check(L.lib().vsseg_dice_att_bwd(st.labels[level].data_ptr(), B, shp[2] * shp[3] * shp[4], st.coef.data_ptr() + 4 * (B * 4 + level * B * 2), 1.0 / st.nl, gs_ptr, dst.data_ptr(),
+    L.check(L.lib().vsseg_dice_att_bwd(st.labels[level].data_ptr(), B, shp[2] * shp[3] * shp[4], st.coef.data_ptr() + 4 * (st.npred + level * B * 2), 1.0 / st.nl, gs_ptr, dst.data_ptr(),
                                        torch.cuda.current_stream().cuda_stream), "dice_att_bwd")
 
 
 class _DiceFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target, supervised, hardness, ce, owner, *atts):
-        ctx.st = st = _dice_forward(logits, target, supervised, hardness, atts, ce[:2], ce[2])
+        ctx.st = st = _dice_forward(logits, target, supervised, hardness, atts, ce[:2], ce[2], owner.region, owner.ce_focal_gamma)
         owner.topk_record = st.topk_rec  # (the Dice_spvPA object: the record of its last call, None without ce_topk)
         return st.loss
 
@@ -208,7 +261,10 @@ class _DiceFn(torch.autograd.Function):
         dev = st.lg.device
         gs = gout.detach().to(torch.float32).contiguous()
         dlog = torch.empty((B, X, Y, Z, 2), dtype=torch.float32, device=dev)
-        if st.ce_coef is None:
+        if st.opts is not None:
+            L.check(lib.vsseg_loss_pred_bwd(st.lg.data_ptr(), 2, st.lab.data_ptr(), B, X * Y * Z, st.hardness, st.coef.data_ptr(), None if st.ce_coef is None else st.ce_coef.data_ptr(), st.opts, gs.data_ptr(), dlog.data_ptr(),
+                                            stream), "loss_pred_bwd")
+        elif st.ce_coef is None:
             L.check(lib.vsseg_dice_pred_bwd(st.lg.data_ptr(), 2, st.lab.data_ptr(), B, X * Y * Z, st.hardness, st.coef.data_ptr(), gs.data_ptr(), dlog.data_ptr(), stream), "dice_pred_bwd")
         elif st.topk:
             L.check(lib.vsseg_dice_ce_topk_pred_bwd(st.lg.data_ptr(), 2, st.lab.data_ptr(), B, X * Y * Z, st.hardness, st.coef.data_ptr(), st.ce_coef.data_ptr(), gs.data_ptr(), dlog.data_ptr(), stream), "dice_ce_topk_pred_bwd")
@@ -226,7 +282,7 @@ class _DiceFn(torch.autograd.Function):
 class Dice_spvPA(_Loss):
     def __init__(self, include_background: bool = True, to_onehot_y: bool = False, sigmoid: bool = False, softmax: bool = False, other_act=None, squared_pred: bool = False,
                  jaccard: bool = False, reduction="mean", supervised_attention=True, hardness_weighting=True, ce_weight: float = 0.0, ce_foreground_weight: float = 1.0,
-                 ce_topk: float = 0.0) -> None:
+                 ce_topk: float = 0.0, tversky_beta: Optional[float] = None, focal_tversky_gamma: float = 1.0, batch_dice: bool = False, ce_focal_gamma: float = 0.0) -> None:
         super().__init__(reduction=getattr(reduction, "value", reduction))
         if other_act is not None and not callable(other_act):
             raise TypeError(f"other_act must be None or callable but is {type(other_act).__name__}.")
@@ -234,6 +290,9 @@ class Dice_spvPA(_Loss):
             raise ValueError("Incompatible values: more than 1 of [sigmoid=True, softmax=True, other_act is not None].")
         self.ce_weight, self.ce_foreground_weight = check_ce(ce_weight, ce_foreground_weight)  # beyond the reference: + ce_weight * cross-entropy on the final logits
         self.ce_topk = check_ce_topk(ce_topk, self.ce_weight)  # ... over the hardest ce_topk percent of the voxels only (0: over all of them)
+        # for small lesions: the Tversky ratio, its focal exponent, one ratio over the batch, the focal cross-entropy (region: None with the first three at their defaults)
+        self.region, self.ce_focal_gamma = check_region(tversky_beta, focal_tversky_gamma, batch_dice, ce_focal_gamma, self.ce_weight, self.ce_topk)
+        self.tversky_beta, self.focal_tversky_gamma, self.batch_dice = (None, 1.0, False) if self.region is None else self.region
         self.topk_record = None  # with ce_topk: the select's record of the last call (device tensor of four int64: threshold_bits | passes_done << 32, n_gt, n_eq, K)
         # the reference's Dice_spvPA.forward ignores every option except the two below (it builds its inner Dice objects with fixed options)
         self.include_background, self.to_onehot_y, self.sigmoid, self.softmax = include_background, to_onehot_y, sigmoid, softmax
@@ -262,11 +321,14 @@ class Dice_spvPA(_Loss):
         atts: Sequence[torch.Tensor] = list(att_maps) if self.supervised_attention else []
         glogits_dst, gatt_bufs = landing
         with torch.no_grad():
-            st = _dice_forward(x, target, bool(self.supervised_attention), bool(self.hardness_weighting), atts, (self.ce_weight, self.ce_foreground_weight), self.ce_topk)
+            st = _dice_forward(x, target, bool(self.supervised_attention), bool(self.hardness_weighting), atts, (self.ce_weight, self.ce_foreground_weight), self.ce_topk, self.region, self.ce_focal_gamma)
             self.topk_record = st.topk_rec
             B, X, Y, Z = st.shape
             stream = torch.cuda.current_stream().cuda_stream
-            if st.ce_coef is None:
+            if st.opts is not None:
+                L.check(L.lib().vsseg_loss_pred_bwd_to(st.lg.data_ptr(), 2, st.lab.data_ptr(), B, X * Y * Z, st.hardness, st.coef.data_ptr(), None if st.ce_coef is None else st.ce_coef.data_ptr(), st.opts, None, glogits_dst,
+                                                       stream), "loss_pred_bwd_to")
+            elif st.ce_coef is None:
                 L.check(L.lib().vsseg_dice_pred_bwd_to(st.lg.data_ptr(), 2, st.lab.data_ptr(), B, X * Y * Z, st.hardness, st.coef.data_ptr(), None, glogits_dst, stream), "dice_pred_bwd_to")
             elif st.topk:
                 L.check(L.lib().vsseg_dice_ce_topk_pred_bwd_to(st.lg.data_ptr(), 2, st.lab.data_ptr(), B, X * Y * Z, st.hardness, st.coef.data_ptr(), st.ce_coef.data_ptr(), None, glogits_dst, stream), "dice_ce_topk_pred_bwd_to")
@@ -291,6 +353,6 @@ class Dice_spvPA(_Loss):
                 bd.n, bd.nlevels, bd.gscale = B, len(coarse), None
                 for j, (level, buf, nv) in enumerate(coarse):
                     bd.label[j], bd.datt[j], bd.nvox[j] = st.labels[level].data_ptr(), buf.data_ptr(), nv
-                    bd.coef[j] = st.coef.data_ptr() + 4 * (B * 4 + level * B * 2)
+                    bd.coef[j] = st.coef.data_ptr() + 4 * (st.npred + level * B * 2)
                 L.check(L.lib().vsseg_dice_att_bwd_levels(bd, stream), "dice_att_bwd_levels")
         return st.loss, written

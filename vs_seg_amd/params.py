@@ -26,7 +26,7 @@ from typing import Dict, Iterator, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import SGD, Adam, AdamW, Dice_spvPA, UNet2d5_spvPA, check_ce, check_ce_topk, check_optimizer, compute_dice_score, poly_lr, sliding_window_inference
+from . import SGD, Adam, AdamW, Dice_spvPA, UNet2d5_spvPA, check_ce, check_ce_topk, check_optimizer, check_region, compute_dice_score, poly_lr, sliding_window_inference
 from .optim import DEFAULT_WEIGHT_DECAY, LR_SCHEDULES, OPTIMIZERS
 from .inferers import argmax_segmentation, tta_masks
 from .metrics import MEASUREMENT_FIELDS, check_tolerances, compute_measurements, compute_surface_distances, compute_surface_metrics, surface_metric_fields, voxel_spacing
@@ -130,6 +130,10 @@ class VSparams:
         parser.add_argument("--ce_weight", type=float, default=0.0, metavar="LAMBDA", help="training loss: add LAMBDA times the voxel-wise cross-entropy of the final logits to the Dice loss (the Dice + CE loss of nnU-Net, MONAI's DiceCELoss; 0: off, the reference's loss)")
         parser.add_argument("--ce_foreground_weight", type=float, default=1.0, metavar="W", help="class weight of the foreground voxels in the cross-entropy term, the background's being 1 (needs --ce_weight > 0)")
         parser.add_argument("--ce_topk", type=float, default=0.0, metavar="PCT", help="training loss: average the cross-entropy term over the hardest PCT percent of the voxels of the batch only, selected on the GPU, and divide by their number K, not by the class-weight sum (the Dice + TopK loss of nnU-Net, DC_and_topk_loss: --ce_weight 1 --ce_topk 10; in (0, 100], needs --ce_weight > 0; 0: off, the mean over every voxel)")
+        parser.add_argument("--tversky_beta", type=float, default=None, metavar="BETA", help="training loss: replace every Dice ratio by the Tversky index (2I + eps) / (2 (1 - BETA) P + 2 BETA G + eps): BETA weights the missed tumour voxels, 1 - BETA the false positives (mirrored for the background class); in (0, 1), above 0.5 a missed voxel costs more, 0.5 is the Dice ratio (Salehi 2017, MONAI's TverskyLoss; default: off, 0.5 where --focal_tversky_gamma or --batch_dice is given)")
+        parser.add_argument("--focal_tversky_gamma", type=float, default=1.0, metavar="GAMMA", help="training loss: raise every region term 1 - T to the power GAMMA, floored at 1e-7 (the focal Tversky loss of Abraham 2019 is GAMMA = 0.75); in [0.25, 4] (1: off)")
+        parser.add_argument("--batch_dice", action="store_true", help="training loss: form one region ratio per class and per attention level over the pooled sums of the batch instead of one per sample, so that a sample without tumour has no ratio of its own (nnU-Net's batch_dice); under data parallelism the pool is the samples of the rank's own batch, nothing is exchanged between ranks")
+        parser.add_argument("--ce_focal_gamma", type=float, default=0.0, metavar="GAMMA", help="training loss: weight every voxel of the cross-entropy term by (1 - p_y)^GAMMA (the focal loss of MONAI's DiceFocalLoss; with --tversky_beta and --focal_tversky_gamma the Unified Focal family); in (0, 5], needs --ce_weight > 0, not together with --ce_topk; 0: off")
         parser.add_argument("--optimizer", type=str, default="adam", choices=list(OPTIMIZERS), help="adam: the reference's Adam with coupled weight decay; adamw: decoupled weight decay (torch.optim.AdamW); sgd: SGD with --momentum / --nesterov (nnU-Net: --optimizer sgd --nesterov --weight_decay 3e-5 --clip_grad_norm 12 --lr_schedule poly --initial_learning_rate 1e-2)")
         parser.add_argument("--momentum", type=float, default=None, metavar="MU", help="momentum of --optimizer sgd, in [0, 1) (default 0.99; sgd only)")
         parser.add_argument("--nesterov", action="store_true", help="Nesterov momentum (--optimizer sgd only)")
@@ -143,6 +147,7 @@ class VSparams:
             opt = check_optimizer(args.optimizer, args.momentum, args.nesterov, args.weight_decay, args.clip_grad_norm, args.lr_schedule, args.poly_power)
             ce_weight, ce_foreground_weight = check_ce(args.ce_weight, args.ce_foreground_weight)
             ce_topk = check_ce_topk(args.ce_topk, ce_weight)
+            region, ce_focal_gamma = check_region(args.tversky_beta, args.focal_tversky_gamma, args.batch_dice, args.ce_focal_gamma, ce_weight, ce_topk)
             augment = check_augment(*(getattr(args, "aug_" + k) for k in AUGMENT_KEYS))
             field = check_field_augment(args.aug_elastic_mag, args.aug_bias_field, args.aug_field_spacing)
             appearance = check_appearance_augment(*(getattr(args, "aug_" + k) for k in APPEARANCE_KEYS))
@@ -181,6 +186,8 @@ class VSparams:
         self.aug_elastic_mag, self.aug_bias_field, self.aug_field_spacing = (field[k] for k in FIELD_KEYS)
         self.aug_blur_sigma, self.aug_lowres, self.aug_contrast, self.aug_gamma, self.aug_appearance_prob = (appearance[k] for k in APPEARANCE_KEYS)
         self.ce_weight, self.ce_foreground_weight, self.ce_topk = ce_weight, ce_foreground_weight, ce_topk
+        self.tversky_beta, self.focal_tversky_gamma, self.batch_dice = region if region is not None else (None, 1.0, False)  # (None: the reference's Dice ratio per sample)
+        self.ce_focal_gamma = ce_focal_gamma
         self.results_folder_path = os.path.join(self.data_root, "results", "debug" if self.debug else args.results_folder_name)
         self.logs_path = os.path.join(self.results_folder_path, "logs")
         self.model_path = os.path.join(self.results_folder_path, "model")
@@ -220,6 +227,7 @@ class VSparams:
                           tuple("aug_" + k for k in AUGMENT_KEYS) if any(self.augment.values()) else ()) + (
                               ("aug_elastic_mag", "aug_bias_field", "aug_field_spacing") if self.aug_elastic_mag or self.aug_bias_field else ()) + (
                                   tuple("aug_" + k for k in APPEARANCE_KEYS) if self._appearance_on else ()) + (("ce_weight", "ce_foreground_weight") if self.ce_weight > 0 else ()) + (("ce_topk",) if self.ce_topk > 0 else ()) + (
+                                      ("tversky_beta", "focal_tversky_gamma", "batch_dice") if self.tversky_beta is not None else ()) + (("ce_focal_gamma",) if self.ce_focal_gamma > 0 else ()) + (
                                       (("optimizer",) + (("momentum", "nesterov") if self.optimizer == "sgd" else ())) if self.optimizer != "adam" else ()) + (
                                           ("clip_grad_norm",) if self.clip_grad_norm > 0 else ()) + (("lr_schedule", "poly_power") if self.lr_schedule == "poly" else ()):
             log("{:<34s} {}".format(k + " =", getattr(self, k)))
@@ -338,7 +346,8 @@ class VSparams:
 
     def set_and_get_loss_function(self):
         self.logger.info("Setting up the loss function...")
-        return Dice_spvPA(to_onehot_y=True, softmax=True, supervised_attention=self.attention, hardness_weighting=self.hardness, ce_weight=self.ce_weight, ce_foreground_weight=self.ce_foreground_weight, ce_topk=self.ce_topk)
+        return Dice_spvPA(to_onehot_y=True, softmax=True, supervised_attention=self.attention, hardness_weighting=self.hardness, ce_weight=self.ce_weight, ce_foreground_weight=self.ce_foreground_weight, ce_topk=self.ce_topk,
+                          tversky_beta=self.tversky_beta, focal_tversky_gamma=self.focal_tversky_gamma, batch_dice=self.batch_dice, ce_focal_gamma=self.ce_focal_gamma)
 
     def set_and_get_optimizer(self, model):
         self.logger.info("Setting up the optimizer...")
