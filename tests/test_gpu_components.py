@@ -1,7 +1,6 @@
 """-m gpu: vs_seg_amd.connected_components / keep_largest_component (csrc/components.hip) against the numpy union-find oracle: random masks, known
 answers, paths that cross every tile seam, the foreground rules, the full 512x512x120 volume, determinism, and VSparams --keep_largest_component end
 to end.  Every comparison is between integers or exact 0.0 / 1.0 values: no tolerance anywhere."""
-import argparse
 import csv
 import glob
 import os
@@ -14,16 +13,9 @@ pytestmark = pytest.mark.gpu
 
 from tests import components_oracle as CO  # noqa: E402
 from tests.test_components_host import CONNECTIVITIES, DENSITIES, SHAPES, random_mask  # noqa: E402
+from tests.volume_cases import far_island_case, full_size_outputs as _full_size_outputs, logits as _logits, run_inference as _run_inference  # noqa: E402
 from vs_seg_amd import compute_dice_score, compute_surface_distances, connected_components, keep_largest_component  # noqa: E402
 from vs_seg_amd.inferers import argmax_segmentation  # noqa: E402
-
-
-def _logits(pred):
-    """[B,2,X,Y,Z] logits whose argmax is `pred` [B,X,Y,Z], with random magnitudes."""
-    rng = np.random.default_rng(11)
-    a = rng.standard_normal(pred.shape).astype(np.float32)
-    b = a + np.where(pred, 1.0, -1.0).astype(np.float32) * rng.uniform(0.01, 2.0, pred.shape).astype(np.float32)
-    return torch.from_numpy(np.stack([a, b], 1)).cuda()
 
 
 def _check_labels(masks, connectivity):
@@ -51,7 +43,7 @@ def _check_keep(masks, connectivity):
     return out
 
 
-@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("shape", SHAPES + [(9, 17, 130)])  # (the last one: every axis straddles the tile and z crosses two seams, as the morphology routes are tested)
 @pytest.mark.parametrize("density", DENSITIES)
 @pytest.mark.parametrize("connectivity", CONNECTIVITIES)
 def test_labels_against_oracle_random_masks(shape, density, connectivity):
@@ -134,18 +126,9 @@ def test_empty_prediction():
     assert not stats.any() and torch.equal(out[:, 0], torch.ones_like(out[:, 0])) and not out[:, 1].any()
 
 
-def _full_size_outputs(pred):
-    cl = torch.full((1, *pred.shape, 2), -1.0, device="cuda")
-    cl[0, ..., 1] = torch.where(torch.from_numpy(pred).cuda(), 1.0, -2.0)
-    return cl.permute(0, 4, 1, 2, 3)  # [1,2,X,Y,Z] view of channels-last storage, as sliding_window_inference returns it
-
-
 def test_full_size_channels_last_drops_the_far_island():
     """The tumour + far island of the surface-distance test at 512 x 512 x 120: the island goes, and with it the 100 mm Hausdorff distance."""
-    shape = (512, 512, 120)
-    g = np.ogrid[: shape[0], : shape[1], : shape[2]]
-    tum = lambda c, r: ((g[0] - c[0]) / r[0]) ** 2 + ((g[1] - c[1]) / r[1]) ** 2 + ((g[2] - c[2]) / r[2]) ** 2 <= 1.0  # noqa: E731
-    tumour, island = tum((302, 219, 61), (13, 12, 5)), tum((40, 470, 12), (3, 2, 1.5))
+    tumour, island, gt = far_island_case()
     assert tumour.sum() == 3213 and island.sum() == 41
     outputs = _full_size_outputs(tumour | island)
     before = outputs.clone()
@@ -160,7 +143,7 @@ def test_full_size_channels_last_drops_the_far_island():
     island_label = int(np.flatnonzero(island.ravel())[0]) + 1
     want = torch.from_numpy(np.where(tumour, label, 0) + np.where(island, island_label, 0)).to(torch.int32).cuda()
     assert torch.equal(labels[0], want)
-    lab = torch.from_numpy(tum((300, 220, 60), (14, 11, 5)).astype(np.float32))[None, None].cuda()
+    lab = torch.from_numpy(gt.astype(np.float32))[None, None].cuda()
     spacing = (0.41, 0.41, 1.5)
     clean = compute_surface_distances(_full_size_outputs(tumour), lab, spacing, None)
     assert torch.equal(compute_surface_distances(filtered, lab, spacing, None), clean)
@@ -209,47 +192,6 @@ def test_deterministic_batch_equals_single_calls_and_second_stream():
             ld, _ = connected_components(lg, c)
         side.synchronize()
         assert torch.equal(a, d) and torch.equal(sa, sd) and torch.equal(la, ld)
-
-
-class _BrightVoxels:
-    """A stand-in network: class 1 where the image is brighter than `threshold`, so that the prediction is the bright tumour plus scattered noise voxels."""
-
-    def __init__(self, threshold):
-        self.threshold = threshold
-
-    def eval(self):
-        return self
-
-    def __call__(self, x):
-        return (torch.cat([torch.zeros_like(x), x - self.threshold], 1),)
-
-
-def _run_inference(tmp_path, extra, bright_quantile=None):
-    from tests.test_gpu_data import _write_cases
-    from vs_seg_amd.params import VSparams
-
-    root = str(tmp_path)
-    split = _write_cases(root, 4, np.random.default_rng(3))
-    argv = ["--split", split, "--data_root", root, "--results_folder_name", "t", "--compute_dtype", "fp32"] + extra
-    p = VSparams(argparse.ArgumentParser(), argv)
-    p.sliding_window_inferer_roi_size = [64, 64, 16]
-    p.create_results_folders()
-    logger = p.set_up_logger("test_log.txt")
-    p.log_parameters()
-    _, _, test_files = p.load_T1_or_T2_data()
-    _, _, stf = p.get_transforms()
-    test_loader = p.cache_transformed_test_data(test_files, stf)
-    torch.manual_seed(0)
-    if bright_quantile is None:
-        model = p.set_and_get_model()
-        model.eval()
-    else:
-        model = _BrightVoxels(float(next(iter(test_loader))["image"].flatten().quantile(bright_quantile)))
-    scores = p.run_inference(model, test_loader)
-    for h in list(logger.handlers):
-        logger.removeHandler(h)
-        h.close()
-    return p, model, test_loader, scores, open(os.path.join(p.logs_path, "test_log.txt")).read()
 
 
 @pytest.mark.parametrize("connectivity", [26, 6])

@@ -5,7 +5,6 @@ numpy oracle, known answers, empty masks, the foreground rules of compute_dice_s
 Tolerances: counts equal; volumes and the centroid distance rtol 1e-9 (a handful of fp64 operations on exact integers); diameters rtol 1e-6 (d^2
 carries at most three products and two sums in fp32: off by at most about 6 * 2^-24 = 3.6e-7, d by half of that); diameters at unit spacing and
 extents below 2048 equal (every d^2 is an integer below 2^24)."""
-import argparse
 import csv
 import os
 
@@ -16,7 +15,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from tests import measure_oracle as MO  # noqa: E402
-from tests.test_gpu_surface_metrics import _ellipsoids, _label, _logits  # noqa: E402
+from tests.test_gpu_surface_metrics import _ellipsoids  # noqa: E402
+from tests.volume_cases import far_island_case, full_size_outputs, label as _label, logits as _logits, run_inference as _run_inference  # noqa: E402
 from vs_seg_amd import MEASUREMENT_FIELDS, compute_measurements  # noqa: E402
 
 COUNTS, EXACT64, DIAMETERS = [0, 1], [2, 3, 4], [5, 6, 7, 8]
@@ -167,14 +167,9 @@ def test_foreground_rules_match_compute_dice_score():
 def test_full_size_channels_last_with_far_island():
     """512 x 512 x 120 with the logits in the channels-last view the sliding window returns: a tumour ellipsoid in both masks (shifted in the
     prediction) and one far false-positive island, which sets the prediction's diameter."""
-    shape = (512, 512, 120)
-    g = np.ogrid[: shape[0], : shape[1], : shape[2]]
-    tum = lambda c, r: ((g[0] - c[0]) / r[0]) ** 2 + ((g[1] - c[1]) / r[1]) ** 2 + ((g[2] - c[2]) / r[2]) ** 2 <= 1.0  # noqa: E731
-    gt = tum((300, 220, 60), (14, 11, 5))
-    pred = tum((302, 219, 61), (13, 12, 5)) | tum((40, 470, 12), (3, 2, 1.5))
-    cl = torch.full((1, *shape, 2), -1.0, device="cuda")
-    cl[0, ..., 1] = torch.where(torch.from_numpy(pred).cuda(), 1.0, -2.0)
-    outputs = cl.permute(0, 4, 1, 2, 3)  # [1,2,X,Y,Z] view of channels-last storage, as sliding_window_inference returns it
+    tumour, island, gt = far_island_case()
+    pred = tumour | island
+    outputs = full_size_outputs(pred)
     lab = torch.from_numpy(gt.astype(np.float32))[None, None].cuda()
     spacing = (0.41, 0.41, 1.5)
     got = compute_measurements(outputs, lab, spacing).cpu().numpy()
@@ -193,31 +188,6 @@ def test_deterministic_and_batch_equals_single_calls():
     assert torch.equal(a, b) and not torch.isnan(a).any()
     singles = torch.cat([compute_measurements(lg[i:i + 1], lab[i:i + 1], (0.41, 0.43, 1.5)) for i in range(2)])
     assert torch.equal(a, singles)
-
-
-def _run_inference(tmp_path, flags):
-    from tests.test_gpu_data import _write_cases
-    from vs_seg_amd.params import VSparams
-
-    root = str(tmp_path)
-    split = _write_cases(root, 4, np.random.default_rng(3))
-    argv = ["--split", split, "--data_root", root, "--results_folder_name", "t", "--compute_dtype", "fp32"] + list(flags)
-    p = VSparams(argparse.ArgumentParser(), argv)
-    p.sliding_window_inferer_roi_size = [64, 64, 16]
-    p.create_results_folders()
-    logger = p.set_up_logger("test_log.txt")
-    p.log_parameters()
-    _, _, test_files = p.load_T1_or_T2_data()
-    _, _, stf = p.get_transforms()
-    test_loader = p.cache_transformed_test_data(test_files, stf)
-    torch.manual_seed(0)
-    model = p.set_and_get_model()
-    model.eval()
-    scores = p.run_inference(model, test_loader)
-    for h in list(logger.handlers):
-        logger.removeHandler(h)
-        h.close()
-    return p, model, test_loader, scores, open(os.path.join(p.logs_path, "test_log.txt")).read()
 
 
 PER_CASE = ("volume_pred_mm3", "volume_label_mm3", "volume_error_mm3", "centroid_distance_mm", "max_diameter_pred_mm", "max_diameter_label_mm", "max_axial_diameter_pred_mm",

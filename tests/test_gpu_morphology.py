@@ -1,7 +1,6 @@
 """-m gpu: vs_seg_amd.fill_holes / remove_small_components (csrc/components.hip) against the numpy oracle (tests/morphology_oracle.py): random masks, known
 answers, cavities that cross every tile seam, the foreground rules, the full 512x512x120 volume, determinism, and VSparams --fill_holes /
 --min_component_mm3 end to end.  Every comparison is between integers or exact 0.0 / 1.0 values: no tolerance anywhere."""
-import argparse
 import csv
 import functools
 import glob
@@ -17,17 +16,10 @@ from tests import components_oracle as CO  # noqa: E402
 from tests import morphology_oracle as MO  # noqa: E402
 from tests.test_components_host import random_mask  # noqa: E402
 from tests.test_morphology_host import CONNECTIVITIES, FILL_DENSITIES, KNOWN, SHAPES, SMALL_DENSITIES  # noqa: E402
+from tests.volume_cases import full_size_ellipsoid as ell, full_size_outputs as _full_size_outputs, logits as _logits, run_inference as _run_inference  # noqa: E402
 from vs_seg_amd import (compute_dice_score, compute_surface_distances, connected_components, fill_holes, keep_largest_component, min_component_voxels,  # noqa: E402
                         remove_small_components)
 from vs_seg_amd.inferers import argmax_segmentation  # noqa: E402
-
-
-def _logits(pred):
-    """[B,2,X,Y,Z] logits whose argmax is `pred` [B,X,Y,Z], with random magnitudes."""
-    rng = np.random.default_rng(11)
-    a = rng.standard_normal(pred.shape).astype(np.float32)
-    b = a + np.where(pred, 1.0, -1.0).astype(np.float32) * rng.uniform(0.01, 2.0, pred.shape).astype(np.float32)
-    return torch.from_numpy(np.stack([a, b], 1)).cuda()
 
 
 def _check_fill(masks, connectivity, want=None):
@@ -225,20 +217,11 @@ def test_empty_and_all_foreground_small_volumes():
     assert torch.equal(out, full)
 
 
-def _full_size_outputs(pred):
-    cl = torch.full((1, *pred.shape, 2), -1.0, device="cuda")
-    cl[0, ..., 1] = torch.where(torch.from_numpy(pred).cuda(), 1.0, -2.0)
-    return cl.permute(0, 4, 1, 2, 3)  # [1,2,X,Y,Z] view of channels-last storage, as sliding_window_inference returns it
-
-
 @functools.lru_cache(maxsize=1)
 def _full_size_case():
     """512 x 512 x 120: an ellipsoid with an inner cavity and a 5-voxel island far away, built analytically (the numpy oracle is not run at 31 M voxels)."""
-    shape = (512, 512, 120)
-    g = np.ogrid[: shape[0], : shape[1], : shape[2]]
-    ell = lambda c, r: ((g[0] - c[0]) / r[0]) ** 2 + ((g[1] - c[1]) / r[1]) ** 2 + ((g[2] - c[2]) / r[2]) ** 2 <= 1.0  # noqa: E731
     tumour, cavity = ell((302, 219, 61), (13, 12, 5)), ell((303, 218, 62), (6, 5, 2))
-    island = np.zeros(shape, bool)
+    island = np.zeros(tumour.shape, bool)
     island[40, 470:475, 12] = True
     assert tumour.sum() == 3213 and cavity.sum() == 235 and not (cavity & ~ell((302, 219, 61), (11, 10, 4))).any()  # the cavity lies well inside
     return tumour, cavity, island
@@ -314,43 +297,6 @@ def test_deterministic_batch_equals_single_calls_and_second_stream():
             side.synchronize()
             assert torch.equal(a, d) and torch.equal(sa, sd)
         assert int(fill_holes(lg, c, return_stats=True)[1][:, 2].sum()) > 0
-
-
-class _BrightVoxels:
-    """A stand-in network: class 1 where the image is brighter than `threshold`, so that the prediction is the bright tumour plus scattered noise voxels."""
-
-    def __init__(self, threshold):
-        self.threshold = threshold
-
-    def eval(self):
-        return self
-
-    def __call__(self, x):
-        return (torch.cat([torch.zeros_like(x), x - self.threshold], 1),)
-
-
-def _run_inference(tmp_path, extra, bright_quantile):
-    from tests.test_gpu_data import _write_cases
-    from vs_seg_amd.params import VSparams
-
-    root = str(tmp_path)
-    split = _write_cases(root, 4, np.random.default_rng(3))
-    argv = ["--split", split, "--data_root", root, "--results_folder_name", "t", "--compute_dtype", "fp32"] + extra
-    p = VSparams(argparse.ArgumentParser(), argv)
-    p.sliding_window_inferer_roi_size = [64, 64, 16]
-    p.create_results_folders()
-    logger = p.set_up_logger("test_log.txt")
-    p.log_parameters()
-    _, _, test_files = p.load_T1_or_T2_data()
-    _, _, stf = p.get_transforms()
-    test_loader = p.cache_transformed_test_data(test_files, stf)
-    torch.manual_seed(0)
-    model = _BrightVoxels(float(next(iter(test_loader))["image"].flatten().quantile(bright_quantile)))
-    scores = p.run_inference(model, test_loader)
-    for h in list(logger.handlers):
-        logger.removeHandler(h)
-        h.close()
-    return p, model, test_loader, scores, open(os.path.join(p.logs_path, "test_log.txt")).read()
 
 
 OLD_HEADER = ["case", "dice_raw", "dice", "components", "foreground_voxels", "kept_voxels"]

@@ -1,7 +1,6 @@
 """-m gpu: vs_seg_amd.compute_surface_metrics / compute_surface_dice (normalised surface Dice at mm tolerances from the edge pass and distance transform of the
 surface distances, csrc/surface.hip) against the numpy oracle, known answers with exact ties, the empty-mask rules, bit equality with
 compute_surface_distances, the full 512x512x120 volume, and VSparams --surface_dice_mm end to end."""
-import argparse
 import csv
 import functools
 import os
@@ -14,7 +13,8 @@ pytestmark = pytest.mark.gpu
 
 from tests import surface_dice_oracle as SDO  # noqa: E402
 from tests import surface_oracle as SO  # noqa: E402
-from tests.test_gpu_surface_metrics import _check, _ellipsoids, _label, _logits  # noqa: E402
+from tests.test_gpu_surface_metrics import _check, _ellipsoids  # noqa: E402
+from tests.volume_cases import far_island_case, full_size_outputs, label as _label, logits as _logits, run_inference as _run_inference  # noqa: E402
 from vs_seg_amd import compute_surface_dice, compute_surface_distances, compute_surface_metrics, surface_metric_fields  # noqa: E402
 
 TOL_EXACT = (0.0, 1.0, 1.5, 2.0, 3.3)  # at spacing None and (0.5, 0.5, 1.5): the fp32 field is exact, so ties are decided exactly
@@ -127,14 +127,9 @@ def test_shares_the_call_with_the_surface_distances():
 def test_full_size_channels_last_with_far_island():
     """The 512 x 512 x 120 case of test_gpu_surface_metrics: a tumour ellipsoid in both masks (shifted in the prediction) and one far false-positive island.  The
     island shows in the surface precision and in masd, and not in the recall."""
-    shape = (512, 512, 120)
-    g = np.ogrid[: shape[0], : shape[1], : shape[2]]
-    tum = lambda c, r: ((g[0] - c[0]) / r[0]) ** 2 + ((g[1] - c[1]) / r[1]) ** 2 + ((g[2] - c[2]) / r[2]) ** 2 <= 1.0  # noqa: E731
-    gt = tum((300, 220, 60), (14, 11, 5))
-    pred = tum((302, 219, 61), (13, 12, 5)) | tum((40, 470, 12), (3, 2, 1.5))
-    cl = torch.full((1, *shape, 2), -1.0, device="cuda")
-    cl[0, ..., 1] = torch.where(torch.from_numpy(pred).cuda(), 1.0, -2.0)
-    outputs = cl.permute(0, 4, 1, 2, 3)  # [1,2,X,Y,Z] view of channels-last storage, as sliding_window_inference returns it
+    tumour, island, gt = far_island_case()
+    pred = tumour | island
+    outputs = full_size_outputs(pred)
     lab = torch.from_numpy(gt.astype(np.float32))[None, None].cuda()
     spacing, tol = (0.41, 0.41, 1.5), (0.0, 0.5, 1.0, 2.0, 3.0)
     assert SDO.near_ties(pred, gt, spacing, tol, 1e-4) == 0
@@ -145,30 +140,6 @@ def test_full_size_channels_last_with_far_island():
     print("got", got.cpu().numpy().tolist(), "want", want.tolist())
     _check_all(got.cpu().numpy(), [want])
     assert torch.equal(got[:, :2], compute_surface_distances(outputs, lab, spacing, 95.0))
-
-
-def _run_inference(tmp_path, flags):
-    from tests.test_gpu_data import _write_cases
-    from vs_seg_amd.params import VSparams
-
-    root = str(tmp_path)
-    split = _write_cases(root, 4, np.random.default_rng(3))
-    p = VSparams(argparse.ArgumentParser(), ["--split", split, "--data_root", root, "--results_folder_name", "t", "--compute_dtype", "fp32"] + flags)
-    p.sliding_window_inferer_roi_size = [64, 64, 16]
-    p.create_results_folders()
-    logger = p.set_up_logger("test_log.txt")
-    p.log_parameters()
-    _, _, test_files = p.load_T1_or_T2_data()
-    _, _, stf = p.get_transforms()
-    test_loader = p.cache_transformed_test_data(test_files, stf)
-    torch.manual_seed(0)
-    model = p.set_and_get_model()
-    model.eval()
-    scores = p.run_inference(model, test_loader)
-    for h in list(logger.handlers):
-        logger.removeHandler(h)
-        h.close()
-    return p, model, test_loader, scores, open(os.path.join(p.logs_path, "test_log.txt")).read()
 
 
 def test_vsparams_surface_dice_end_to_end(tmp_path):

@@ -1,6 +1,5 @@
 """-m gpu: vs_seg_amd.compute_surface_distances (HD / ASSD on the device, csrc/surface.hip) against the brute-force numpy oracle, known answers,
 empty masks, the foreground rules of compute_dice_score, the full 512x512x120 volume, determinism, and VSparams --surface_metrics end to end."""
-import argparse
 import csv
 import os
 
@@ -11,6 +10,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from tests import surface_oracle as SO  # noqa: E402
+from tests.volume_cases import far_island_case, full_size_outputs, label as _label, logits as _logits, run_inference  # noqa: E402
 from vs_seg_amd import compute_surface_distances  # noqa: E402
 
 
@@ -24,18 +24,6 @@ def _ellipsoids(shape, rng, k):
         r = [rng.uniform(0.15, 0.45) * s + 0.6 for s in shape]
         m |= sum(((gi - ci) / ri) ** 2 for gi, ci, ri in zip(g, c, r)) <= 1.0
     return m
-
-
-def _logits(pred):
-    """[B,2,X,Y,Z] logits whose argmax is `pred` [B,X,Y,Z], with random magnitudes."""
-    rng = np.random.default_rng(11)
-    a = rng.standard_normal(pred.shape).astype(np.float32)
-    b = a + np.where(pred, 1.0, -1.0).astype(np.float32) * rng.uniform(0.01, 2.0, pred.shape).astype(np.float32)
-    return torch.from_numpy(np.stack([a, b], 1)).cuda()
-
-
-def _label(gt):
-    return torch.from_numpy(gt[:, None].astype(np.float32)).cuda()
 
 
 def _check(got, want):
@@ -113,14 +101,9 @@ def test_foreground_rules_match_compute_dice_score():
 def test_full_size_channels_last_with_far_island():
     """512 x 512 x 120 with the logits in the channels-last view the sliding window returns: a tumour ellipsoid in both masks (shifted in the
     prediction) and one far false-positive island; the masks are small, so the brute-force oracle needs no scipy."""
-    shape = (512, 512, 120)
-    g = np.ogrid[: shape[0], : shape[1], : shape[2]]
-    tum = lambda c, r: ((g[0] - c[0]) / r[0]) ** 2 + ((g[1] - c[1]) / r[1]) ** 2 + ((g[2] - c[2]) / r[2]) ** 2 <= 1.0  # noqa: E731
-    gt = tum((300, 220, 60), (14, 11, 5))
-    pred = tum((302, 219, 61), (13, 12, 5)) | tum((40, 470, 12), (3, 2, 1.5))
-    cl = torch.full((1, *shape, 2), -1.0, device="cuda")
-    cl[0, ..., 1] = torch.where(torch.from_numpy(pred).cuda(), 1.0, -2.0)
-    outputs = cl.permute(0, 4, 1, 2, 3)  # [1,2,X,Y,Z] view of channels-last storage, as sliding_window_inference returns it
+    tumour, island, gt = far_island_case()
+    pred = tumour | island
+    outputs = full_size_outputs(pred)
     lab = torch.from_numpy(gt.astype(np.float32))[None, None].cuda()
     spacing = (0.41, 0.41, 1.5)
     hd95 = compute_surface_distances(outputs, lab, spacing, 95.0).cpu().numpy()
@@ -143,35 +126,10 @@ def test_deterministic_and_batch_equals_single_calls():
     assert torch.equal(a, singles)
 
 
-def _run_inference(tmp_path, surface):
-    from tests.test_gpu_data import _write_cases
-    from vs_seg_amd.params import VSparams
-
-    root = str(tmp_path)
-    split = _write_cases(root, 4, np.random.default_rng(3))
-    argv = ["--split", split, "--data_root", root, "--results_folder_name", "t", "--compute_dtype", "fp32"] + (["--surface_metrics"] if surface else [])
-    p = VSparams(argparse.ArgumentParser(), argv)
-    p.sliding_window_inferer_roi_size = [64, 64, 16]
-    p.create_results_folders()
-    logger = p.set_up_logger("test_log.txt")
-    p.log_parameters()
-    _, _, test_files = p.load_T1_or_T2_data()
-    _, _, stf = p.get_transforms()
-    test_loader = p.cache_transformed_test_data(test_files, stf)
-    torch.manual_seed(0)
-    model = p.set_and_get_model()
-    model.eval()
-    scores = p.run_inference(model, test_loader)
-    for h in list(logger.handlers):
-        logger.removeHandler(h)
-        h.close()
-    return p, model, test_loader, scores, open(os.path.join(p.logs_path, "test_log.txt")).read()
-
-
 def test_vsparams_surface_metrics_end_to_end(tmp_path):
     from vs_seg_amd import sliding_window_inference
 
-    p, model, loader, scores, log = _run_inference(tmp_path / "on", True)
+    p, model, loader, scores, log = run_inference(tmp_path / "on", ["--surface_metrics"])
     assert scores.shape == (1,)
     assert "hd95_mm[0] = " in log and "assd_mm[0] = " in log and "mean_hd95_mm = " in log and "mean_assd_mm = " in log and "surface_metrics =" in log
     rows = list(csv.DictReader(open(os.path.join(p.figures_path, "test_surface_metrics.csv"))))
@@ -184,6 +142,6 @@ def test_vsparams_surface_metrics_end_to_end(tmp_path):
     got = np.array([float(rows[0]["hd95_mm"]), float(rows[0]["assd_mm"])])
     np.testing.assert_array_equal(got, want.astype(np.float64))  # (equal_nan: NaN and inf compare equal to themselves)
 
-    p2, _, _, _, log2 = _run_inference(tmp_path / "off", False)
+    p2, _, _, _, log2 = run_inference(tmp_path / "off", [])
     assert not os.path.exists(os.path.join(p2.figures_path, "test_surface_metrics.csv"))
     assert "hd95" not in log2 and "assd" not in log2 and "surface_metrics =" not in log2  # (the tmp path holds this test's name)

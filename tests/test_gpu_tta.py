@@ -150,7 +150,7 @@ def test_sharded_inference_with_mirrored_passes_equals_the_single_process_result
 
 
 def test_vsparams_tta_flips_end_to_end(tmp_path):
-    from tests.test_gpu_components import _run_inference
+    from tests.volume_cases import run_inference as _run_inference
 
     p, model, loader, scores, log = _run_inference(tmp_path / "on", ["--tta_flips", "0"])
     assert scores.shape == (1,) and "tta_flips =" in log and "tta_average =" in log

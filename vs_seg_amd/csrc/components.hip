@@ -13,24 +13,23 @@
 //             final root of a component is its smallest index whatever the order of the unions.
 //   flatten   parent[v] = root(v); a root zeroes its own size counter (the only counters that are ever read).
 //   sizes     voxels per root: a workgroup sums the component of its smallest root in LDS (one atomic per tile for a compact component), the others per wave.
-//   select    every root offers (size << 32) | (0xFFFFFFFF - label) to one 64-bit atomicMax (largest size, then smallest label) and is counted.
+//   tally     every root offers (size << 32) | (0xFFFFFFFF - label) to one 64-bit atomicMax (largest size, then smallest label) and is counted.
 //   write     the whole volume: int32 labels (root + 1), or the one-hot fp32 prediction of the selected component; parents are read inside the box only.
 //             Writes 4 B (labels) or 8 B (one-hot) per voxel.  Block 0 also writes the four statistics.
 //
-// merge .. select run on grids sized for the volume; workgroups whose tile misses the bounding box (which lives in device memory) exit at once.  No kernel waits for
+// merge .. tally run on grids sized for the volume; workgroups whose tile misses the bounding box (which lives in device memory) exit at once.  No kernel waits for
 // another workgroup: every loop either walks parent links towards strictly smaller indices or retries an atomicMin with a strictly smaller operand.  Only integer
 // atomics decide anything, so the result is a function of the mask alone.
 //
 // Two more routes through the same passes, with the same two properties (vsseg_remove_small_components, vsseg_fill_holes):
-//   remove small  init, local, merge, flatten, sizes as above; `count` (for `select`): the roots, and those with cnt[root] >= min_voxels with their voxels;
+//   remove small  init, local, merge, flatten, sizes as above; `tally`: the roots, and those with cnt[root] >= min_voxels with their voxels;
 //                 `write`: one-hot of cnt[root] >= min_voxels.  min_voxels is a kernel argument.
 //   fill holes    init; `scan`: the logits of the whole volume once (8 B per voxel), leaving |P| and the bounding box of P; then local (on the COMPLEMENT of P inside
 //                 the box, the logits of the box read again), merge and a flatten that also marks the roots with a voxel on a face of the box, all confined to the
-//                 box; `count`: unmarked roots (holes) and their voxels; `write`: one-hot of P or unmarked, 8 B per voxel.  Why the box suffices: above fh_scan_kernel.
+//                 box; `tally`: unmarked roots (holes) and their voxels; `write`: one-hot of P or unmarked, 8 B per voxel.  Why the box suffices: above fh_scan_kernel.
 //                 Background comes as whole rows, so this route's local pass labels a tile of 32 equal single-run rows without a union, and its merge pass makes
 //                 one union per lane and neighbour tile, not one per row (cc_unite); neither changes a label.
-#include <limits.h>
-#include "common.h"
+#include "volume.h"
 
 namespace {
 
@@ -49,29 +48,19 @@ struct CompRec {
 struct CompLayout {
   int64_t parent, cnt, total;
 };
-inline int64_t cc_align(int64_t v) { return (v + 255) & ~(int64_t)255; }
 CompLayout cc_layout(int64_t nvox) {
   CompLayout l;
-  l.parent = cc_align(sizeof(CompRec));
-  l.cnt = l.parent + cc_align(nvox * 4);
-  l.total = l.cnt + cc_align(nvox * 4);
+  l.parent = align256(sizeof(CompRec));
+  l.cnt = l.parent + align256(nvox * 4);
+  l.total = l.cnt + align256(nvox * 4);
   return l;
 }
+enum CompRoute { CC_LABELS, CC_LARGEST, CC_SMALL, CC_HOLES };  // the four entry points; CC_LABELS and CC_LARGEST differ in what `write` stores only
 
 // the four forward neighbour rows of a row (with dz = -1, 0, 1 each) and the row itself (dz = +1 only): the 13 offsets that follow (0, 0, 0) in raster order
 __device__ __forceinline__ int cc_dx(int n) { return n >= 2 ? 1 : 0; }      // n = 0 .. 4: (0, 0), (0, 1), (1, -1), (1, 0), (1, 1)
 __device__ __forceinline__ int cc_dy(int n) { return n < 2 ? n : n - 3; }
 
-__device__ __forceinline__ int cc_wave_min(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int cc_wave_max(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
 __device__ __forceinline__ bool cc_bit(unsigned long long m, int i) { return (m >> i) & 1ull; }
 
 // Union-find over an array of parent links with L[i] <= i (a root has L[i] == i).  LDS: workgroup scope; global memory: agent scope, so that a link another
@@ -101,9 +90,22 @@ __device__ __forceinline__ void cc_union(int* L, int a, int b) {
   }
 }
 
-__device__ __forceinline__ bool cc_tile_outside_box(const CompRec* __restrict__ rec, int x0, int y0, int z0) {
-  return rec->bmax[0] < x0 || rec->bmin[0] >= x0 + CT_X || rec->bmax[1] < y0 || rec->bmin[1] >= y0 + CT_Y || rec->bmax[2] < z0 || rec->bmin[2] >= z0 + CT_Z;
-}
+// The tile of a workgroup and a thread's place in it: wave w owns the rows r = 4 k + w (x = x0 + r / 8, y = y0 + r % 8), lane l the voxel z = z0 + l of each.
+struct CompTile {
+  const int x0 = blockIdx.z * CT_X, y0 = blockIdx.y * CT_Y, z0 = blockIdx.x * CT_Z;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, z = z0 + lane;
+  __device__ __forceinline__ bool outside_box(const CompRec* rec, int margin = 0) const {  // no voxel within `margin` of the box (an empty box: every tile)
+    return rec->bmax[0] + margin < x0 || rec->bmin[0] - margin >= x0 + CT_X || rec->bmax[1] + margin < y0 || rec->bmin[1] - margin >= y0 + CT_Y ||
+           rec->bmax[2] + margin < z0 || rec->bmin[2] - margin >= z0 + CT_Z;
+  }
+  template <typename F>
+  __device__ __forceinline__ void rows(int X, int Y, F f) const {  // f(r, x, y) for this wave's rows inside the volume
+    for (int k = 0; k < CT_ROWS / 4; ++k) {
+      const int r = k * 4 + wave, x = x0 + (r >> 3), y = y0 + (r & 7);
+      if (x < X && y < Y) f(r, x, y);  // (the same in every lane of the wave)
+    }
+  }
+};
 
 __global__ __launch_bounds__(256) void cc_init_kernel(CompRec* rec) {
   if (threadIdx.x == 0) {
@@ -112,10 +114,7 @@ __global__ __launch_bounds__(256) void cc_init_kernel(CompRec* rec) {
     rec->ncomp = 0;
     rec->nkept = 0;
   }
-  if (threadIdx.x < 3) {
-    rec->bmin[threadIdx.x] = INT_MAX;
-    rec->bmax[threadIdx.x] = -1;
-  }
+  box_reset(rec->bmin, rec->bmax, 3);
 }
 
 // HOLES: the mask is the COMPLEMENT of P inside the bounding box of P, which an earlier pass (fh_scan_kernel) has left in the record: background voxels of the box get
@@ -126,14 +125,12 @@ __global__ __launch_bounds__(256) void cc_local_kernel(const float* __restrict__
                                                       CompRec* __restrict__ rec) {
   __shared__ unsigned long long rowmask[CT_ROWS];
   __shared__ int L[CT_ROWS * CT_Z];
-  const int z0 = blockIdx.x * CT_Z, y0 = blockIdx.y * CT_Y, x0 = blockIdx.z * CT_X;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int z = z0 + lane;
+  const CompTile t;
+  const int x0 = t.x0, y0 = t.y0, z0 = t.z0, wave = t.wave, lane = t.lane, z = t.z;
   int b0x = 0, b0y = 0, b0z = 0, b1x = 0, b1y = 0, b1z = 0;
   if constexpr (HOLES) {
+    if (t.outside_box(rec, 1)) return;
     b0x = rec->bmin[0], b0y = rec->bmin[1], b0z = rec->bmin[2], b1x = rec->bmax[0], b1y = rec->bmax[1], b1z = rec->bmax[2];
-    // (an empty P has bmin = INT_MAX: every tile leaves here)
-    if (b1x + 1 < x0 || b0x - 1 >= x0 + CT_X || b1y + 1 < y0 || b0y - 1 >= y0 + CT_Y || b1z + 1 < z0 || b0z - 1 >= z0 + CT_Z) return;
   }
   float2 lg[CT_ROWS / 4];
   bool in[CT_ROWS / 4];  // HOLES: the voxel lies in the volume and in the box
@@ -149,7 +146,7 @@ __global__ __launch_bounds__(256) void cc_local_kernel(const float* __restrict__
 #pragma unroll
   for (int k = 0; k < CT_ROWS / 4; ++k) {
     const int r = k * 4 + wave;
-    const bool m = HOLES ? in[k] && !(lg[k].y > lg[k].x) : lg[k].y > lg[k].x;
+    const bool m = HOLES ? in[k] && !vsseg_pred_fg(lg[k]) : vsseg_pred_fg(lg[k]);
     const unsigned long long bits = __ballot(m);
     if (lane == 0) rowmask[r] = bits;
     const unsigned long long gaps = ~bits & ((1ull << lane) - 1ull);  // background voxels below this one: the run starts behind the highest of them
@@ -214,23 +211,18 @@ __global__ __launch_bounds__(256) void cc_local_kernel(const float* __restrict__
     }
     parent[((int64_t)x * Y + y) * Z + z] = p;
     if constexpr (HOLES)
-      if (p >= 0) cnt[((int64_t)x * Y + y) * Z + z] = 0;  // the mark of a root that touches a face of the box (fh_flatten_kernel); only a root's is ever read
+      if (p >= 0) cnt[((int64_t)x * Y + y) * Z + z] = 0;  // the mark of a root that touches a face of the box (cc_flatten_kernel<true>); only a root's is ever read
   }
   if constexpr (HOLES) return;  // |P| and the box are there already
   if (wave == 0) {  // lanes 0 .. 31: one row each
     const unsigned long long bits = lane < CT_ROWS ? rowmask[lane & (CT_ROWS - 1)] : 0ull;
-    const bool has = bits != 0;
-    unsigned n = (unsigned)__builtin_popcountll(bits);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
     const int x = x0 + (lane >> 3), y = y0 + (lane & 7);
-    const int lo0 = cc_wave_min(has ? x : INT_MAX), lo1 = cc_wave_min(has ? y : INT_MAX), lo2 = cc_wave_min(has ? z0 + __builtin_ctzll(bits | (1ull << 63)) : INT_MAX);
-    const int hi0 = cc_wave_max(has ? x : -1), hi1 = cc_wave_max(has ? y : -1), hi2 = cc_wave_max(has ? z0 + 63 - __builtin_clzll(bits | 1ull) : -1);
-    if (lane == 0) {  // integer atomics: the record does not depend on the order in which workgroups finish
-      atomicAdd(&rec->fg, (unsigned long long)n);
-      atomicMin(&rec->bmin[0], lo0), atomicMin(&rec->bmin[1], lo1), atomicMin(&rec->bmin[2], lo2);
-      atomicMax(&rec->bmax[0], hi0), atomicMax(&rec->bmax[1], hi1), atomicMax(&rec->bmax[2], hi2);
-    }
+    CountBox<3> box;
+    box.clear();
+    box.n[0] = (unsigned)__builtin_popcountll(bits);
+    if (bits) box.grow({x, y, z0 + __builtin_ctzll(bits)}, {x, y, z0 + 63 - __builtin_clzll(bits)});
+    box.wave_reduce();
+    if (lane == 0) box.merge(&rec->fg, rec->bmin, rec->bmax);
   }
 }
 
@@ -251,18 +243,16 @@ __device__ __forceinline__ void cc_unite(int* parent, int va, int vb, int& last_
 
 template <bool MEMO>
 __global__ __launch_bounds__(256) void cc_merge_kernel(const CompRec* __restrict__ rec, int X, int Y, int Z, int conn, int* parent) {
-  const int z0 = blockIdx.x * CT_Z, y0 = blockIdx.y * CT_Y, x0 = blockIdx.z * CT_X;
-  if (cc_tile_outside_box(rec, x0, y0, z0)) return;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int z = z0 + lane;
+  const CompTile t;
+  if (t.outside_box(rec)) return;
+  const int lane = t.lane, z = t.z;
   int last_a = -1, last_b = -1;  // MEMO: the pair of this lane's previous union
-  for (int k = 0; k < CT_ROWS / 4; ++k) {
-    const int r = k * 4 + wave, lx = r >> 3, ly = r & 7, x = x0 + lx, y = y0 + ly;
-    if (x >= X || y >= Y) continue;  // (the same in every lane of the wave)
+  t.rows(X, Y, [&](int r, int x, int y) {
+    const int lx = r >> 3, ly = r & 7;
     const int64_t row = ((int64_t)x * Y + y) * Z;
     const bool mine = z < Z && parent[row + z] >= 0;  // (whether a voxel is foreground never changes)
     const unsigned long long me = __ballot(mine);
-    if (!me) continue;
+    if (!me) return;
     const int v = (int)(row + z);
     // the foreground of the five rows at z - 1, z, z + 1 first (no divergent work between the ballots): bits of the 64 voxels of this tile's z range, and the
     // two voxels just outside it, which lanes 0 and 63 read
@@ -279,7 +269,7 @@ __global__ __launch_bounds__(256) void cc_merge_kernel(const CompRec* __restrict
       qm[n] = lane == 0 ? (z >= 1 && parent[row2 + z - 1] >= 0) : cc_bit(nb[n], lane - 1);
       qp[n] = lane == 63 ? (z + 1 < Z && parent[row2 + z + 1] >= 0) : cc_bit(nb[n], lane + 1);
     }
-    if (!mine) continue;
+    if (!mine) return;
     const bool me_m = lane > 0 && cc_bit(me, lane - 1), me_p = lane < 63 && cc_bit(me, lane + 1);  // this run's voxels beside this one, in this tile
 #pragma unroll
     for (int n = 0; n < 5; ++n) {
@@ -295,33 +285,32 @@ __global__ __launch_bounds__(256) void cc_merge_kernel(const CompRec* __restrict
       if (s > 0 && s + 1 <= conn && qm[n] && (lane == 0 || (other_xy && !q0 && !me_m))) cc_unite<MEMO>(parent, v, (int)(row2 + z - 1), last_a, last_b);
       if ((s == 0 || s + 1 <= conn) && qp[n] && (lane == 63 || (other_xy && !q0 && !me_p))) cc_unite<MEMO>(parent, v, (int)(row2 + z + 1), last_a, last_b);
     }
-  }
+  });
 }
 
+// parent[v] = root(v).  A root zeroes its own size counter; HOLES: a background voxel on a face of the box marks its root instead (cnt[root] = 1; this route's
+// local pass zeroed every mark, and every marker stores the same value).
+template <bool HOLES>
 __global__ __launch_bounds__(256) void cc_flatten_kernel(const CompRec* __restrict__ rec, int X, int Y, int Z, int* parent, unsigned* __restrict__ cnt) {
-  const int z0 = blockIdx.x * CT_Z, y0 = blockIdx.y * CT_Y, x0 = blockIdx.z * CT_X;
-  if (cc_tile_outside_box(rec, x0, y0, z0)) return;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int z = z0 + lane;
-  if (z >= Z) return;
-  for (int k = 0; k < CT_ROWS / 4; ++k) {
-    const int r = k * 4 + wave, x = x0 + (r >> 3), y = y0 + (r & 7);
-    if (x >= X || y >= Y) continue;
+  const CompTile t;
+  if (t.outside_box(rec) || t.z >= Z) return;
+  const int z = t.z;
+  const int b0x = rec->bmin[0], b0y = rec->bmin[1], b0z = rec->bmin[2], b1x = rec->bmax[0], b1y = rec->bmax[1], b1z = rec->bmax[2];
+  t.rows(X, Y, [&](int, int x, int y) {
     const int v = (int)(((int64_t)x * Y + y) * Z + z);
-    if (parent[v] < 0) continue;
+    if (parent[v] < 0) return;                  // (HOLES: a voxel with a parent lies in the box)
     const int root = cc_find<true>(parent, v);  // (a link another thread has flattened meanwhile is as good as the old one)
     parent[v] = root;
-    if (root == v) cnt[v] = 0;
-  }
+    if (HOLES ? x == b0x || x == b1x || y == b0y || y == b1y || z == b0z || z == b1z : root == v) cnt[root] = HOLES;
+  });
 }
 
 __global__ __launch_bounds__(256) void cc_sizes_kernel(const CompRec* __restrict__ rec, int X, int Y, int Z, const int* __restrict__ parent, unsigned* cnt) {
   __shared__ int s_root;
   __shared__ unsigned s_cnt;
-  const int z0 = blockIdx.x * CT_Z, y0 = blockIdx.y * CT_Y, x0 = blockIdx.z * CT_X;
-  if (cc_tile_outside_box(rec, x0, y0, z0)) return;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int z = z0 + lane;
+  const CompTile t;
+  if (t.outside_box(rec)) return;
+  const int x0 = t.x0, y0 = t.y0, wave = t.wave, lane = t.lane, z = t.z;
   if (threadIdx.x == 0) s_root = INT_MAX, s_cnt = 0;
   __syncthreads();
   int p[CT_ROWS / 4], lo = INT_MAX;
@@ -331,7 +320,7 @@ __global__ __launch_bounds__(256) void cc_sizes_kernel(const CompRec* __restrict
     p[k] = (x < X && y < Y && z < Z) ? parent[((int64_t)x * Y + y) * Z + z] : -1;
     if (p[k] >= 0) lo = min(lo, p[k]);
   }
-  lo = cc_wave_min(lo);
+  lo = wave_min_i(lo);
   if (lane == 0 && lo != INT_MAX) atomicMin(&s_root, lo);
   __syncthreads();
   const int first = s_root;  // the smallest root seen in this tile: summed in LDS; INT_MAX: no foreground here
@@ -356,89 +345,77 @@ __global__ __launch_bounds__(256) void cc_sizes_kernel(const CompRec* __restrict
   if (threadIdx.x == 0 && s_cnt) atomicAdd(cnt + first, s_cnt);
 }
 
-__global__ __launch_bounds__(256) void cc_select_kernel(CompRec* __restrict__ rec, int X, int Y, int Z, const int* __restrict__ parent, const unsigned* __restrict__ cnt) {
-  const int z0 = blockIdx.x * CT_Z, y0 = blockIdx.y * CT_Y, x0 = blockIdx.z * CT_X;
-  if (cc_tile_outside_box(rec, x0, y0, z0)) return;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int z = z0 + lane;
-  unsigned long long key = 0;
-  unsigned roots = 0;
-  for (int k = 0; k < CT_ROWS / 4; ++k) {
-    const int r = k * 4 + wave, x = x0 + (r >> 3), y = y0 + (r & 7);
-    if (x >= X || y >= Y || z >= Z) continue;
+// One walk over the roots of the tiles in the box, one set of integer atomics per wave that met any (integer sums and maxima: the order does not matter):
+//   CC_LABELS, CC_LARGEST  every root is counted and offers its key to `best`
+//   CC_SMALL               every root is counted; those with cnt[root] >= min_voxels are counted in nkept, their voxels in `best`
+//   CC_HOLES               the roots without a mark are the holes (ncomp), the voxels below them |H| (best)
+template <CompRoute R>
+__global__ __launch_bounds__(256) void cc_tally_kernel(CompRec* __restrict__ rec, int X, int Y, int Z, const int* __restrict__ parent, const unsigned* __restrict__ cnt,
+                                                      unsigned long long min_voxels) {
+  constexpr bool PICK = R == CC_LABELS || R == CC_LARGEST;
+  const CompTile t;
+  if (t.outside_box(rec)) return;
+  const int z = t.z;
+  unsigned long long acc = 0;  // PICK: the largest key; otherwise the voxels kept / filled
+  unsigned roots = 0, kept = 0;
+  t.rows(X, Y, [&](int, int x, int y) {
+    if (z >= Z) return;
     const int v = (int)(((int64_t)x * Y + y) * Z + z);
-    if (parent[v] != v) continue;
-    const unsigned long long mykey = ((unsigned long long)cnt[v] << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)(v + 1));
-    key = mykey > key ? mykey : key;
-    ++roots;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long other = __shfl_xor(key, o, 64);
-    key = other > key ? other : key;
-    roots += __shfl_xor(roots, o, 64);
-  }
-  if (lane == 0 && roots) {
-    atomicMax(&rec->best, key);
-    atomicAdd(&rec->ncomp, roots);
-  }
+    const int p = parent[v];
+    if constexpr (R == CC_HOLES) {
+      if (p < 0 || cnt[p]) return;
+      ++acc;
+      roots += p == v;
+    } else {
+      if (p != v) return;
+      const unsigned c = cnt[v];
+      ++roots;
+      const unsigned long long key = ((unsigned long long)c << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)(v + 1));
+      if (PICK) acc = key > acc ? key : acc;
+      else if ((unsigned long long)c >= min_voxels) ++kept, acc += c;
+    }
+  });
+  acc = PICK ? wave_max_u64(acc) : wave_sum_u64(acc);
+  roots = wave_sum_u(roots);
+  if (R == CC_SMALL) kept = wave_sum_u(kept);
+  if (t.lane != 0) return;
+  if (roots) atomicAdd(&rec->ncomp, roots);
+  if (PICK && roots) atomicMax(&rec->best, acc);
+  if (!PICK && acc) atomicAdd(&rec->best, acc);
+  if (kept) atomicAdd(&rec->nkept, kept);
 }
 
-// LABELS: out = int32 labels [X][Y][Z]; otherwise out = fp32 one-hot [X][Y][Z][2] of the selected component.
-template <bool LABELS>
-__global__ __launch_bounds__(256) void cc_write_kernel(const CompRec* __restrict__ rec, int Y, int Z, int64_t nvox, const int* __restrict__ parent, void* __restrict__ out,
-                                                      long long* __restrict__ stats) {
+// The result over the whole volume; parents (and the counter of a voxel's root) are read inside the box only.  CC_LABELS: out = int32 labels [X][Y][Z]; the other
+// routes: out = fp32 one-hot [X][Y][Z][2], 1 on the selected component / on the components of P with at least min_voxels voxels / on P (in the box: no parent) and on
+// the background components without a mark.  Block 0 also writes the four statistics of the route.
+template <CompRoute R>
+__global__ __launch_bounds__(256) void cc_write_kernel(const CompRec* __restrict__ rec, int Y, int Z, int64_t nvox, const int* __restrict__ parent, const unsigned* __restrict__ cnt,
+                                                      unsigned long long min_voxels, void* __restrict__ out, long long* __restrict__ stats) {
+  constexpr bool PICK = R == CC_LABELS || R == CC_LARGEST;
   const unsigned long long best = rec->best;
-  const int keep = best ? (int)(0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull)) - 1 : -2;  // root of the selected component
+  const int keep = best ? (int)(0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull)) - 1 : -2;  // PICK: root of the selected component
   if (stats && blockIdx.x == 0 && threadIdx.x == 0) {
     stats[0] = (long long)rec->fg;
     stats[1] = (long long)rec->ncomp;
-    stats[2] = (long long)(best >> 32);
-    stats[3] = best ? (long long)keep + 1 : 0;
+    stats[2] = PICK ? (long long)(best >> 32) : (long long)best;
+    stats[3] = PICK ? (best ? (long long)keep + 1 : 0) : R == CC_HOLES ? (long long)(rec->fg + best) : (long long)rec->nkept;
   }
   const int b0x = rec->bmin[0], b0y = rec->bmin[1], b0z = rec->bmin[2], b1x = rec->bmax[0], b1y = rec->bmax[1], b1z = rec->bmax[2];
   for (unsigned v = blockIdx.x * 256u + threadIdx.x; v < (unsigned)nvox; v += gridDim.x * 256u) {  // (nvox < 2^31 and the stride < 2^24: no wrap)
     const unsigned xy = v / (unsigned)Z, x = xy / (unsigned)Y;
     const int z = (int)(v - xy * (unsigned)Z), y = (int)(xy - x * (unsigned)Y);
-    int p = -1;
-    if ((int)x >= b0x && (int)x <= b1x && y >= b0y && y <= b1y && z >= b0z && z <= b1z) p = parent[v];
-    if (LABELS) {
+    const bool in_box = (int)x >= b0x && (int)x <= b1x && y >= b0y && y <= b1y && z >= b0z && z <= b1z;
+    const int p = in_box ? parent[v] : -1;
+    if constexpr (R == CC_LABELS) {
       static_cast<int*>(out)[v] = p + 1;
     } else {
-      const float f = p == keep ? 1.f : 0.f;
+      bool on;
+      if (R == CC_LARGEST) on = p == keep;
+      else if (R == CC_SMALL) on = p >= 0 && (unsigned long long)cnt[p] >= min_voxels;
+      else on = in_box && (p < 0 || cnt[p] == 0);
+      const float f = on ? 1.f : 0.f;
       static_cast<float2*>(out)[v] = make_float2(1.f - f, f);
     }
-  }
-}
-
-// ---- remove small components: the passes up to `sizes` as above, then a count of the roots that pass the threshold and a write that tests cnt[root] ----
-
-__global__ __launch_bounds__(256) void rs_count_kernel(CompRec* __restrict__ rec, int X, int Y, int Z, const int* __restrict__ parent, const unsigned* __restrict__ cnt,
-                                                      unsigned long long min_voxels) {
-  const int z0 = blockIdx.x * CT_Z, y0 = blockIdx.y * CT_Y, x0 = blockIdx.z * CT_X;
-  if (cc_tile_outside_box(rec, x0, y0, z0)) return;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int z = z0 + lane;
-  unsigned long long kept_voxels = 0;
-  unsigned roots = 0, kept = 0;
-  for (int k = 0; k < CT_ROWS / 4; ++k) {
-    const int r = k * 4 + wave, x = x0 + (r >> 3), y = y0 + (r & 7);
-    if (x >= X || y >= Y || z >= Z) continue;
-    const int v = (int)(((int64_t)x * Y + y) * Z + z);
-    if (parent[v] != v) continue;
-    const unsigned c = cnt[v];
-    ++roots;
-    if ((unsigned long long)c >= min_voxels) ++kept, kept_voxels += c;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    kept_voxels += __shfl_xor(kept_voxels, o, 64);
-    roots += __shfl_xor(roots, o, 64);
-    kept += __shfl_xor(kept, o, 64);
-  }
-  if (lane == 0 && roots) {  // integer sums: the order does not matter
-    atomicAdd(&rec->ncomp, roots);
-    if (kept) atomicAdd(&rec->nkept, kept), atomicAdd(&rec->best, kept_voxels);
   }
 }
 
@@ -450,130 +427,32 @@ __global__ __launch_bounds__(256) void rs_count_kernel(CompRec* __restrict__ rec
 // the volume, or the voxel's straight neighbour beyond the face starts such a line, and a straight step is allowed at every connectivity.
 
 __global__ __launch_bounds__(256) void fh_scan_kernel(const float* __restrict__ logits, int Y, int Z, int64_t nvox, CompRec* __restrict__ rec) {
-  unsigned n = 0;
-  int lo0 = INT_MAX, lo1 = INT_MAX, lo2 = INT_MAX, hi0 = -1, hi1 = -1, hi2 = -1;
+  CountBox<3> box;
+  box.clear();
   for (unsigned v = blockIdx.x * 256u + threadIdx.x; v < (unsigned)nvox; v += gridDim.x * 256u) {  // (nvox < 2^31 and the stride < 2^24: no wrap)
-    const float2 lg = reinterpret_cast<const float2*>(logits)[v];
-    if (!(lg.y > lg.x)) continue;
+    if (!vsseg_pred_fg(reinterpret_cast<const float2*>(logits)[v])) continue;
     const unsigned xy = v / (unsigned)Z, x = xy / (unsigned)Y;
-    const int z = (int)(v - xy * (unsigned)Z), y = (int)(xy - x * (unsigned)Y);
-    ++n;
-    lo0 = min(lo0, (int)x), lo1 = min(lo1, y), lo2 = min(lo2, z);
-    hi0 = max(hi0, (int)x), hi1 = max(hi1, y), hi2 = max(hi2, z);
+    const int p[3] = {(int)x, (int)(xy - x * (unsigned)Y), (int)(v - xy * (unsigned)Z)};
+    ++box.n[0];
+    box.grow(p, p);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
-  if (!n) return;  // (the same in every lane of the wave)
-  lo0 = cc_wave_min(lo0), lo1 = cc_wave_min(lo1), lo2 = cc_wave_min(lo2);
-  hi0 = cc_wave_max(hi0), hi1 = cc_wave_max(hi1), hi2 = cc_wave_max(hi2);
-  if ((threadIdx.x & 63) == 0) {
-    atomicAdd(&rec->fg, (unsigned long long)n);
-    // the box only ever grows, so a bound that a (possibly stale) look already shows as reached needs no atomic: an all-foreground volume would otherwise queue
-    // six atomics per wave on six addresses
-    const int lo[3] = {lo0, lo1, lo2}, hi[3] = {hi0, hi1, hi2};
-    for (int a = 0; a < 3; ++a) {
-      if (lo[a] < __hip_atomic_load(&rec->bmin[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&rec->bmin[a], lo[a]);
-      if (hi[a] > __hip_atomic_load(&rec->bmax[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&rec->bmax[a], hi[a]);
-    }
-  }
+  box.wave_reduce();
+  if ((threadIdx.x & 63) == 0) box.merge<true>(&rec->fg, rec->bmin, rec->bmax);  // one merge per wave: with a look first
 }
 
-// parent[v] = root(v), and a background voxel on a face of the box marks its root (cnt[root] = 1; fh local zeroed every mark, and every marker stores the same value)
-__global__ __launch_bounds__(256) void fh_flatten_kernel(const CompRec* __restrict__ rec, int X, int Y, int Z, int* parent, unsigned* __restrict__ cnt) {
-  const int z0 = blockIdx.x * CT_Z, y0 = blockIdx.y * CT_Y, x0 = blockIdx.z * CT_X;
-  if (cc_tile_outside_box(rec, x0, y0, z0)) return;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int z = z0 + lane;
-  if (z >= Z) return;
-  const int b0x = rec->bmin[0], b0y = rec->bmin[1], b0z = rec->bmin[2], b1x = rec->bmax[0], b1y = rec->bmax[1], b1z = rec->bmax[2];
-  for (int k = 0; k < CT_ROWS / 4; ++k) {
-    const int r = k * 4 + wave, x = x0 + (r >> 3), y = y0 + (r & 7);
-    if (x >= X || y >= Y) continue;
-    const int v = (int)(((int64_t)x * Y + y) * Z + z);
-    if (parent[v] < 0) continue;  // (a voxel with a parent lies in the box)
-    const int root = cc_find<true>(parent, v);
-    parent[v] = root;
-    if (x == b0x || x == b1x || y == b0y || y == b1y || z == b0z || z == b1z) cnt[root] = 1;
-  }
-}
-
-// holes = roots without a mark, |H| = their voxels
-__global__ __launch_bounds__(256) void fh_count_kernel(CompRec* __restrict__ rec, int X, int Y, int Z, const int* __restrict__ parent, const unsigned* __restrict__ cnt) {
-  const int z0 = blockIdx.x * CT_Z, y0 = blockIdx.y * CT_Y, x0 = blockIdx.z * CT_X;
-  if (cc_tile_outside_box(rec, x0, y0, z0)) return;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int z = z0 + lane;
-  unsigned holes = 0, filled = 0;
-  for (int k = 0; k < CT_ROWS / 4; ++k) {
-    const int r = k * 4 + wave, x = x0 + (r >> 3), y = y0 + (r & 7);
-    if (x >= X || y >= Y || z >= Z) continue;
-    const int v = (int)(((int64_t)x * Y + y) * Z + z);
-    const int p = parent[v];
-    if (p < 0 || cnt[p]) continue;
-    ++filled;
-    holes += p == v;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    holes += __shfl_xor(holes, o, 64);
-    filled += __shfl_xor(filled, o, 64);
-  }
-  if (lane == 0 && filled) {
-    atomicAdd(&rec->best, (unsigned long long)filled);
-    if (holes) atomicAdd(&rec->ncomp, holes);
-  }
-}
-
-// The one-hot fp32 result of the two routes over the whole volume; parents (and the counter of a voxel's root) are read inside the box only.
-// HOLES: 1 on P (in the box: no parent) and on the background components without a mark; otherwise 1 on the components of P with at least min_voxels voxels.
-template <bool HOLES>
-__global__ __launch_bounds__(256) void morph_write_kernel(const CompRec* __restrict__ rec, int Y, int Z, int64_t nvox, const int* __restrict__ parent, const unsigned* __restrict__ cnt,
-                                                         unsigned long long min_voxels, float2* __restrict__ out, long long* __restrict__ stats) {
-  if (stats && blockIdx.x == 0 && threadIdx.x == 0) {
-    stats[0] = (long long)rec->fg;
-    stats[1] = (long long)rec->ncomp;
-    stats[2] = (long long)rec->best;
-    stats[3] = HOLES ? (long long)(rec->fg + rec->best) : (long long)rec->nkept;
-  }
-  const int b0x = rec->bmin[0], b0y = rec->bmin[1], b0z = rec->bmin[2], b1x = rec->bmax[0], b1y = rec->bmax[1], b1z = rec->bmax[2];
-  for (unsigned v = blockIdx.x * 256u + threadIdx.x; v < (unsigned)nvox; v += gridDim.x * 256u) {  // (nvox < 2^31 and the stride < 2^24: no wrap)
-    const unsigned xy = v / (unsigned)Z, x = xy / (unsigned)Y;
-    const int z = (int)(v - xy * (unsigned)Z), y = (int)(xy - x * (unsigned)Y);
-    float f = 0.f;
-    if ((int)x >= b0x && (int)x <= b1x && y >= b0y && y <= b1y && z >= b0z && z <= b1z) {
-      const int p = parent[v];
-      if (HOLES) f = (p < 0 || cnt[p] == 0) ? 1.f : 0.f;
-      else f = (p >= 0 && (unsigned long long)cnt[p] >= min_voxels) ? 1.f : 0.f;
-    }
-    out[v] = make_float2(1.f - f, f);
-  }
-}
-
-bool cc_dims_ok(const int32_t* dims) {
-  if (!dims) return false;
-  for (int a = 0; a < 3; ++a)
-    if (dims[a] < 1 || dims[a] > CC_MAX_EXTENT) return false;
-  return true;
-}
-
-enum CompRoute { CC_LABELS, CC_LARGEST, CC_SMALL, CC_HOLES };
-
-int cc_run(const char* name, CompRoute route, const float* logits, int32_t pitch, const int32_t* dims, int32_t connectivity, int64_t min_voxels, void* scratch, int64_t scratch_bytes,
-           void* out, int64_t* stats, void* stream) {
-  const bool labels = route == CC_LABELS;
-  const int out_align = labels ? 4 : 8;
-  VSSEG_CHECK(logits && scratch && out && (stats || !labels), "%s: null pointer (logits, scratch, %s)", name, labels ? "labels, stats" : "out");
-  VSSEG_CHECK(pitch == 2, "%s: pitch must be 2 (channels-last two-class logits), got %d", name, pitch);
-  VSSEG_CHECK(cc_dims_ok(dims), "%s: dims must be 1 .. %d on every axis", name, CC_MAX_EXTENT);
+template <CompRoute R>
+int cc_run(const char* name, const float* logits, int32_t pitch, const int32_t* dims, int32_t connectivity, int64_t min_voxels, void* scratch, int64_t scratch_bytes, void* out,
+           int64_t* stats, void* stream) {
+  constexpr bool labels = R == CC_LABELS, holes = R == CC_HOLES;
+  VOLUME_CHECK_ARGS(name, logits && scratch && out && (stats || !labels), labels ? " (logits, scratch, labels, stats)" : " (logits, scratch, out)", pitch, dims, CC_MAX_EXTENT, true,
+                    "", (const float*)nullptr, aligned_to(logits, 8) && aligned_to(out, labels ? 4 : 8) && aligned_to(stats, 8) && aligned_to(scratch, 256),
+                    labels ? "logits / stats 8 B, labels 4 B, scratch 256 B" : "logits / stats 8 B, out 8 B, scratch 256 B", scratch_bytes,
+                    cc_layout((int64_t)dims[0] * dims[1] * dims[2]).total, "vsseg_components_scratch_bytes");
   const int64_t nvox = (int64_t)dims[0] * dims[1] * dims[2];
   VSSEG_CHECK(nvox < (int64_t)INT32_MAX, "%s: dims %d x %d x %d hold %lld voxels, the int32 labels allow fewer than 2^31 - 1", name, dims[0], dims[1], dims[2], (long long)nvox);
   VSSEG_CHECK(connectivity == 6 || connectivity == 18 || connectivity == 26, "%s: connectivity must be 6, 18 or 26, got %d", name, connectivity);
   VSSEG_CHECK(min_voxels >= 0, "%s: min_voxels must not be negative, got %lld", name, (long long)min_voxels);
-  VSSEG_CHECK((reinterpret_cast<uintptr_t>(logits) & 7) == 0 && (reinterpret_cast<uintptr_t>(out) & (uintptr_t)(out_align - 1)) == 0 && (reinterpret_cast<uintptr_t>(stats) & 7) == 0 &&
-                  (reinterpret_cast<uintptr_t>(scratch) & 255) == 0,
-              "%s: misaligned operand (logits / stats 8 B, %s, scratch 256 B)", name, labels ? "labels 4 B" : "out 8 B");
   const CompLayout l = cc_layout(nvox);
-  VSSEG_CHECK(scratch_bytes >= l.total, "%s: %lld bytes of scratch, %lld needed (vsseg_components_scratch_bytes)", name, (long long)scratch_bytes, (long long)l.total);
   const int X = dims[0], Y = dims[1], Z = dims[2];
   const int conn = connectivity == 6 ? 1 : connectivity == 18 ? 2 : 3;  // largest |dx| + |dy| + |dz| of a neighbour
   hipStream_t s = as_stream(stream);
@@ -581,33 +460,18 @@ int cc_run(const char* name, CompRoute route, const float* logits, int32_t pitch
   CompRec* rec = reinterpret_cast<CompRec*>(base);
   int* parent = reinterpret_cast<int*>(base + l.parent);
   unsigned* cnt = reinterpret_cast<unsigned*>(base + l.cnt);
-  long long* st = reinterpret_cast<long long*>(stats);
   const unsigned long long minv = (unsigned long long)min_voxels;
   const dim3 tiles((Z + CT_Z - 1) / CT_Z, (Y + CT_Y - 1) / CT_Y, (X + CT_X - 1) / CT_X);
   const int wg = grid_for(nvox, 256, 256 * 32);
   hipLaunchKernelGGL(cc_init_kernel, dim3(1), dim3(64), 0, s, rec);
-  if (route == CC_HOLES) {
-    hipLaunchKernelGGL(fh_scan_kernel, dim3(wg), dim3(256), 0, s, logits, Y, Z, nvox, rec);
-    hipLaunchKernelGGL(cc_local_kernel<true>, tiles, dim3(256), 0, s, logits, X, Y, Z, conn, parent, cnt, rec);
-    hipLaunchKernelGGL(cc_merge_kernel<true>, tiles, dim3(256), 0, s, (const CompRec*)rec, X, Y, Z, conn, parent);
-    hipLaunchKernelGGL(fh_flatten_kernel, tiles, dim3(256), 0, s, (const CompRec*)rec, X, Y, Z, parent, cnt);
-    hipLaunchKernelGGL(fh_count_kernel, tiles, dim3(256), 0, s, rec, X, Y, Z, (const int*)parent, (const unsigned*)cnt);
-    hipLaunchKernelGGL(morph_write_kernel<true>, dim3(wg), dim3(256), 0, s, (const CompRec*)rec, Y, Z, nvox, (const int*)parent, (const unsigned*)cnt, 0ull, static_cast<float2*>(out), st);
-    VSSEG_LAUNCH_CHECK(name);
-    return VSSEG_OK;
-  }
-  hipLaunchKernelGGL(cc_local_kernel<false>, tiles, dim3(256), 0, s, logits, X, Y, Z, conn, parent, cnt, rec);
-  hipLaunchKernelGGL(cc_merge_kernel<false>, tiles, dim3(256), 0, s, (const CompRec*)rec, X, Y, Z, conn, parent);
-  hipLaunchKernelGGL(cc_flatten_kernel, tiles, dim3(256), 0, s, (const CompRec*)rec, X, Y, Z, parent, cnt);
-  hipLaunchKernelGGL(cc_sizes_kernel, tiles, dim3(256), 0, s, (const CompRec*)rec, X, Y, Z, (const int*)parent, cnt);
-  if (route == CC_SMALL) {
-    hipLaunchKernelGGL(rs_count_kernel, tiles, dim3(256), 0, s, rec, X, Y, Z, (const int*)parent, (const unsigned*)cnt, minv);
-    hipLaunchKernelGGL(morph_write_kernel<false>, dim3(wg), dim3(256), 0, s, (const CompRec*)rec, Y, Z, nvox, (const int*)parent, (const unsigned*)cnt, minv, static_cast<float2*>(out), st);
-  } else {
-    hipLaunchKernelGGL(cc_select_kernel, tiles, dim3(256), 0, s, rec, X, Y, Z, (const int*)parent, (const unsigned*)cnt);
-    if (labels) hipLaunchKernelGGL(cc_write_kernel<true>, dim3(wg), dim3(256), 0, s, (const CompRec*)rec, Y, Z, nvox, (const int*)parent, out, st);
-    else hipLaunchKernelGGL(cc_write_kernel<false>, dim3(wg), dim3(256), 0, s, (const CompRec*)rec, Y, Z, nvox, (const int*)parent, out, st);
-  }
+  if (holes) hipLaunchKernelGGL(fh_scan_kernel, dim3(wg), dim3(256), 0, s, logits, Y, Z, nvox, rec);
+  hipLaunchKernelGGL(cc_local_kernel<holes>, tiles, dim3(256), 0, s, logits, X, Y, Z, conn, parent, cnt, rec);
+  hipLaunchKernelGGL(cc_merge_kernel<holes>, tiles, dim3(256), 0, s, (const CompRec*)rec, X, Y, Z, conn, parent);
+  hipLaunchKernelGGL(cc_flatten_kernel<holes>, tiles, dim3(256), 0, s, (const CompRec*)rec, X, Y, Z, parent, cnt);
+  if (!holes) hipLaunchKernelGGL(cc_sizes_kernel, tiles, dim3(256), 0, s, (const CompRec*)rec, X, Y, Z, (const int*)parent, cnt);
+  hipLaunchKernelGGL(cc_tally_kernel<R>, tiles, dim3(256), 0, s, rec, X, Y, Z, (const int*)parent, (const unsigned*)cnt, minv);
+  hipLaunchKernelGGL(cc_write_kernel<R>, dim3(wg), dim3(256), 0, s, (const CompRec*)rec, Y, Z, nvox, (const int*)parent, (const unsigned*)cnt, minv, out,
+                     reinterpret_cast<long long*>(stats));
   VSSEG_LAUNCH_CHECK(name);
   return VSSEG_OK;
 }
@@ -615,7 +479,7 @@ int cc_run(const char* name, CompRoute route, const float* logits, int32_t pitch
 }  // namespace
 
 extern "C" int64_t vsseg_components_scratch_bytes(const int32_t dims[3]) {
-  VSSEG_CHECK(cc_dims_ok(dims), "vsseg_components_scratch_bytes: dims must be 1 .. %d on every axis", CC_MAX_EXTENT);
+  VSSEG_CHECK(dims_ok(dims, CC_MAX_EXTENT), "vsseg_components_scratch_bytes: dims must be 1 .. %d on every axis", CC_MAX_EXTENT);
   const int64_t nvox = (int64_t)dims[0] * dims[1] * dims[2];
   VSSEG_CHECK(nvox < (int64_t)INT32_MAX, "vsseg_components_scratch_bytes: dims %d x %d x %d hold %lld voxels, the int32 labels allow fewer than 2^31 - 1", dims[0], dims[1], dims[2],
               (long long)nvox);
@@ -624,20 +488,20 @@ extern "C" int64_t vsseg_components_scratch_bytes(const int32_t dims[3]) {
 
 extern "C" int vsseg_components_label(const float* logits, int32_t pitch, const int32_t dims[3], int32_t connectivity, void* scratch, int64_t scratch_bytes, int32_t* labels,
                                       int64_t* stats, void* stream) {
-  return cc_run("vsseg_components_label", CC_LABELS, logits, pitch, dims, connectivity, 0, scratch, scratch_bytes, labels, stats, stream);
+  return cc_run<CC_LABELS>("vsseg_components_label", logits, pitch, dims, connectivity, 0, scratch, scratch_bytes, labels, stats, stream);
 }
 
 extern "C" int vsseg_keep_largest_component(const float* logits, int32_t pitch, const int32_t dims[3], int32_t connectivity, void* scratch, int64_t scratch_bytes, float* out,
                                             int64_t* stats, void* stream) {
-  return cc_run("vsseg_keep_largest_component", CC_LARGEST, logits, pitch, dims, connectivity, 0, scratch, scratch_bytes, out, stats, stream);
+  return cc_run<CC_LARGEST>("vsseg_keep_largest_component", logits, pitch, dims, connectivity, 0, scratch, scratch_bytes, out, stats, stream);
 }
 
 extern "C" int vsseg_fill_holes(const float* logits, int32_t pitch, const int32_t dims[3], int32_t connectivity, void* scratch, int64_t scratch_bytes, float* out, int64_t* stats,
                                 void* stream) {
-  return cc_run("vsseg_fill_holes", CC_HOLES, logits, pitch, dims, connectivity, 0, scratch, scratch_bytes, out, stats, stream);
+  return cc_run<CC_HOLES>("vsseg_fill_holes", logits, pitch, dims, connectivity, 0, scratch, scratch_bytes, out, stats, stream);
 }
 
 extern "C" int vsseg_remove_small_components(const float* logits, int32_t pitch, const int32_t dims[3], int32_t connectivity, int64_t min_voxels, void* scratch, int64_t scratch_bytes,
                                              float* out, int64_t* stats, void* stream) {
-  return cc_run("vsseg_remove_small_components", CC_SMALL, logits, pitch, dims, connectivity, min_voxels, scratch, scratch_bytes, out, stats, stream);
+  return cc_run<CC_SMALL>("vsseg_remove_small_components", logits, pitch, dims, connectivity, min_voxels, scratch, scratch_bytes, out, stats, stream);
 }

@@ -3,6 +3,7 @@
 // forward and once backward; the ~25 ATen temporaries of the reference never exist.
 #include "common.h"
 #include "topk.h"
+#include "volume.h"  // the mask rule
 
 #define SMOOTH 1e-5
 
@@ -808,8 +809,8 @@ __global__ void hard_dice_kernel(const float* __restrict__ logits, int pitch, co
   float pg = 0, p = 0, g = 0;
   for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v < nvox; v += (int64_t)gridDim.x * blockDim.x) {
     float2 l = *reinterpret_cast<const float2*>(logits + v * pitch);
-    float pr = l.y > l.x ? 1.f : 0.f;
-    float gg = ((int)(long long)label[v]) == 1 ? 1.f : 0.f;
+    float pr = vsseg_pred_fg(l) ? 1.f : 0.f;
+    float gg = vsseg_label_fg(label[v]) ? 1.f : 0.f;
     pg += pr * gg; p += pr; g += gg;
   }
   double vals[3] = {pg, p, g};
@@ -824,7 +825,7 @@ extern "C" int vsseg_hard_dice_counts(const float* logits, int32_t pitch, const 
 __global__ void argmax2_kernel(const float* __restrict__ logits, int pitch, int64_t nvox, uint8_t* __restrict__ dst) {
   for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v < nvox; v += (int64_t)gridDim.x * blockDim.x) {
     float2 l = *reinterpret_cast<const float2*>(logits + v * pitch);
-    dst[v] = l.y > l.x ? 1 : 0;
+    dst[v] = vsseg_pred_fg(l) ? 1 : 0;
   }
 }
 extern "C" int vsseg_argmax2(const float* logits, int32_t pitch, int64_t nvox, uint8_t* dst, void* stream) {

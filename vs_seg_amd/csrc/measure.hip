@@ -19,9 +19,8 @@
 //
 // d^2 = (sx dx)^2 + (sy dy)^2 + (sz dz)^2 is formed in fp32 from exact integer differences; its maximum is taken over the bit patterns (non-negative
 // floats order like their uint32 bits), with an unsigned atomicMax: nothing depends on the order in which workgroups finish.
-#include <limits.h>
 #include <math.h>
-#include "common.h"
+#include "volume.h"
 
 namespace {
 
@@ -40,25 +39,8 @@ struct MeasRec {                       // index 0: P, 1: G
   unsigned best[2][2];                 // fp32 bits of the largest d^2: all pairs, pairs with equal z
 };
 
-inline int64_t meas_align(int64_t v) { return (v + 255) & ~(int64_t)255; }
-inline int64_t meas_tables_offset() { return meas_align(sizeof(MeasRec)); }
-inline int64_t meas_total(int64_t ncol) { return meas_tables_offset() + meas_align(4 * ncol * (int64_t)sizeof(int)); }  // tables [mask][min, max][Y * Z]
-
-__device__ __forceinline__ unsigned meas_wave_sum(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ int meas_wave_min(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int meas_wave_max(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
+inline int64_t meas_tables_offset() { return align256(sizeof(MeasRec)); }
+inline int64_t meas_total(int64_t ncol) { return meas_tables_offset() + align256(4 * ncol * (int64_t)sizeof(int)); }  // tables [mask][min, max][Y * Z]
 
 __global__ __launch_bounds__(256) void meas_init_kernel(MeasRec* __restrict__ rec, int* __restrict__ tab, int ncol) {
   const int c = blockIdx.x * 256 + threadIdx.x;
@@ -73,10 +55,7 @@ __global__ __launch_bounds__(256) void meas_init_kernel(MeasRec* __restrict__ re
     unsigned* w = reinterpret_cast<unsigned*>(rec);
     for (int i = threadIdx.x; i < (int)(sizeof(MeasRec) / 4); i += 256) w[i] = 0;
     __syncthreads();
-    if (threadIdx.x < 4) {
-      rec->bmin[threadIdx.x >> 1][threadIdx.x & 1] = INT_MAX;
-      rec->bmax[threadIdx.x >> 1][threadIdx.x & 1] = -1;
-    }
+    box_reset(&rec->bmin[0][0], &rec->bmax[0][0], 4);  // the two (y, z) boxes
   }
 }
 
@@ -84,7 +63,8 @@ template <bool HAS_LABEL>
 __global__ __launch_bounds__(256) void meas_stream_kernel(const float* __restrict__ logits, const float* __restrict__ label, int X, int Z, int ncol, int* __restrict__ tab,
                                                          MeasRec* __restrict__ rec) {
   constexpr int NM = HAS_LABEL ? 2 : 1;
-  __shared__ int red[4][2][8];
+  __shared__ CountBox<2> red[2][4];  // mask, wave
+  __shared__ unsigned sums[2][4][3];
   const int c = blockIdx.x * 256 + threadIdx.x;
   const int x0 = blockIdx.y * MS_XC;
   const int x1 = c < ncol ? min(x0 + MS_XC, X) : x0;  // a thread past the last column reads nothing
@@ -103,7 +83,7 @@ __global__ __launch_bounds__(256) void meas_stream_kernel(const float* __restric
     for (int u = 0; u < MS_U; ++u) {
       const int x = xb + u;
       if (x >= x1) continue;
-      const bool in[2] = {l[u].y > l[u].x, ((int)(long long)g[u]) == 1};  // the rules of hard_dice_kernel (loss.hip)
+      const bool in[2] = {vsseg_pred_fg(l[u]), vsseg_label_fg(g[u])};
 #pragma unroll
       for (int m = 0; m < NM; ++m)
         if (in[m]) ++n[m], sx[m] += (unsigned)x, lo[m] = min(lo[m], x), hi[m] = max(hi[m], x);
@@ -119,25 +99,24 @@ __global__ __launch_bounds__(256) void meas_stream_kernel(const float* __restric
       atomicMax(&tab[(2 * m + 1) * (int64_t)ncol + c], hi[m]);
     }
     // per wave: at most 64 * MS_XC voxels with indices below 8192: every sum is at most 2^24
-    const int v[8] = {(int)meas_wave_sum(n[m]),          (int)meas_wave_sum(sx[m]),          (int)meas_wave_sum(n[m] * (unsigned)y), (int)meas_wave_sum(n[m] * (unsigned)z),
-                      meas_wave_min(n[m] ? y : INT_MAX), meas_wave_min(n[m] ? z : INT_MAX), meas_wave_max(n[m] ? y : -1),           meas_wave_max(n[m] ? z : -1)};
-    if (lane == 0)
-      for (int i = 0; i < 8; ++i) red[wave][m][i] = v[i];
+    CountBox<2> box;
+    box.clear();
+    box.n[0] = n[m];
+    if (n[m]) box.grow({y, z}, {y, z});
+    box.wave_reduce();
+    const unsigned v[3] = {wave_sum_u(sx[m]), wave_sum_u(n[m] * (unsigned)y), wave_sum_u(n[m] * (unsigned)z)};
+    if (lane == 0) {
+      red[m][wave] = box;
+      for (int a = 0; a < 3; ++a) sums[m][wave][a] = v[a];
+    }
   }
   __syncthreads();
-  if (threadIdx.x < NM) {
+  if (threadIdx.x < NM) {  // integer atomics: the record does not depend on the order in which workgroups finish
     const int m = threadIdx.x;
-    unsigned long long s[4] = {0, 0, 0, 0};
-    int l2[2] = {INT_MAX, INT_MAX}, h2[2] = {-1, -1};
-    for (int w = 0; w < 4; ++w) {
-      for (int i = 0; i < 4; ++i) s[i] += (unsigned)red[w][m][i];
-      for (int a = 0; a < 2; ++a) l2[a] = min(l2[a], red[w][m][4 + a]), h2[a] = max(h2[a], red[w][m][6 + a]);
-    }
-    if (s[0]) {  // integer atomics: the record does not depend on the order in which workgroups finish
-      atomicAdd(&rec->cnt[m], s[0]);
-      for (int a = 0; a < 3; ++a)
-        if (s[1 + a]) atomicAdd(&rec->sum[m][a], s[1 + a]);
-      for (int a = 0; a < 2; ++a) atomicMin(&rec->bmin[m][a], l2[a]), atomicMax(&rec->bmax[m][a], h2[a]);
+    joined(red[m]).merge(&rec->cnt[m], rec->bmin[m], rec->bmax[m]);
+    for (int a = 0; a < 3; ++a) {
+      const unsigned long long s = ((unsigned long long)sums[m][0][a] + sums[m][1][a]) + ((unsigned long long)sums[m][2][a] + sums[m][3][a]);
+      if (s) atomicAdd(&rec->sum[m][a], s);
     }
   }
 }
@@ -200,7 +179,7 @@ __global__ __launch_bounds__(256) void meas_pair_kernel(MeasRec* __restrict__ re
       }
     }
   }
-  const unsigned u3 = (unsigned)meas_wave_max((int)__float_as_uint(best3)), u2 = (unsigned)meas_wave_max((int)__float_as_uint(best2));  // sign bit clear: int order = float order
+  const unsigned u3 = (unsigned)wave_max_i((int)__float_as_uint(best3)), u2 = (unsigned)wave_max_i((int)__float_as_uint(best2));  // sign bit clear: int order = float order
   if ((threadIdx.x & 63) == 0) {
     if (u3) atomicMax(&rec->best[m][0], u3);
     if (u2) atomicMax(&rec->best[m][1], u2);
@@ -230,34 +209,22 @@ __global__ void meas_finalize_kernel(const MeasRec* __restrict__ rec, float sx, 
   out[4] = sqrt(d2);  // NaN when either mask is empty or there is no label
 }
 
-bool meas_dims_ok(const int32_t* dims) {
-  if (!dims) return false;
-  for (int a = 0; a < 3; ++a)
-    if (dims[a] < 1 || dims[a] > MEAS_MAX_EXTENT) return false;
-  return (int64_t)dims[1] * dims[2] <= MEAS_MAX_COLUMNS;
-}
+bool meas_dims_ok(const int32_t* dims) { return dims_ok(dims, MEAS_MAX_EXTENT) && (int64_t)dims[1] * dims[2] <= MEAS_MAX_COLUMNS; }
 
 }  // namespace
 
-#define MEAS_DIMS_MSG "dims must be 1 .. %d on every axis with dims[1] * dims[2] <= %d"
-
 extern "C" int64_t vsseg_measure_scratch_bytes(const int32_t dims[3]) {
-  VSSEG_CHECK(meas_dims_ok(dims), "vsseg_measure_scratch_bytes: " MEAS_DIMS_MSG, MEAS_MAX_EXTENT, MEAS_MAX_COLUMNS);
+  VSSEG_CHECK(meas_dims_ok(dims), "vsseg_measure_scratch_bytes: dims must be 1 .. %d on every axis with dims[1] * dims[2] <= %d", MEAS_MAX_EXTENT, MEAS_MAX_COLUMNS);
   return meas_total((int64_t)dims[1] * dims[2]);
 }
 
 extern "C" int vsseg_measurements(const float* logits, int32_t pitch, const float* label, const int32_t dims[3], const float spacing[3], void* scratch, int64_t scratch_bytes,
                                   double* out, void* stream) {
-  VSSEG_CHECK(logits && scratch && out && spacing, "vsseg_measurements: null pointer (only label may be NULL)");
-  VSSEG_CHECK(pitch == 2, "vsseg_measurements: pitch must be 2 (channels-last two-class logits), got %d", pitch);
-  VSSEG_CHECK(meas_dims_ok(dims), "vsseg_measurements: " MEAS_DIMS_MSG, MEAS_MAX_EXTENT, MEAS_MAX_COLUMNS);
-  for (int a = 0; a < 3; ++a) VSSEG_CHECK(spacing[a] > 0.f && spacing[a] < __builtin_inff(), "vsseg_measurements: spacing[%d] = %g is not a positive finite value", a, (double)spacing[a]);
-  VSSEG_CHECK((reinterpret_cast<uintptr_t>(logits) & 7) == 0 && (reinterpret_cast<uintptr_t>(label) & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0 &&
-                  (reinterpret_cast<uintptr_t>(scratch) & 255) == 0,
-              "vsseg_measurements: misaligned operand (logits / out 8 B, label 4 B, scratch 256 B)");
+  static_assert(MEAS_MAX_COLUMNS == 262144, "the text of the dims message below");
+  VOLUME_CHECK_ARGS("vsseg_measurements", logits && scratch && out && spacing, " (only label may be NULL)", pitch, dims, MEAS_MAX_EXTENT, meas_dims_ok(dims),
+                    " with dims[1] * dims[2] <= 262144", spacing, aligned_to(logits, 8) && aligned_to(label, 4) && aligned_to(out, 8) && aligned_to(scratch, 256),
+                    "logits / out 8 B, label 4 B, scratch 256 B", scratch_bytes, meas_total((int64_t)dims[1] * dims[2]), "vsseg_measure_scratch_bytes");
   const int X = dims[0], Y = dims[1], Z = dims[2], ncol = Y * Z;
-  const int64_t total = meas_total(ncol);
-  VSSEG_CHECK(scratch_bytes >= total, "vsseg_measurements: %lld bytes of scratch, %lld needed (vsseg_measure_scratch_bytes)", (long long)scratch_bytes, (long long)total);
   hipStream_t s = as_stream(stream);
   MeasRec* rec = reinterpret_cast<MeasRec*>(scratch);
   int* tab = reinterpret_cast<int*>(static_cast<char*>(scratch) + meas_tables_offset());

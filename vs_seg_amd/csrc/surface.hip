@@ -18,9 +18,8 @@
 // which already holds every edge voxel's squared field value, also counts per direction and tolerance the edge voxels with field <= tau^2 (integer
 // atomics: LDS per workgroup, then one 64-bit add per non-zero counter), and its finalize also writes masd from the two per-direction sums and the
 // normalised surface Dice, surface precision and surface recall of every tolerance.  vsseg_surface_distances runs the kernels it always ran.
-#include <limits.h>
 #include <math.h>
-#include "common.h"
+#include "volume.h"
 
 namespace {
 
@@ -49,52 +48,32 @@ struct SurfTol {  // the tolerances of a call, by value in the kernel arguments
 struct SurfLayout {
   int64_t partial, edges, field, total;
 };
-inline int64_t surf_align(int64_t v) { return (v + 255) & ~(int64_t)255; }
 SurfLayout surf_layout(int64_t nvox) {
   SurfLayout l;
-  l.partial = surf_align(sizeof(SurfRec));
-  l.edges = l.partial + surf_align(SURF_RB * 2 * sizeof(double));
-  l.field = l.edges + surf_align(nvox);
-  l.total = l.field + surf_align(nvox * (int64_t)sizeof(float2));
+  l.partial = align256(sizeof(SurfRec));
+  l.edges = l.partial + align256(SURF_RB * 2 * sizeof(double));
+  l.field = l.edges + align256(nvox);
+  l.total = l.field + align256(nvox * (int64_t)sizeof(float2));
   return l;
 }
 
 __device__ __forceinline__ unsigned surf_mask(const float* __restrict__ logits, const float* __restrict__ label, int64_t v) {
   const float2 l = *reinterpret_cast<const float2*>(logits + 2 * v);
-  return (l.y > l.x ? 1u : 0u) | (((int)(long long)label[v]) == 1 ? 2u : 0u);  // the rules of hard_dice_kernel (loss.hip)
-}
-
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ unsigned wave_sum_u(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
+  return (vsseg_pred_fg(l) ? 1u : 0u) | (vsseg_label_fg(label[v]) ? 2u : 0u);
 }
 
 __global__ __launch_bounds__(256) void surf_init_kernel(SurfRec* rec) {
   unsigned* w = reinterpret_cast<unsigned*>(rec);
   for (int i = threadIdx.x; i < (int)(sizeof(SurfRec) / 4); i += 256) w[i] = 0;
   __syncthreads();
-  if (threadIdx.x < 3) {
-    rec->bmin[threadIdx.x] = INT_MAX;
-    rec->bmax[threadIdx.x] = -1;
-  }
+  box_reset(rec->bmin, rec->bmax, 3);
 }
 
 __global__ __launch_bounds__(256) void surf_edge_kernel(const float* __restrict__ logits, const float* __restrict__ label, int X, int Y, int Z, uint8_t* __restrict__ edges,
                                                        SurfRec* __restrict__ rec) {
   // ring of four staged planes (plane x in win[x & 3]): iteration x writes plane x + 1 over plane x - 3, whose last readers passed iteration x - 1's barrier
   __shared__ uint8_t win[4][EW_Y][EW_Z];
-  __shared__ int red[4][8];
+  __shared__ CountBox<3, 2> red[4];
   const int z0 = blockIdx.x * ET_Z, y0 = blockIdx.y * ET_Y, x0 = blockIdx.z * ET_X;
   const int x1 = min(x0 + ET_X, X);
   const int tz = threadIdx.x & 63, ty = threadIdx.x >> 6;  // rows ty, ty + 4, ty + 8, ty + 12 of column tz
@@ -110,8 +89,8 @@ __global__ __launch_bounds__(256) void surf_edge_kernel(const float* __restrict_
   };
   stage(x0 - 1);
   stage(x0);
-  unsigned n0 = 0, n1 = 0;
-  int lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {-1, -1, -1};
+  CountBox<3, 2> box;  // |E(P)|, |E(G)| and the box of both
+  box.clear();
   const int z = z0 + tz, c = tz + 1;
   for (int x = x0; x < x1; ++x) {
     stage(x + 1);
@@ -127,33 +106,16 @@ __global__ __launch_bounds__(256) void surf_edge_kernel(const float* __restrict_
       const unsigned e = wc[r][c] & ~inner & 3u;
       edges[((int64_t)x * Y + y) * Z + z] = (uint8_t)e;
       if (e) {
-        n0 += e & 1u;
-        n1 += e >> 1;
-        lo[0] = min(lo[0], x); hi[0] = max(hi[0], x);
-        lo[1] = min(lo[1], y); hi[1] = max(hi[1], y);
-        lo[2] = min(lo[2], z); hi[2] = max(hi[2], z);
+        box.n[0] += e & 1u;
+        box.n[1] += e >> 1;
+        box.grow({x, y, z}, {x, y, z});
       }
     }
   }
-  const unsigned w0 = wave_sum_u(n0), w1 = wave_sum_u(n1);
-  int v[8] = {(int)w0, (int)w1, wave_min_i(lo[0]), wave_min_i(lo[1]), wave_min_i(lo[2]), wave_max_i(hi[0]), wave_max_i(hi[1]), wave_max_i(hi[2])};
-  if ((threadIdx.x & 63) == 0)
-    for (int i = 0; i < 8; ++i) red[threadIdx.x >> 6][i] = v[i];
+  box.wave_reduce();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = box;
   __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long c0 = 0, c1 = 0;
-    int l[3] = {INT_MAX, INT_MAX, INT_MAX}, h[3] = {-1, -1, -1};
-    for (int wv = 0; wv < 4; ++wv) {
-      c0 += (unsigned)red[wv][0];
-      c1 += (unsigned)red[wv][1];
-      for (int a = 0; a < 3; ++a) l[a] = min(l[a], red[wv][2 + a]), h[a] = max(h[a], red[wv][5 + a]);
-    }
-    if (c0 + c1) {  // integer atomics: the record does not depend on the order in which workgroups finish
-      if (c0) atomicAdd(&rec->cnt[0], c0);
-      if (c1) atomicAdd(&rec->cnt[1], c1);
-      for (int a = 0; a < 3; ++a) atomicMin(&rec->bmin[a], l[a]), atomicMax(&rec->bmax[a], h[a]);
-    }
-  }
+  if (threadIdx.x == 0) joined(red).merge(rec->cnt, rec->bmin, rec->bmax);  // one set of atomics per workgroup that saw an edge voxel
 }
 
 // One per-axis pass of the squared distance transform inside the box, both fields at once (.x: to E(G), .y: to E(P)).  AX = 2 (along z) is the
@@ -378,13 +340,6 @@ __global__ __launch_bounds__(256) void surf_finalize_kernel(const SurfRec* __res
   }
 }
 
-bool surf_dims_ok(const int32_t* dims) {
-  if (!dims) return false;
-  for (int a = 0; a < 3; ++a)
-    if (dims[a] < 1 || dims[a] > SURF_MAX_EXTENT) return false;
-  return true;
-}
-
 int surf_pt_log2(int extent) {  // lines per distance-transform workgroup: at most 16, and [extent][lines] float2 within 64 KiB
   int l = 4;
   while (l > 0 && (int64_t)extent * (8 << l) > 65536) --l;
@@ -394,7 +349,7 @@ int surf_pt_log2(int extent) {  // lines per distance-transform workgroup: at mo
 }  // namespace
 
 extern "C" int64_t vsseg_surface_scratch_bytes(const int32_t dims[3]) {
-  VSSEG_CHECK(surf_dims_ok(dims), "vsseg_surface_scratch_bytes: dims must be 1 .. %d on every axis", SURF_MAX_EXTENT);
+  VSSEG_CHECK(dims_ok(dims, SURF_MAX_EXTENT), "vsseg_surface_scratch_bytes: dims must be 1 .. %d on every axis", SURF_MAX_EXTENT);
   return surf_layout((int64_t)dims[0] * dims[1] * dims[2]).total;
 }
 
@@ -403,17 +358,12 @@ namespace {
 // The launch sequence of both entry points.  tol == nullptr: vsseg_surface_distances (two outputs, no counting); otherwise vsseg_surface_metrics.
 int surf_launch(const char* who, const float* logits, int32_t pitch, const float* label, const int32_t dims[3], const float spacing[3], double percentile, const SurfTol* tol,
                 void* scratch, int64_t scratch_bytes, float* out, void* stream) {
-  VSSEG_CHECK(logits && label && scratch && out && spacing, "%s: null pointer", who);
-  VSSEG_CHECK(pitch == 2, "%s: pitch must be 2 (channels-last two-class logits), got %d", who, pitch);
-  VSSEG_CHECK(surf_dims_ok(dims), "%s: dims must be 1 .. %d on every axis", who, SURF_MAX_EXTENT);
-  for (int a = 0; a < 3; ++a) VSSEG_CHECK(spacing[a] > 0.f && spacing[a] < __builtin_inff(), "%s: spacing[%d] = %g is not a positive finite value", who, a, (double)spacing[a]);
+  VOLUME_CHECK_ARGS(who, logits && label && scratch && out && spacing, "", pitch, dims, SURF_MAX_EXTENT, true, "", spacing,
+                    aligned_to(logits, 8) && aligned_to(label, 4) && aligned_to(out, 4) && aligned_to(scratch, 256), "logits 8 B, label / out 4 B, scratch 256 B", scratch_bytes,
+                    surf_layout((int64_t)dims[0] * dims[1] * dims[2]).total, "vsseg_surface_scratch_bytes");
   VSSEG_CHECK(percentile >= 0.0 && percentile <= 100.0, "%s: percentile %g outside [0, 100]", who, percentile);
-  VSSEG_CHECK((reinterpret_cast<uintptr_t>(logits) & 7) == 0 && (reinterpret_cast<uintptr_t>(label) & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0 &&
-                  (reinterpret_cast<uintptr_t>(scratch) & 255) == 0,
-              "%s: misaligned operand (logits 8 B, label / out 4 B, scratch 256 B)", who);
   const int X = dims[0], Y = dims[1], Z = dims[2];
   const SurfLayout l = surf_layout((int64_t)X * Y * Z);
-  VSSEG_CHECK(scratch_bytes >= l.total, "%s: %lld bytes of scratch, %lld needed (vsseg_surface_scratch_bytes)", who, (long long)scratch_bytes, (long long)l.total);
   hipStream_t s = as_stream(stream);
   char* base = static_cast<char*>(scratch);
   SurfRec* rec = reinterpret_cast<SurfRec*>(base);

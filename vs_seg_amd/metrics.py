@@ -11,16 +11,13 @@ from __future__ import annotations
 
 import ctypes
 import math
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib as L
-from .inferers import _as_cl
-
-_SCRATCH_CACHE: Dict[tuple, torch.Tensor] = {}  # (device, dims, stream) -> scratch of vsseg_surface_distances
-_MEASURE_SCRATCH_CACHE: Dict[tuple, torch.Tensor] = {}  # ... of vsseg_measurements
+from . import _volume as V
 
 MEASUREMENT_FIELDS = ("voxels_pred", "voxels_label", "volume_pred_mm3", "volume_label_mm3", "centroid_distance_mm", "max_diameter_pred_mm", "max_diameter_label_mm",
                       "max_axial_diameter_pred_mm", "max_axial_diameter_label_mm")  # the nine outputs of vsseg_measurements, in order
@@ -34,30 +31,18 @@ def voxel_spacing(affine) -> Tuple[float, float, float]:
     return tuple(float(v) for v in np.linalg.norm(a[:3, :3], axis=0))
 
 
-def _scratch(device, dims, stream, cache=_SCRATCH_CACHE, what="surface_scratch_bytes") -> torch.Tensor:
-    key = (str(device), tuple(dims), stream)
-    buf = cache.get(key)
-    if buf is None:
-        nbytes = int(getattr(L.lib(), "vsseg_" + what)(L.i3(dims)))
-        if nbytes < 0:
-            L.check(nbytes, what)
-        while len(cache) >= 4:
-            cache.pop(next(iter(cache)))
-        buf = torch.empty(nbytes, dtype=torch.uint8, device=device)  # (the caching allocator's blocks are 512-byte aligned)
-        cache[key] = buf
-    return buf
-
-
-def _spacing3(spacing) -> Tuple[float, float, float]:
-    if spacing is None:
-        return (1.0, 1.0, 1.0)
-    try:
-        spacing = tuple(float(s) for s in spacing)
-    except (TypeError, ValueError):
-        raise ValueError(f"spacing must be three positive numbers (mm) or None, got {spacing!r}") from None
-    if len(spacing) != 3 or not all(math.isfinite(s) and s > 0 for s in spacing):
-        raise ValueError(f"spacing must be three positive finite numbers (mm) or None, got {spacing!r}")
-    return spacing
+def _surface(caller: str, name: str, predicted_probabilities, label, spacing, percentile, columns: int, extra: tuple = ()) -> torch.Tensor:
+    """The body of `compute_surface_distances` and `compute_surface_metrics`: vsseg_<name> once per volume, `extra` between percentile and scratch."""
+    percentile = V.percentile100(percentile)
+    sp = V.float3(V.spacing3(spacing))
+    B, dims = V.check_prediction("predicted_probabilities", predicted_probabilities)
+    lg, lab = V.on_device(caller, "predicted_probabilities", predicted_probabilities, label, B, dims)
+    stream = torch.cuda.current_stream(lg.device).cuda_stream
+    nv = dims[0] * dims[1] * dims[2]
+    scratch = V.scratch("surface_scratch_bytes", lg.device, dims, stream)
+    out = torch.empty((B, columns), dtype=torch.float32, device=lg.device)
+    V.each_volume(name, B, stream, (lg, 2 * nv), 2, (lab, nv), L.i3(dims), sp, percentile, *extra, scratch.data_ptr(), scratch.numel(), (out, columns))
+    return out
 
 
 def compute_surface_distances(predicted_probabilities: torch.Tensor, label: torch.Tensor, spacing: Optional[Sequence[float]] = None,
@@ -65,39 +50,7 @@ def compute_surface_distances(predicted_probabilities: torch.Tensor, label: torc
     """[B,2] fp32 on the device: column 0 the Hausdorff distance at `percentile` (None: the maximum), column 1 the average symmetric surface
     distance, in mm for voxel extents `spacing` (x, y, z; None: voxel units).  `predicted_probabilities` [B,2,X,Y,Z] logits or probabilities in
     any layout (as `compute_dice_score` takes them), `label` [B,1,X,Y,Z].  No host synchronisation."""
-    if percentile is None:
-        percentile = 100.0  # numpy.percentile at 100 is the maximum
-    try:
-        percentile = float(percentile)
-    except (TypeError, ValueError):
-        raise ValueError(f"percentile must be a number in [0, 100] or None, got {percentile!r}") from None
-    if not 0.0 <= percentile <= 100.0:
-        raise ValueError(f"percentile must be in [0, 100], got {percentile}")
-    spacing = _spacing3(spacing)
-    if predicted_probabilities.dim() != 5 or predicted_probabilities.shape[1] != 2:
-        raise ValueError(f"expected predicted_probabilities [B,2,X,Y,Z], got {tuple(predicted_probabilities.shape)}")
-    B, _, X, Y, Z = predicted_probabilities.shape
-    if tuple(label.shape) != (B, 1, X, Y, Z):
-        raise ValueError(f"expected label [B,1,X,Y,Z] = {(B, 1, X, Y, Z)}, got {tuple(label.shape)}")
-    if not (predicted_probabilities.is_cuda and label.is_cuda):
-        raise RuntimeError("vs_seg_amd.compute_surface_distances runs on an MI355X only; there is no CPU fallback")
-    if label.device != predicted_probabilities.device:
-        raise ValueError(f"predicted_probabilities on {predicted_probabilities.device}, label on {label.device}")
-    lib = L.lib()
-    stream = torch.cuda.current_stream(predicted_probabilities.device).cuda_stream
-    lg = _as_cl(predicted_probabilities)  # [B,X,Y,Z,2] fp32: a view of the sliding window's channels-last output, no copy
-    lab = label.detach()
-    if lab.dtype != torch.float32 or not lab.is_contiguous():
-        lab = lab.to(torch.float32).contiguous()
-    dims = (int(X), int(Y), int(Z))
-    nv = dims[0] * dims[1] * dims[2]
-    scratch = _scratch(lg.device, dims, stream)
-    sp = (ctypes.c_float * 3)(*spacing)
-    out = torch.empty((B, 2), dtype=torch.float32, device=lg.device)
-    for b in range(B):
-        L.check(lib.vsseg_surface_distances(lg.data_ptr() + 8 * b * nv, 2, lab.data_ptr() + 4 * b * nv, L.i3(dims), sp, percentile, scratch.data_ptr(), scratch.numel(),
-                                            out.data_ptr() + 8 * b, stream), "surface_distances")
-    return out
+    return _surface("compute_surface_distances", "surface_distances", predicted_probabilities, label, spacing, percentile, 2)
 
 
 MAX_TOLERANCES = 8  # of one vsseg_surface_metrics call
@@ -133,42 +86,9 @@ def compute_surface_metrics(predicted_probabilities: torch.Tensor, label: torch.
     within tau of the other boundary; MONAI's `compute_surface_dice`), the surface precision (that share of the prediction's boundary) and the surface recall (of
     the label's).  A distance equal to tau counts.  Both masks empty: NaN; one empty: hd, assd, masd +inf, nsd 0, the fraction over the empty boundary NaN and the
     other 0.  One edge pass and one distance transform serve every column (vsseg_surface_metrics, csrc/surface.hip).  No host synchronisation."""
-    if percentile is None:
-        percentile = 100.0
-    try:
-        percentile = float(percentile)
-    except (TypeError, ValueError):
-        raise ValueError(f"percentile must be a number in [0, 100] or None, got {percentile!r}") from None
-    if not 0.0 <= percentile <= 100.0:
-        raise ValueError(f"percentile must be in [0, 100], got {percentile}")
-    spacing = _spacing3(spacing)
     tol = check_tolerances(tolerances)
-    if predicted_probabilities.dim() != 5 or predicted_probabilities.shape[1] != 2:
-        raise ValueError(f"expected predicted_probabilities [B,2,X,Y,Z], got {tuple(predicted_probabilities.shape)}")
-    B, _, X, Y, Z = predicted_probabilities.shape
-    if tuple(label.shape) != (B, 1, X, Y, Z):
-        raise ValueError(f"expected label [B,1,X,Y,Z] = {(B, 1, X, Y, Z)}, got {tuple(label.shape)}")
-    if not (predicted_probabilities.is_cuda and label.is_cuda):
-        raise RuntimeError("vs_seg_amd.compute_surface_metrics runs on an MI355X only; there is no CPU fallback")
-    if label.device != predicted_probabilities.device:
-        raise ValueError(f"predicted_probabilities on {predicted_probabilities.device}, label on {label.device}")
-    lib = L.lib()
-    stream = torch.cuda.current_stream(predicted_probabilities.device).cuda_stream
-    lg = _as_cl(predicted_probabilities)  # [B,X,Y,Z,2] fp32
-    lab = label.detach()
-    if lab.dtype != torch.float32 or not lab.is_contiguous():
-        lab = lab.to(torch.float32).contiguous()
-    dims = (int(X), int(Y), int(Z))
-    nv = dims[0] * dims[1] * dims[2]
-    scratch = _scratch(lg.device, dims, stream)
-    sp = (ctypes.c_float * 3)(*spacing)
     tl = (ctypes.c_float * max(len(tol), 1))(*tol)
-    n = 3 + 3 * len(tol)
-    out = torch.empty((B, n), dtype=torch.float32, device=lg.device)
-    for b in range(B):
-        L.check(lib.vsseg_surface_metrics(lg.data_ptr() + 8 * b * nv, 2, lab.data_ptr() + 4 * b * nv, L.i3(dims), sp, percentile, tl, len(tol), scratch.data_ptr(), scratch.numel(),
-                                          out.data_ptr() + 4 * n * b, stream), "surface_metrics")
-    return out
+    return _surface("compute_surface_metrics", "surface_metrics", predicted_probabilities, label, spacing, percentile, 3 + 3 * len(tol), (tl, len(tol)))
 
 
 def compute_surface_dice(predicted_probabilities: torch.Tensor, label: torch.Tensor, spacing: Optional[Sequence[float]] = None, tolerances: Sequence[float] = (1.0,)) -> torch.Tensor:
@@ -182,31 +102,13 @@ def compute_measurements(predicted_probabilities: torch.Tensor, label: Optional[
     `spacing` (x, y, z in mm; None: voxel units).  `predicted_probabilities` [B,2,X,Y,Z] logits or probabilities in any layout, `label` [B,1,X,Y,Z] or
     None (the label columns and the centroid distance are then NaN).  Empty mask: its diameters and the centroid distance are NaN.  Y * Z <= 2^18.
     No host synchronisation (vsseg_measurements, csrc/measure.hip)."""
-    spacing = _spacing3(spacing)
-    if predicted_probabilities.dim() != 5 or predicted_probabilities.shape[1] != 2:
-        raise ValueError(f"expected predicted_probabilities [B,2,X,Y,Z], got {tuple(predicted_probabilities.shape)}")
-    B, _, X, Y, Z = predicted_probabilities.shape
-    if label is not None and tuple(label.shape) != (B, 1, X, Y, Z):
-        raise ValueError(f"expected label [B,1,X,Y,Z] = {(B, 1, X, Y, Z)}, got {tuple(label.shape)}")
-    if not (predicted_probabilities.is_cuda and (label is None or label.is_cuda)):
-        raise RuntimeError("vs_seg_amd.compute_measurements runs on an MI355X only; there is no CPU fallback")
-    if label is not None and label.device != predicted_probabilities.device:
-        raise ValueError(f"predicted_probabilities on {predicted_probabilities.device}, label on {label.device}")
-    lib = L.lib()
-    stream = torch.cuda.current_stream(predicted_probabilities.device).cuda_stream
-    lg = _as_cl(predicted_probabilities)  # [B,X,Y,Z,2] fp32
-    lab = None
-    if label is not None:
-        lab = label.detach()
-        if lab.dtype != torch.float32 or not lab.is_contiguous():
-            lab = lab.to(torch.float32).contiguous()
-    dims = (int(X), int(Y), int(Z))
+    sp = V.float3(V.spacing3(spacing))
+    B, dims = V.check_prediction("predicted_probabilities", predicted_probabilities)
+    lg, lab = V.on_device("compute_measurements", "predicted_probabilities", predicted_probabilities, label, B, dims)
+    stream = torch.cuda.current_stream(lg.device).cuda_stream
     nv = dims[0] * dims[1] * dims[2]
-    scratch = _scratch(lg.device, dims, stream, _MEASURE_SCRATCH_CACHE, "measure_scratch_bytes")
-    sp = (ctypes.c_float * 3)(*spacing)
+    scratch = V.scratch("measure_scratch_bytes", lg.device, dims, stream)
     n = len(MEASUREMENT_FIELDS)
     out = torch.empty((B, n), dtype=torch.float64, device=lg.device)
-    for b in range(B):
-        L.check(lib.vsseg_measurements(lg.data_ptr() + 8 * b * nv, 2, None if lab is None else lab.data_ptr() + 4 * b * nv, L.i3(dims), sp, scratch.data_ptr(), scratch.numel(),
-                                       out.data_ptr() + 8 * n * b, stream), "measurements")
+    V.each_volume("measurements", B, stream, (lg, 2 * nv), 2, (lab, nv), L.i3(dims), sp, scratch.data_ptr(), scratch.numel(), (out, n))
     return out

@@ -11,58 +11,41 @@ prediction is a one-hot fp32 [B,2,X,Y,Z] tensor, so that `compute_dice_score`, `
 from __future__ import annotations
 
 import math
-from typing import Dict, Tuple
+from typing import Tuple
 
 import numpy as np
 import torch
 
 from . import _lib as L
-from .inferers import _as_cl
-
-_SCRATCH_CACHE: Dict[tuple, torch.Tensor] = {}  # (device, dims, stream) -> scratch of the four entry points of components.hip
+from . import _volume as V
 
 
-def _scratch(device, dims, stream) -> torch.Tensor:
-    key = (str(device), tuple(dims), stream)
-    buf = _SCRATCH_CACHE.get(key)
-    if buf is None:
-        nbytes = int(L.lib().vsseg_components_scratch_bytes(L.i3(dims)))
-        if nbytes < 0:
-            L.check(nbytes, "components_scratch_bytes")
-        while len(_SCRATCH_CACHE) >= 4:
-            _SCRATCH_CACHE.pop(next(iter(_SCRATCH_CACHE)))
-        buf = torch.empty(nbytes, dtype=torch.uint8, device=device)  # (the caching allocator's blocks are 512-byte aligned)
-        _SCRATCH_CACHE[key] = buf
-    return buf
-
-
-def _checked(name: str, outputs: torch.Tensor, connectivity) -> Tuple[int, Tuple[int, int, int]]:
-    if not isinstance(outputs, torch.Tensor) or outputs.dim() != 5 or outputs.shape[1] != 2:
-        raise ValueError(f"expected outputs [B,2,X,Y,Z], got {tuple(outputs.shape) if isinstance(outputs, torch.Tensor) else type(outputs).__name__}")
+def _route(name: str, outputs: torch.Tensor, connectivity, return_stats: bool, extra: tuple = (), labels: bool = False, caller: str = ""):
+    """The body of the four calls: vsseg_<name> once per volume, `extra` between connectivity and scratch.  (result, stats or None): the one-hot fp32 [B,2,X,Y,Z]
+    prediction (a view of channels-last storage), or with `labels` the int32 [B,X,Y,Z] labels."""
+    B, dims = V.check_prediction("outputs", outputs)
     if isinstance(connectivity, bool) or not isinstance(connectivity, int) or connectivity not in (6, 18, 26):
         raise ValueError(f"connectivity must be 6, 18 or 26, got {connectivity!r}")
-    if not outputs.is_cuda:
-        raise RuntimeError(f"vs_seg_amd.{name} runs on an MI355X only; there is no CPU fallback")
-    B, _, X, Y, Z = outputs.shape
-    return int(B), (int(X), int(Y), int(Z))
+    lg, _ = V.on_device(caller or name, "outputs", outputs)
+    stream = torch.cuda.current_stream(lg.device).cuda_stream
+    nv = dims[0] * dims[1] * dims[2]
+    scratch = V.scratch("components_scratch_bytes", lg.device, dims, stream)
+    out = torch.empty((B, *dims) if labels else (B, *dims, 2), dtype=torch.int32 if labels else torch.float32, device=lg.device)
+    stats = torch.empty((B, 4), dtype=torch.int64, device=lg.device) if return_stats else None
+    V.each_volume(name, B, stream, (lg, 2 * nv), 2, L.i3(dims), connectivity, *extra, scratch.data_ptr(), scratch.numel(), (out, nv if labels else 2 * nv), (stats, 4))
+    return (out if labels else out.permute(0, 4, 1, 2, 3)), stats
 
 
 def connected_components(outputs: torch.Tensor, connectivity: int = 26) -> Tuple[torch.Tensor, torch.Tensor]:
     """(labels int32 [B,X,Y,Z], stats int64 [B,4]) on the device for `outputs` [B,2,X,Y,Z] logits or probabilities in any layout.  labels: 0 on the
     background, 1 + the smallest linear index of its component on a foreground voxel.  stats: foreground voxels, number of components, voxels of the
     largest component, its label (0 when there is no foreground).  No host synchronisation."""
-    B, dims = _checked("connected_components", outputs, connectivity)
-    lib = L.lib()
-    stream = torch.cuda.current_stream(outputs.device).cuda_stream
-    lg = _as_cl(outputs)  # [B,X,Y,Z,2] fp32: a view of the sliding window's channels-last output, no copy
-    nv = dims[0] * dims[1] * dims[2]
-    scratch = _scratch(lg.device, dims, stream)
-    labels = torch.empty((B, *dims), dtype=torch.int32, device=lg.device)
-    stats = torch.empty((B, 4), dtype=torch.int64, device=lg.device)
-    for b in range(B):
-        L.check(lib.vsseg_components_label(lg.data_ptr() + 8 * b * nv, 2, L.i3(dims), connectivity, scratch.data_ptr(), scratch.numel(), labels.data_ptr() + 4 * b * nv,
-                                           stats.data_ptr() + 32 * b, stream), "components_label")
-    return labels, stats
+    return _route("components_label", outputs, connectivity, True, labels=True, caller="connected_components")
+
+
+def _one_hot(name: str, outputs, connectivity, return_stats: bool, extra: tuple = ()):
+    result, stats = _route(name, outputs, connectivity, return_stats, extra)
+    return (result, stats) if return_stats else result
 
 
 def keep_largest_component(outputs: torch.Tensor, connectivity: int = 26, return_stats: bool = False):
@@ -70,19 +53,7 @@ def keep_largest_component(outputs: torch.Tensor, connectivity: int = 26, return
     [B,2,X,Y,Z] (a view of channels-last storage, as `sliding_window_inference` returns), channel 1 = 1.0 on the kept component and 0.0 elsewhere,
     channel 0 = 1 - channel 1.  `outputs` is not written.  With `return_stats` also the int64 [B,4] statistics of `connected_components`.  No host
     synchronisation."""
-    B, dims = _checked("keep_largest_component", outputs, connectivity)
-    lib = L.lib()
-    stream = torch.cuda.current_stream(outputs.device).cuda_stream
-    lg = _as_cl(outputs)
-    nv = dims[0] * dims[1] * dims[2]
-    scratch = _scratch(lg.device, dims, stream)
-    out = torch.empty((B, *dims, 2), dtype=torch.float32, device=lg.device)
-    stats = torch.empty((B, 4), dtype=torch.int64, device=lg.device) if return_stats else None
-    for b in range(B):
-        L.check(lib.vsseg_keep_largest_component(lg.data_ptr() + 8 * b * nv, 2, L.i3(dims), connectivity, scratch.data_ptr(), scratch.numel(), out.data_ptr() + 8 * b * nv,
-                                                 stats.data_ptr() + 32 * b if return_stats else None, stream), "keep_largest_component")
-    filtered = out.permute(0, 4, 1, 2, 3)
-    return (filtered, stats) if return_stats else filtered
+    return _one_hot("keep_largest_component", outputs, connectivity, return_stats)
 
 
 def min_component_voxels(min_mm3: float, spacing) -> int:
@@ -96,23 +67,6 @@ def min_component_voxels(min_mm3: float, spacing) -> int:
     return int(math.ceil(float(min_mm3) / (sx * sy * sz)))
 
 
-def _one_hot_route(name: str, outputs: torch.Tensor, connectivity, return_stats: bool, extra: tuple):
-    """The loop over the batch that `fill_holes` and `remove_small_components` share: one call of vsseg_<name> per volume, `extra` between connectivity and scratch."""
-    B, dims = _checked(name, outputs, connectivity)
-    fn = getattr(L.lib(), "vsseg_" + name)
-    stream = torch.cuda.current_stream(outputs.device).cuda_stream
-    lg = _as_cl(outputs)
-    nv = dims[0] * dims[1] * dims[2]
-    scratch = _scratch(lg.device, dims, stream)
-    out = torch.empty((B, *dims, 2), dtype=torch.float32, device=lg.device)
-    stats = torch.empty((B, 4), dtype=torch.int64, device=lg.device) if return_stats else None
-    for b in range(B):
-        L.check(fn(lg.data_ptr() + 8 * b * nv, 2, L.i3(dims), connectivity, *extra, scratch.data_ptr(), scratch.numel(), out.data_ptr() + 8 * b * nv,
-                   stats.data_ptr() + 32 * b if return_stats else None, stream), name)
-    result = out.permute(0, 4, 1, 2, 3)
-    return (result, stats) if return_stats else result
-
-
 def fill_holes(outputs: torch.Tensor, connectivity: int = 6, return_stats: bool = False):
     """The prediction `outputs` [B,2,X,Y,Z] (logits or probabilities, any layout) with the holes of its foreground P filled (MONAI's `FillHoles`,
     `scipy.ndimage.binary_fill_holes`): fp32 [B,2,X,Y,Z] (a view of channels-last storage), channel 1 = 1.0 on P and on every connected component of
@@ -120,7 +74,7 @@ def fill_holes(outputs: torch.Tensor, connectivity: int = 6, return_stats: bool 
     `connectivity` is that of the BACKGROUND: 6 (scipy's default, the dual of a 26-connected foreground), 18 or 26 (MONAI's default).  A tunnel through a
     ring is not a hole; a volume with an extent of 1 or 2 along an axis has none; an empty prediction stays empty.  `outputs` is not written.  With
     `return_stats` also int64 [B,4] on the device: |P|, the number of holes, the filled voxels |H|, |P| + |H|.  No host synchronisation."""
-    return _one_hot_route("fill_holes", outputs, connectivity, return_stats, ())
+    return _one_hot("fill_holes", outputs, connectivity, return_stats)
 
 
 def remove_small_components(outputs: torch.Tensor, min_voxels: int, connectivity: int = 26, return_stats: bool = False):
@@ -130,4 +84,4 @@ def remove_small_components(outputs: torch.Tensor, min_voxels: int, connectivity
     the number of components of P, the kept voxels, the kept components.  No host synchronisation: the threshold goes to the device as an argument."""
     if isinstance(min_voxels, bool) or not isinstance(min_voxels, int) or not 0 <= min_voxels < 2**63:
         raise ValueError(f"min_voxels must be an integer >= 0, got {min_voxels!r}")
-    return _one_hot_route("remove_small_components", outputs, connectivity, return_stats, (min_voxels,))
+    return _one_hot("remove_small_components", outputs, connectivity, return_stats, (min_voxels,))
