@@ -666,6 +666,45 @@ typedef struct {
   float contrast, gamma;  /* 1, 1: the job is left untouched */
 } vsseg_tone_job;
 int vsseg_patch_tone(const vsseg_tone_job* jobs_host, const void* jobs_dev, int32_t njobs, float* x, int64_t n, float* stats, double* work, void* stream);
+/* Acquisition artefacts on the image patches of a training batch (ABI version 21), applied AFTER the crop launch and BEFORE vsseg_patch_filter / vsseg_patch_tone (an artefact
+ * of the acquisition precedes post-hoc appearance changes): thick slices along z, phase-encode ghosting along x or y and a k-space spike, what TorchIO users know as
+ * RandomAnisotropy, RandomGhosting and RandomSpike.  Each has an exact image-domain form for the cases below, so no FFT is taken.  Motion and Gibbs ringing are out of scope.
+ * src, dst and scratch are [njobs][rx][ry][rz] fp32 with z contiguous, 16-byte aligned, src != dst; job j reads patch j of src (and of scratch) and writes patch j of dst,
+ * nothing else.  The order is fixed, y = S(G(T(v))), and the result of each stage is rounded to fp32 before the next stage reads it.
+ *   thick T      f = `thick` (1: off, v passes bit-exactly), o = `thick_offset`, 0 <= o < f.  Slab of z: k(z) = (z + o) / f (integer division); the first and the last slab of
+ *                a column may be short, and (rz - 1 + o) / f == 0 is one slab.  m_k = the fp32 sum of the slab's voxels in ascending z, divided by their count (correctly
+ *                rounded); c_k = (first + last z index of the slab) / 2, a multiple of 0.5 and exact in fp32.  For the output z with k = k(z): the pair (a, b) is (k, k+1)
+ *                if z >= c_k and (k-1, k) otherwise; a pair that leaves the range of slabs collapses to the end slab with phi = 0, otherwise
+ *                  phi = (z - c_a) / (c_b - c_a)   (fp32, correctly rounded division),        out = fmaf(phi, m_b - m_a, m_a)
+ *                slab means along z, interpolated linearly back between the slab centres: a thick-slice acquisition resampled to the grid of the patch.
+ *   ghosting G   axis a = `ghost_axis` (0 = x, 1 = y), N = roi_a, n = `ghosts` (0: off; otherwise n >= 2 divides N), s = N / n, alpha = `ghost_alpha` in (0, 1], u the input
+ *                of the stage.  In k-space along a every n-th line is scaled by 1 - alpha and the DC line is left alone (TorchIO's rule); in image space, which is the
+ *                contract, for the voxel at index i of a line along a:
+ *                  mu = (float)(sum of the N voxels of the line in fp64 / N),     S = sum_{j=0..n-1} u[(i + j s) mod N]   (fp32; the order is not part of the contract),
+ *                  c = alpha / n   (fp32, correctly rounded),                      out = fmaf(alpha, mu, fmaf(-c, S, u[i]))
+ *                n copies of the line, shifted by multiples of s, are subtracted with weight alpha / n and the mean is put back: the mean of every line is preserved and a
+ *                constant line comes out unchanged, both up to the rounding bound derived in tests/acquisition_oracle.py.
+ *   spike S      amp = `spike_amp` (0: off), (kx, ky) = `spike_k`, phase = `spike_phase`, w the input of the stage.  In k-space amp rx ry / 2 e^{+-i phase} is added at
+ *                (kx, ky) and at (-kx, -ky) of every z slice; in image space, at the voxel (x, y, z):
+ *                  t = ((kx x mod rx) ry + (ky y mod ry) rx) mod (rx ry)   (64-bit integers: the phase is reduced before any rounding, the argument stays below 2 pi + phase),
+ *                  theta = fmaf(6.2831853f, (float)t / (float)(rx ry), phase),     out = fmaf(amp, cosf(theta), w)     (accurate cosf, correctly rounded division)
+ *   neutral      a job with thick == 1, ghosts == 0 and spike_amp == 0 is a plain copy, bit for bit.
+ *   launches     at most two kernels: one forms T, one G and S (and the copy).  A job with thick slices AND ghosting or a spike passes T(v) through its patch of `scratch`,
+ *                which may be null when no job needs it (VSSEG_EINVAL otherwise).  No atomics: a launch is bit-reproducible run to run.
+ * Argument checks, on the host copy and before anything is launched (the entry point never reads device memory, synchronises or allocates): no null pointers, src != dst,
+ * 1 <= njobs <= 65535, 1 <= roi_a <= 65535, 16-byte alignment, 1 <= thick <= 8, 0 <= thick_offset < thick, ghost_axis in {0, 1}, ghosts 0 or (>= 2 and a divisor of roi_axis),
+ * with ghosts != 0 ghost_alpha finite and in (0, 1], spike_amp and spike_phase finite, with spike_amp != 0: 0 <= spike_k < roi in-plane and not (0, 0). */
+typedef struct {
+  int32_t thick;          /* slab height f in voxels along z, 1: off */
+  int32_t thick_offset;   /* o, 0 <= o < f */
+  int32_t ghost_axis;     /* 0 = x, 1 = y */
+  int32_t ghosts;         /* n >= 2 dividing roi[ghost_axis]; 0: off */
+  float   ghost_alpha;    /* in (0, 1] when ghosts != 0 */
+  float   spike_amp;      /* 0: off */
+  int32_t spike_k[2];     /* 0 <= kx < rx, 0 <= ky < ry, not both 0 when spike_amp != 0 */
+  float   spike_phase;    /* radians, in [0, 2 pi) */
+} vsseg_acquisition_job;
+int vsseg_patch_acquisition(const vsseg_acquisition_job* jobs_host, const void* jobs_dev, int32_t njobs, const float* src, float* dst, float* scratch, const int32_t roi[3], void* stream);
 /* NormalizeIntensityd (ref:params/VSparams.py:213): y = (x - mean) / std over all n voxels (population std; std == 0: no
  * division).  acc2 = 2 doubles of device scratch (sum, sum of squares; left filled for inspection). */
 int vsseg_normalize_intensity(const float* x, float* y, int64_t n, double* acc2, void* stream);

@@ -58,6 +58,11 @@ class ToneJob(C.Structure):  # vsseg_tone_job
     _fields_ = [("contrast", C.c_float), ("gamma", C.c_float)]  # 1, 1: the job is left untouched
 
 
+class AcquisitionJob(C.Structure):  # vsseg_acquisition_job
+    _fields_ = [("thick", C.c_int32), ("thick_offset", C.c_int32), ("ghost_axis", C.c_int32), ("ghosts", C.c_int32), ("ghost_alpha", C.c_float), ("spike_amp", C.c_float), ("spike_k", C.c_int32 * 2),
+                ("spike_phase", C.c_float)]  # thick 1, ghosts 0, spike_amp 0: the job is a copy
+
+
 GRAD_NORM_SHARD, GRAD_NORM_FINAL = 8192, 256  # VSSEG_GRAD_NORM_SHARD / _FINAL: elements per partial of vsseg_grad_norm, partials per pass of its finalising workgroup
 
 
@@ -239,7 +244,7 @@ class ChainDesc(C.Structure):  # vsseg_chain_desc
 
 # every exported entry point of include/vsseg_hip.h (the non-GPU tests check the .so exports each of them)
 SYMBOLS = [
-    "vsseg_last_error", "vsseg_version", "vsseg_fx_status", "vsseg_memset_zero", "vsseg_copy_bytes", "vsseg_store_u64", "vsseg_crop_flip", "vsseg_crop_affine", "vsseg_crop_field", "vsseg_patch_filter", "vsseg_patch_tone", "vsseg_normalize_intensity", "vsseg_igemm", "vsseg_igemm_lds_bytes", "vsseg_conv_chain", "vsseg_conv_chain_lds_bytes", "vsseg_conv_to1", "vsseg_wgrad", "vsseg_conv_bwd_fused", "vsseg_wgrad_narrow", "vsseg_wgrad_narrow_bn", "vsseg_gather_cast", "vsseg_merge_residual_grads", "vsseg_stage_input",
+    "vsseg_last_error", "vsseg_version", "vsseg_fx_status", "vsseg_memset_zero", "vsseg_copy_bytes", "vsseg_store_u64", "vsseg_crop_flip", "vsseg_crop_affine", "vsseg_crop_field", "vsseg_patch_filter", "vsseg_patch_tone", "vsseg_patch_acquisition", "vsseg_normalize_intensity", "vsseg_igemm", "vsseg_igemm_lds_bytes", "vsseg_conv_chain", "vsseg_conv_chain_lds_bytes", "vsseg_conv_to1", "vsseg_wgrad", "vsseg_conv_bwd_fused", "vsseg_wgrad_narrow", "vsseg_wgrad_narrow_bn", "vsseg_gather_cast", "vsseg_merge_residual_grads", "vsseg_stage_input",
     "vsseg_bn_finalize", "vsseg_bn_fold_eval", "vsseg_bn_act_fwd", "vsseg_bn_act_fwd_res1", "vsseg_bn_act_bwd_reduce", "vsseg_bn_act_bwd_finalize", "vsseg_bn_act_bwd_apply",
     "vsseg_dropout_mask", "vsseg_att_apply_fwd", "vsseg_att_apply_bwd", "vsseg_channel_sum", "vsseg_add_inplace", "vsseg_copy_cast",
     "vsseg_maxpool_label", "vsseg_dice_pred_sums", "vsseg_dice_att_sums", "vsseg_dice_finalize", "vsseg_dice_pred_bwd", "vsseg_dice_pred_bwd_to", "vsseg_dice_att_bwd", "vsseg_dice_level_sums", "vsseg_dice_tail_sums", "vsseg_dice_att_bwd_levels", "vsseg_ce_sums", "vsseg_dice_ce_finalize", "vsseg_dice_ce_pred_bwd", "vsseg_dice_ce_pred_bwd_to", "vsseg_fork_event_create", "vsseg_fork_event_destroy", "vsseg_fork_arm", "vsseg_fork_disarm", "vsseg_stream_wait_event",
@@ -278,6 +283,7 @@ def lib():
         L.vsseg_crop_field.argtypes = [C.POINTER(FieldJob), vp, i32, vp, I3, I3, u64, vp]
         L.vsseg_patch_filter.argtypes = [C.POINTER(FilterJob), vp, i32, vp, vp, vp, I3, vp]
         L.vsseg_patch_tone.argtypes = [C.POINTER(ToneJob), vp, i32, vp, i64, vp, vp, vp]
+        L.vsseg_patch_acquisition.argtypes = [C.POINTER(AcquisitionJob), vp, i32, vp, vp, vp, I3, vp]
         L.vsseg_normalize_intensity.argtypes = [vp, vp, i64, vp, vp]
         L.vsseg_igemm.argtypes = [C.POINTER(IgemmDesc), vp]
         L.vsseg_igemm_lds_bytes.argtypes = [C.POINTER(IgemmDesc)]

@@ -13,6 +13,8 @@ in-plane elastic deformation and a scalar for a multiplicative MR bias field; wi
 Four appearance families act on the image after the crop launch, each per sample with probability `appearance_prob`: an in-plane Gaussian blur and a simulated
 low-resolution acquisition (`vsseg_patch_filter`), then a contrast change and a gamma curve (`vsseg_patch_tone`; batchgenerators' ContrastAugmentation with
 preserve_range, MONAI's RandAdjustContrast).
+Three acquisition families act on the image between the crop launch and the appearance families, each per sample with probability `acquisition_prob`: thick slices along
+z, phase-encode ghosting along x or y and a k-space spike (`vsseg_patch_acquisition`; TorchIO's RandomAnisotropy, RandomGhosting, RandomSpike).
 
 The numpy restatement of MONAI 0.4.0's arithmetic that checks the HIP path (`vsseg_normalize_intensity`, `vsseg_crop_flip`) is test
 infrastructure and lives in `oracle/data_oracle.py` (parity unpinned — MONAI is not installed).  `PatchSampler`
@@ -102,6 +104,31 @@ def check_appearance_augment(blur_sigma=0.0, lowres=0.0, contrast=0.0, gamma=0.0
     return a
 
 
+ACQUISITION_KEYS = ("thick_slices", "ghost", "spike", "acquisition_prob")
+GHOST_COUNTS = (2, 3, 4, 6, 8)  # the ghost counts a sample may draw: those that divide the axis
+
+
+def check_acquisition_augment(thick_slices=0, ghost=0.0, spike=0.0, acquisition_prob=0.25) -> Dict[str, float]:
+    """The three acquisition ranges (0 = off) and the per-sample, per-family probability; ValueError for a non-finite value, thick_slices that is neither 0 nor an
+    integer in 2..4 (the largest slab height in voxels along z: 4 x 1.5 mm = 6 mm slices), ghost outside [0, 1] (the largest attenuation of the ghosted k-space
+    lines), spike < 0 (the largest amplitude, in standard deviations of the normalised image) and acquisition_prob outside [0, 1]."""
+    a = dict(thick_slices=float(thick_slices), ghost=float(ghost), spike=float(spike), acquisition_prob=float(acquisition_prob))
+    for k, v in a.items():
+        if not (np.isfinite(v) and v >= 0.0):
+            raise ValueError(f"augmentation range {k} = {v}: must be finite and >= 0")
+    if a["thick_slices"] != int(a["thick_slices"]) or int(a["thick_slices"]) not in (0, 2, 3, 4):
+        raise ValueError(f"thick_slices = {thick_slices}: 0 (off) or an integer slab height in 2..4 voxels")
+    a["thick_slices"] = int(a["thick_slices"])
+    if a["ghost"] > 1.0:
+        raise ValueError(f"ghost = {a['ghost']}: an attenuation, at most 1")
+    if a["acquisition_prob"] > 1.0:
+        raise ValueError(f"acquisition_prob = {a['acquisition_prob']}: a probability, at most 1")
+    return a
+
+
+NEUTRAL_ACQUISITION = dict(thick=1, thick_offset=0, ghost_axis=0, ghosts=0, ghost_alpha=np.float32(0.0), spike_amp=np.float32(0.0), spike_k=(0, 0), spike_phase=np.float32(0.0))
+
+
 def blur_taps(sigma: float) -> np.ndarray:
     """The R + 1 half-taps of `vsseg_filter_job.taps` for R = ceil(3 sigma): w_k = exp(-k^2 / (2 sigma^2)), normalised in fp64 so that w_0 + 2 sum_{k>=1} w_k = 1,
     rounded once to fp32.  sigma = 0: no taps (radius 0)."""
@@ -157,11 +184,22 @@ class RandomTail:
     With a non-zero appearance range (`blur_sigma`, `lowres`, `contrast`, `gamma`) a FIFTH state is seeded from `R` after those, so all the draws above are the same with
     the appearance families on or off.  `draw_appearance()` draws per sample, for each family whose range is non-zero, in the order blur, low resolution, contrast, gamma:
     first `random_sample() < appearance_prob`, then the value (sigma ~ U(S/2, S), f ~ U(F, 1), c ~ U(1 - C, 1 + C), gamma ~ U(1 - G, 1 + G)).  Both numbers are always
-    drawn, so the position in the stream does not depend on the outcome; a family that is not hit gets its neutral value (sigma = 0, f = 1, c = 1, gamma = 1)."""
+    drawn, so the position in the stream does not depend on the outcome; a family that is not hit gets its neutral value (sigma = 0, f = 1, c = 1, gamma = 1).
+
+    With a non-zero acquisition range (`thick_slices`, `ghost`, `spike`) a SIXTH state is seeded from `R` after those, so all the draws above are the same with the
+    acquisition families on or off.  `draw_acquisition(roi)` draws per sample, for each family whose range is non-zero, in the order thick slices, ghosting, spike, and
+    a family that is on always draws all its numbers:
+      thick   random_sample() < acquisition_prob, f = randint(2, F + 1), o = randint(0, 12) % f
+      ghost   random_sample() < acquisition_prob, alpha = uniform(0, A), axis = randint(0, 2), r = randint(0, 120); n = cands[r % len(cands)] with cands the members of
+              GHOST_COUNTS that divide roi[axis]; no candidate, or alpha == 0 in fp32: neutral
+      spike   random_sample() < acquisition_prob, amp = uniform(0, S), kx = randint(0, rx), ky = randint(0, ry), phase = uniform(0, 2 pi); (kx, ky) == (0, 0), or
+              amp == 0 in fp32: neutral
+    The result has the fields of `vsseg_acquisition_job`; NEUTRAL_ACQUISITION is the job that copies."""
 
     def __init__(self, roi: Sequence[int], flip_prob: Optional[float] = 0.5, seed: Optional[int] = None, rotate_deg: float = 0.0, scale: float = 0.0,
                  intensity_scale: float = 0.0, intensity_shift: float = 0.0, noise_std: float = 0.0, elastic_mag: float = 0.0, bias_field: float = 0.0, field_spacing: int = 64,
-                 blur_sigma: float = 0.0, lowres: float = 0.0, contrast: float = 0.0, gamma: float = 0.0, appearance_prob: float = 0.25):
+                 blur_sigma: float = 0.0, lowres: float = 0.0, contrast: float = 0.0, gamma: float = 0.0, appearance_prob: float = 0.25,
+                 thick_slices: int = 0, ghost: float = 0.0, spike: float = 0.0, acquisition_prob: float = 0.25):
         self.roi = tuple(int(r) for r in roi)
         self.flip_prob = flip_prob
         self.augment = check_augment(rotate_deg, scale, intensity_scale, intensity_shift, noise_std)
@@ -170,6 +208,8 @@ class RandomTail:
         self.fielding = self.field["elastic_mag"] != 0.0 or self.field["bias_field"] != 0.0
         self.appearance = check_appearance_augment(blur_sigma, lowres, contrast, gamma, appearance_prob)
         self.appearing = any(self.appearance[k] != 0.0 for k in APPEARANCE_KEYS[:4])
+        self.acquisition = check_acquisition_augment(thick_slices, ghost, spike, acquisition_prob)
+        self.acquiring = any(self.acquisition[k] != 0 for k in ACQUISITION_KEYS[:3])
         self.set_random_state(seed)
 
     def set_random_state(self, seed: Optional[int] = None):
@@ -179,6 +219,7 @@ class RandomTail:
         self._augR = np.random.RandomState(R.randint(MAX_SEED, dtype="uint32")) if self.augmenting else None
         self._fieldR = np.random.RandomState(R.randint(MAX_SEED, dtype="uint32")) if self.fielding else None
         self._appR = np.random.RandomState(R.randint(MAX_SEED, dtype="uint32")) if self.appearing else None
+        self._acqR = np.random.RandomState(R.randint(MAX_SEED, dtype="uint32")) if self.acquiring else None
         return self
 
     def draw(self, shape: Sequence[int]) -> Tuple[bool, Tuple[int, int, int]]:
@@ -214,6 +255,26 @@ class RandomTail:
 
         return (family(a["blur_sigma"], a["blur_sigma"] / 2.0, a["blur_sigma"], 0.0), family(a["lowres"], a["lowres"], 1.0, 1.0),
                 family(a["contrast"], 1.0 - a["contrast"], 1.0 + a["contrast"], 1.0), family(a["gamma"], 1.0 - a["gamma"], 1.0 + a["gamma"], 1.0))
+
+    def draw_acquisition(self, roi: Optional[Sequence[int]] = None) -> Dict:
+        """The fields of `vsseg_acquisition_job` for one sample of patch shape `roi` (default: the sampler's own)."""
+        roi = self.roi if roi is None else tuple(int(r) for r in roi)
+        a, p, R = self.acquisition, self.acquisition["acquisition_prob"], self._acqR
+        job = dict(NEUTRAL_ACQUISITION)
+        if a["thick_slices"]:
+            hit, f, o = R.random_sample() < p, int(R.randint(2, a["thick_slices"] + 1)), int(R.randint(0, 12))
+            if hit:
+                job.update(thick=f, thick_offset=o % f)
+        if a["ghost"] != 0.0:
+            hit, alpha, axis, r = R.random_sample() < p, np.float32(R.uniform(0.0, a["ghost"])), int(R.randint(0, 2)), int(R.randint(0, 120))
+            cands = [n for n in GHOST_COUNTS if roi[axis] % n == 0]
+            if hit and cands and alpha != 0.0:
+                job.update(ghost_axis=axis, ghosts=cands[r % len(cands)], ghost_alpha=alpha)
+        if a["spike"] != 0.0:
+            hit, amp, kx, ky, phase = R.random_sample() < p, np.float32(R.uniform(0.0, a["spike"])), int(R.randint(0, roi[0])), int(R.randint(0, roi[1])), np.float32(R.uniform(0.0, 2.0 * np.pi))
+            if hit and (kx, ky) != (0, 0) and amp != 0.0:
+                job.update(spike_amp=amp, spike_k=(kx, ky), spike_phase=phase)
+        return job
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -264,15 +325,25 @@ class PatchSampler:
     `last_augment[b]` then also holds `blur_sigma` (as drawn), `blur_taps` (fp32, R + 1 values), `coarse` (two ints), `contrast` and `gamma` (fp32), and `last_tone_stats` the
     [B, 4] device tensor {min, max, mean, 0} of the tone launch (None when it was skipped).  The scratch of the filter and the workspace of the tone launch belong to
     the sampler; the filtered image is a new tensor, because it is handed to the caller.  Nothing here reads device memory from the host or synchronises.  With the
-    four ranges 0, or `appearance_prob` 0, the sampler takes the paths above, launch for launch."""
+    four ranges 0, or `appearance_prob` 0, the sampler takes the paths above, launch for launch.
+
+    A non-zero `thick_slices`, `ghost` or `spike` with `acquisition_prob` > 0 adds, after whichever crop launch it is, BEFORE the appearance launches and on the image
+    only, one `vsseg_patch_acquisition` launch when a sample of the batch drew a family (`acquisition_launches` counts them).  `last_augment[b]` then also holds the fields
+    of the sample's `vsseg_acquisition_job`: `thick`, `thick_offset`, `ghost_axis`, `ghosts`, `ghost_alpha` (fp32), `spike_amp` (fp32), `spike_k`, `spike_phase` (fp32).
+    The scratch of the launch belongs to the sampler; nothing reads device memory or synchronises.  With the three ranges 0, or `acquisition_prob` 0, the sampler takes
+    the paths above, launch for launch."""
 
     def __init__(self, cases: List[Dict], roi: Sequence[int], flip_prob: Optional[float] = 0.5, seed: Optional[int] = 0, rotate_deg: float = 0.0, scale: float = 0.0,
                  intensity_scale: float = 0.0, intensity_shift: float = 0.0, noise_std: float = 0.0, elastic_mag: float = 0.0, bias_field: float = 0.0, field_spacing: int = 64,
-                 blur_sigma: float = 0.0, lowres: float = 0.0, contrast: float = 0.0, gamma: float = 0.0, appearance_prob: float = 0.25):
+                 blur_sigma: float = 0.0, lowres: float = 0.0, contrast: float = 0.0, gamma: float = 0.0, appearance_prob: float = 0.25,
+                 thick_slices: int = 0, ghost: float = 0.0, spike: float = 0.0, acquisition_prob: float = 0.25):
         self.cases, self.roi = cases, tuple(int(r) for r in roi)
         self.tail = RandomTail(self.roi, flip_prob, seed, rotate_deg, scale, intensity_scale, intensity_shift, noise_std, elastic_mag, bias_field, field_spacing,
-                               blur_sigma, lowres, contrast, gamma, appearance_prob)
+                               blur_sigma, lowres, contrast, gamma, appearance_prob, thick_slices, ghost, spike, acquisition_prob)
         self.appearing = self.tail.appearing and self.tail.appearance["appearance_prob"] > 0.0
+        self.acquiring = self.tail.acquiring and self.tail.acquisition["acquisition_prob"] > 0.0
+        self.acquisition_launches = 0
+        self._acquisition_scratch: Optional[torch.Tensor] = None  # [B, *roi] of the largest batch so far: a job with thick slices and a later stage passes T(v) through it
         self.last_tone_stats: Optional[torch.Tensor] = None
         self._filter_scratch: Optional[torch.Tensor] = None  # [B, *roi] of the largest batch so far: a job with blur and low resolution passes the blurred patch through it
         self._tone_work: Optional[torch.Tensor] = None  # [B, TONE_SHARDS, 3] fp64
@@ -285,7 +356,35 @@ class PatchSampler:
 
     def sample(self, indices: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:
         img, lab = self._sample_affine(indices) if self.tail.augmenting or self.tail.fielding else self._sample_crop(indices)
+        if self.acquiring:
+            img = self._acquisition(img)
         return (self._appearance(img), lab) if self.appearing else (img, lab)
+
+    def _acquisition(self, img: torch.Tensor) -> torch.Tensor:
+        """thick slices -> ghosting -> spike on the image patches [B, 1, *roi] of the crop launch; draws one sample after the other."""
+        B, dev, stream = img.shape[0], img.device, torch.cuda.current_stream()
+        if not self.last_augment:  # the plain crop keeps no per-sample record of its own
+            self.last_augment = [dict() for _ in range(B)]
+        jobs = (L.AcquisitionJob * B)()
+        any_on = staged = False
+        for b in range(B):
+            job = self.tail.draw_acquisition(self.roi)
+            self.last_augment[b].update(job)
+            j = jobs[b]
+            j.thick, j.thick_offset, j.ghost_axis, j.ghosts, j.ghost_alpha = job["thick"], job["thick_offset"], job["ghost_axis"], job["ghosts"], float(job["ghost_alpha"])
+            j.spike_amp, j.spike_k, j.spike_phase = float(job["spike_amp"]), (C.c_int32 * 2)(*job["spike_k"]), float(job["spike_phase"])
+            later = j.ghosts != 0 or j.spike_amp != 0.0
+            any_on, staged = any_on or later or j.thick != 1, staged or (later and j.thick != 1)
+        if not any_on:
+            return img
+        if staged and (self._acquisition_scratch is None or self._acquisition_scratch.shape[0] < B or self._acquisition_scratch.device != dev):
+            self._acquisition_scratch = torch.empty((B, *self.roi), dtype=torch.float32, device=dev)
+        jbuf = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(dev)
+        out = torch.empty_like(img)
+        L.check(self.lib.vsseg_patch_acquisition(jobs, jbuf.data_ptr(), B, img.data_ptr(), out.data_ptr(), self._acquisition_scratch.data_ptr() if staged else None, L.i3(self.roi), stream.cuda_stream), "patch_acquisition")
+        jbuf.record_stream(stream)
+        self.acquisition_launches += 1
+        return out
 
     def _appearance(self, img: torch.Tensor) -> torch.Tensor:
         """blur -> low resolution -> contrast -> gamma on the image patches [B, 1, *roi] of the crop launch; draws one sample after the other."""

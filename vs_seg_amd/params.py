@@ -33,7 +33,7 @@ from .metrics import MEASUREMENT_FIELDS, check_tolerances, compute_measurements,
 from .postprocess import connected_components, fill_holes, keep_largest_component, min_component_voxels, remove_small_components
 from . import parallel as DP
 from .data import nifti
-from .data.transforms import APPEARANCE_KEYS, AUGMENT_KEYS, FIELD_KEYS, PatchSampler, check_appearance_augment, check_augment, check_field_augment, epoch_batches, load_case
+from .data.transforms import ACQUISITION_KEYS, APPEARANCE_KEYS, AUGMENT_KEYS, FIELD_KEYS, PatchSampler, check_acquisition_augment, check_appearance_augment, check_augment, check_field_augment, epoch_batches, load_case
 
 HP = dict(
     channels=(16, 32, 48, 64, 80, 96),
@@ -61,14 +61,15 @@ class CachedLoader:
     the reference's first-epoch log line divides one by the other (ref:params/VSparams.py:466)."""
 
     def __init__(self, cases: List[Dict], roi: Optional[Sequence[int]], batch_size: int, shuffle: bool, flip_prob: Optional[float], seed: int = 0, pad: Optional[bool] = None,
-                 augment: Optional[Dict[str, float]] = None, field_augment: Optional[Dict[str, float]] = None, appearance_augment: Optional[Dict[str, float]] = None):
+                 augment: Optional[Dict[str, float]] = None, field_augment: Optional[Dict[str, float]] = None, appearance_augment: Optional[Dict[str, float]] = None,
+                 acquisition_augment: Optional[Dict[str, float]] = None):
         self.cases, self.batch_size, self.shuffle = cases, batch_size, shuffle
         # equal step counts on every rank (wrap-around padding) only where every step issues a collective: the shuffled training loader.
         # Validation / test loaders give rank r exactly shard_indices(n, r, world) — a padded case would be counted twice in their sums
         self.pad = shuffle if pad is None else pad
         self.rank, self.world = DP.get_rank(), DP.world_size()
         # every rank shuffles with the SAME stream (the shards must partition one permutation) but draws its own flips / crops
-        self.sampler = PatchSampler(cases, roi, flip_prob, seed + 7919 * self.rank, **(augment or {}), **(field_augment or {}), **(appearance_augment or {})) if roi is not None else None
+        self.sampler = PatchSampler(cases, roi, flip_prob, seed + 7919 * self.rank, **(augment or {}), **(field_augment or {}), **(appearance_augment or {}), **(acquisition_augment or {})) if roi is not None else None
         self._order = np.random.RandomState(seed)
 
     def __len__(self):
@@ -127,6 +128,10 @@ class VSparams:
         parser.add_argument("--aug_contrast", type=float, default=0.0, metavar="FRAC", help="training augmentation: scale the image of a training patch about its mean by a factor drawn from [1 - FRAC, 1 + FRAC], clipped to the range it had (0: off)")
         parser.add_argument("--aug_gamma", type=float, default=0.0, metavar="FRAC", help="training augmentation: apply a gamma curve over the value range of the image of a training patch, with an exponent drawn from [1 - FRAC, 1 + FRAC] (0: off)")
         parser.add_argument("--aug_appearance_prob", type=float, default=0.25, metavar="P", help="probability with which each of the blur, low-resolution, contrast and gamma augmentations is applied to a training sample, independently of the others")
+        parser.add_argument("--aug_thick_slices", type=float, default=0, metavar="F", help="training augmentation: simulate a thick-slice acquisition of the image of a training patch: average slabs of 2 to F voxels along z (drawn per sample, at a random offset) and interpolate linearly back between the slab centres; an integer in 2..4 (0: off)")
+        parser.add_argument("--aug_ghost", type=float, default=0.0, metavar="A", help="training augmentation: add phase-encode ghosts to the image of a training patch: 2 to 8 shifted copies along x or y, as left by attenuating every n-th k-space line by a factor drawn from [0, A]; in [0, 1] (0: off)")
+        parser.add_argument("--aug_spike", type=float, default=0.0, metavar="S", help="training augmentation: add a k-space spike to the image of a training patch: a plane wave in-plane at a random frequency and phase with an amplitude drawn from [0, S], in standard deviations of the normalised image (the herringbone artefact; 0: off)")
+        parser.add_argument("--aug_acquisition_prob", type=float, default=0.25, metavar="P", help="probability with which each of the thick-slice, ghosting and spike augmentations is applied to a training sample, independently of the others")
         parser.add_argument("--ce_weight", type=float, default=0.0, metavar="LAMBDA", help="training loss: add LAMBDA times the voxel-wise cross-entropy of the final logits to the Dice loss (the Dice + CE loss of nnU-Net, MONAI's DiceCELoss; 0: off, the reference's loss)")
         parser.add_argument("--ce_foreground_weight", type=float, default=1.0, metavar="W", help="class weight of the foreground voxels in the cross-entropy term, the background's being 1 (needs --ce_weight > 0)")
         parser.add_argument("--ce_topk", type=float, default=0.0, metavar="PCT", help="training loss: average the cross-entropy term over the hardest PCT percent of the voxels of the batch only, selected on the GPU, and divide by their number K, not by the class-weight sum (the Dice + TopK loss of nnU-Net, DC_and_topk_loss: --ce_weight 1 --ce_topk 10; in (0, 100], needs --ce_weight > 0; 0: off, the mean over every voxel)")
@@ -151,6 +156,7 @@ class VSparams:
             augment = check_augment(*(getattr(args, "aug_" + k) for k in AUGMENT_KEYS))
             field = check_field_augment(args.aug_elastic_mag, args.aug_bias_field, args.aug_field_spacing)
             appearance = check_appearance_augment(*(getattr(args, "aug_" + k) for k in APPEARANCE_KEYS))
+            acquisition = check_acquisition_augment(*(getattr(args, "aug_" + k) for k in ACQUISITION_KEYS))
             min_component_voxels(args.min_component_mm3, (1.0, 1.0, 1.0))  # a finite value >= 0
             surface_dice_mm = tuple(sorted(check_tolerances(args.surface_dice_mm or (), "--surface_dice_mm", distinct=True)))
         except ValueError as e:
@@ -185,6 +191,7 @@ class VSparams:
         self.aug_rotate_deg, self.aug_scale, self.aug_intensity_scale, self.aug_intensity_shift, self.aug_noise_std = (augment[k] for k in AUGMENT_KEYS)
         self.aug_elastic_mag, self.aug_bias_field, self.aug_field_spacing = (field[k] for k in FIELD_KEYS)
         self.aug_blur_sigma, self.aug_lowres, self.aug_contrast, self.aug_gamma, self.aug_appearance_prob = (appearance[k] for k in APPEARANCE_KEYS)
+        self.aug_thick_slices, self.aug_ghost, self.aug_spike, self.aug_acquisition_prob = (acquisition[k] for k in ACQUISITION_KEYS)
         self.ce_weight, self.ce_foreground_weight, self.ce_topk = ce_weight, ce_foreground_weight, ce_topk
         self.tversky_beta, self.focal_tversky_gamma, self.batch_dice = region if region is not None else (None, 1.0, False)  # (None: the reference's Dice ratio per sample)
         self.ce_focal_gamma = ce_focal_gamma
@@ -226,7 +233,7 @@ class VSparams:
                       ("keep_largest_component", "component_connectivity") if self.keep_largest_component else ("component_connectivity",) if self.min_component_mm3 > 0 else ()) + (("tta_flips", "tta_average") if self.tta_flips else ()) + (
                           tuple("aug_" + k for k in AUGMENT_KEYS) if any(self.augment.values()) else ()) + (
                               ("aug_elastic_mag", "aug_bias_field", "aug_field_spacing") if self.aug_elastic_mag or self.aug_bias_field else ()) + (
-                                  tuple("aug_" + k for k in APPEARANCE_KEYS) if self._appearance_on else ()) + (("ce_weight", "ce_foreground_weight") if self.ce_weight > 0 else ()) + (("ce_topk",) if self.ce_topk > 0 else ()) + (
+                                  tuple("aug_" + k for k in APPEARANCE_KEYS) if self._appearance_on else ()) + (tuple("aug_" + k for k in ACQUISITION_KEYS) if self._acquisition_on else ()) + (("ce_weight", "ce_foreground_weight") if self.ce_weight > 0 else ()) + (("ce_topk",) if self.ce_topk > 0 else ()) + (
                                       ("tversky_beta", "focal_tversky_gamma", "batch_dice") if self.tversky_beta is not None else ()) + (("ce_focal_gamma",) if self.ce_focal_gamma > 0 else ()) + (
                                       (("optimizer",) + (("momentum", "nesterov") if self.optimizer == "sgd" else ())) if self.optimizer != "adam" else ()) + (
                                           ("clip_grad_norm",) if self.clip_grad_norm > 0 else ()) + (("lr_schedule", "poly_power") if self.lr_schedule == "poly" else ()):
@@ -269,13 +276,22 @@ class VSparams:
     def _appearance_on(self) -> bool:
         return any(getattr(self, "aug_" + k) for k in APPEARANCE_KEYS[:4])
 
+    @property
+    def acquisition_augment(self) -> Dict[str, float]:
+        """The three acquisition ranges and their probability under PatchSampler's argument names (all three ranges 0: off)."""
+        return {k: getattr(self, "aug_" + k) for k in ACQUISITION_KEYS}
+
+    @property
+    def _acquisition_on(self) -> bool:
+        return any(getattr(self, "aug_" + k) for k in ACQUISITION_KEYS[:3])
+
     def get_transforms(self):
         """The three chains as plain descriptions; `cache_transformed_*_data` executes them (deterministic head cached in
         HBM, random tail per batch).  The augmentation flags reach the training chain only: the five ranges under "augment", the field ranges under "field_augment",
-        the appearance ranges under "appearance_augment"."""
+        the appearance ranges under "appearance_augment", the acquisition ranges under "acquisition_augment"."""
         head = ["LoadNifti", "AddChannel", "Orientation(RAS)", "NormalizeIntensity(image)"]
-        a, f, ap = self.augment, self.field_augment, self.appearance_augment
-        p = f"p={ap['appearance_prob']}"
+        a, f, ap, aq = self.augment, self.field_augment, self.appearance_augment, self.acquisition_augment
+        p, pq = f"p={ap['appearance_prob']}", f"p={aq['acquisition_prob']}"
         # in the order the launch applies them: the deformation acts in patch space, the matrix after it; the bias field multiplies the interpolated value before the gain
         aug = ([f"RandElastic(aug_elastic_mag={f['elastic_mag']}, aug_field_spacing={f['field_spacing']}, in-plane, cubic B-spline)"] if f["elastic_mag"] else []) + (
             [f"RandAffine(aug_rotate_deg={a['rotate_deg']}, aug_scale={a['scale']}, axis=z, about the crop centre)"] if a["rotate_deg"] or a["scale"] else []) + (
@@ -283,11 +299,14 @@ class VSparams:
             [f"RandScaleIntensity(aug_intensity_scale={a['intensity_scale']})"] if a["intensity_scale"] else []) + (
             [f"RandShiftIntensity(aug_intensity_shift={a['intensity_shift']})"] if a["intensity_shift"] else []) + (
             [f"RandGaussianNoise(aug_noise_std={a['noise_std']})"] if a["noise_std"] else []) + (
+            [f"RandThickSlices(aug_thick_slices={aq['thick_slices']}, along z, {pq})"] if aq["thick_slices"] else []) + (
+            [f"RandGhosting(aug_ghost={aq['ghost']}, in-plane, {pq})"] if aq["ghost"] else []) + (
+            [f"RandSpike(aug_spike={aq['spike']}, in-plane, {pq})"] if aq["spike"] else []) + (
             [f"RandGaussianBlur(aug_blur_sigma={ap['blur_sigma']}, in-plane, {p})"] if ap["blur_sigma"] else []) + (
             [f"RandLowResolution(aug_lowres={ap['lowres']}, in-plane, {p})"] if ap["lowres"] else []) + (
             [f"RandContrast(aug_contrast={ap['contrast']}, preserve_range, {p})"] if ap["contrast"] else []) + (
             [f"RandGamma(aug_gamma={ap['gamma']}, {p})"] if ap["gamma"] else [])
-        train = dict(chain=head + [f"SpatialPad({self.pad_crop_shape})", "RandFlip(p=0.5, axis=0)", f"RandSpatialCrop({self.pad_crop_shape})"] + aug, pad=self.pad_crop_shape, roi=self.pad_crop_shape, flip_prob=0.5, augment=a, field_augment=f, appearance_augment=ap)
+        train = dict(chain=head + [f"SpatialPad({self.pad_crop_shape})", "RandFlip(p=0.5, axis=0)", f"RandSpatialCrop({self.pad_crop_shape})"] + aug, pad=self.pad_crop_shape, roi=self.pad_crop_shape, flip_prob=0.5, augment=a, field_augment=f, appearance_augment=ap, acquisition_augment=aq)
         val = dict(chain=head + [f"SpatialPad({self.pad_crop_shape})", f"RandSpatialCrop({self.pad_crop_shape})"], pad=self.pad_crop_shape, roi=self.pad_crop_shape, flip_prob=None)
         test = dict(chain=head, pad=None, roi=None, flip_prob=None)
         return train, val, test
@@ -325,7 +344,7 @@ class VSparams:
     def _cache(self, files, tf, batch_size, shuffle, what):
         self.logger.info(f"Caching {what} data set...")
         cases = [load_case(fd, tf["pad"], self.device) for fd in files]
-        return CachedLoader(cases, tf["roi"], batch_size, shuffle, tf["flip_prob"], seed=0, augment=tf.get("augment"), field_augment=tf.get("field_augment"), appearance_augment=tf.get("appearance_augment"))  # the crop/flip stream is decorrelated per rank inside CachedLoader
+        return CachedLoader(cases, tf["roi"], batch_size, shuffle, tf["flip_prob"], seed=0, augment=tf.get("augment"), field_augment=tf.get("field_augment"), appearance_augment=tf.get("appearance_augment"), acquisition_augment=tf.get("acquisition_augment"))  # the crop/flip stream is decorrelated per rank inside CachedLoader
 
     def cache_transformed_train_data(self, train_files, train_transforms):
         return self._cache(train_files, train_transforms, self.train_batch_size, True, "training")
