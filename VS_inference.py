@@ -10,6 +10,9 @@ directed mean surface distances per test case, from the same GPU call, and write
 the Dice, the surface metrics and the NIfTI export; the raw Dice and the component counts go to the log and figures/test_postprocessing.csv.
 `--fill_holes [--hole_connectivity 6]` fills the holes of each predicted segmentation and `--min_component_mm3 V` drops its connected components below
 V cubic millimetres (both on the GPU, in this order, before --keep_largest_component); their counts are added to the same log and CSV.
+`--closing_mm R` / `--opening_mm R` close / open each predicted segmentation with a ball of R mm at the voxel spacing of the case (on the GPU, after
+--fill_holes and before --min_component_mm3, closing first): fragments a millimetre apart are bridged before the component filters see them, spurs
+thinner than the ball go before the measurements are taken; closed_voxels / opened_voxels are added to the same log and CSV.
 `--measurements` also reports per test case the volume (mm^3), the largest 3-D diameter and the largest diameter within an axial slice (mm) of the
 predicted and of the manual segmentation and the distance between their centres of mass, computed on the GPU (after --keep_largest_component and
 --tta_flips, when given), the volume and diameter errors over the cases, and writes figures/test_measurements.csv.

@@ -235,7 +235,7 @@ int vsseg_fork_event_destroy(void* ev);
 int vsseg_fork_arm(void* ev);
 int vsseg_fork_disarm(void);
 int vsseg_stream_wait_event(void* stream, void* ev);
-int vsseg_version(void); /* 20: + vsseg_loss_opts, vsseg_ce_focal_sums, vsseg_loss_finalize, vsseg_loss_pred_bwd, vsseg_loss_pred_bwd_to; 19: + vsseg_surface_metrics; 18: + vsseg_fill_holes, vsseg_remove_small_components; 17: + vsseg_measure_scratch_bytes, vsseg_measurements; 16: + vsseg_topk_scratch_bytes, vsseg_topk_select, vsseg_ce_topk_select, vsseg_dice_ce_topk_finalize, vsseg_dice_ce_topk_pred_bwd, vsseg_dice_ce_topk_pred_bwd_to; 15: + vsseg_grad_norm_scratch_bytes, vsseg_grad_norm, vsseg_sgd, vsseg_adam_clipped, vsseg_clip_record; 14: + vsseg_ce_sums, vsseg_dice_ce_finalize, vsseg_dice_ce_pred_bwd, vsseg_dice_ce_pred_bwd_to; 13: + vsseg_patch_filter, vsseg_patch_tone; 12: + vsseg_crop_field, vsseg_field_job; 11: + vsseg_crop_affine, vsseg_affine_job; 10: + vsseg_swi_finalize_mirrored, vsseg_crop_job.flip is a three-axis mirror mask (was flip_x); 9: + vsseg_components_scratch_bytes, vsseg_components_label, vsseg_keep_largest_component; 8: + vsseg_surface_distances, vsseg_surface_scratch_bytes; 7: + vsseg_dice_pred_bwd_to, vsseg_dice_level_sums, vsseg_dice_tail_sums, vsseg_dice_att_bwd_levels, vsseg_fork_*, vsseg_stream_wait_event; 6: + launch plans with depth -8 (transition kernel) and -9 (gathering marching kernel); 5: vsseg_wgrad march = 2 (compute weight-gradient kernel), + vsseg_conv_to1, vsseg_conv_chain_desc without h_out (the training variant measured no gain and was deleted); 4: + vsseg_conv_chain; 3: the BatchNorm-block-on-load fields (in_bn_*, keep_*, x_bn_*: round-4 experiment, measured a loss, deleted) left the descriptors, depth -7 plans;
+int vsseg_version(void); /* 22: + vsseg_ball_scratch_bytes, vsseg_ball_morphology; 20: + vsseg_loss_opts, vsseg_ce_focal_sums, vsseg_loss_finalize, vsseg_loss_pred_bwd, vsseg_loss_pred_bwd_to; 19: + vsseg_surface_metrics; 18: + vsseg_fill_holes, vsseg_remove_small_components; 17: + vsseg_measure_scratch_bytes, vsseg_measurements; 16: + vsseg_topk_scratch_bytes, vsseg_topk_select, vsseg_ce_topk_select, vsseg_dice_ce_topk_finalize, vsseg_dice_ce_topk_pred_bwd, vsseg_dice_ce_topk_pred_bwd_to; 15: + vsseg_grad_norm_scratch_bytes, vsseg_grad_norm, vsseg_sgd, vsseg_adam_clipped, vsseg_clip_record; 14: + vsseg_ce_sums, vsseg_dice_ce_finalize, vsseg_dice_ce_pred_bwd, vsseg_dice_ce_pred_bwd_to; 13: + vsseg_patch_filter, vsseg_patch_tone; 12: + vsseg_crop_field, vsseg_field_job; 11: + vsseg_crop_affine, vsseg_affine_job; 10: + vsseg_swi_finalize_mirrored, vsseg_crop_job.flip is a three-axis mirror mask (was flip_x); 9: + vsseg_components_scratch_bytes, vsseg_components_label, vsseg_keep_largest_component; 8: + vsseg_surface_distances, vsseg_surface_scratch_bytes; 7: + vsseg_dice_pred_bwd_to, vsseg_dice_level_sums, vsseg_dice_tail_sums, vsseg_dice_att_bwd_levels, vsseg_fork_*, vsseg_stream_wait_event; 6: + launch plans with depth -8 (transition kernel) and -9 (gathering marching kernel); 5: vsseg_wgrad march = 2 (compute weight-gradient kernel), + vsseg_conv_to1, vsseg_conv_chain_desc without h_out (the training variant measured no gain and was deleted); 4: + vsseg_conv_chain; 3: the BatchNorm-block-on-load fields (in_bn_*, keep_*, x_bn_*: round-4 experiment, measured a loss, deleted) left the descriptors, depth -7 plans;
                             * 2: fixed-point accumulators documented + vsseg_fx_status; 1: the buffers below were described as plain doubles */
 
 /* ---- Accumulator buffers are 64-bit FIXED-POINT integers, not doubles ------------------------------------------------------------------
@@ -792,6 +792,32 @@ int vsseg_fill_holes(const float* logits, int32_t pitch, const int32_t dims[3], 
                      int64_t* stats /* may be NULL */, void* stream);
 int vsseg_remove_small_components(const float* logits, int32_t pitch, const int32_t dims[3], int32_t connectivity, int64_t min_voxels, void* scratch, int64_t scratch_bytes,
                                   float* out, int64_t* stats /* may be NULL */, void* stream);
+
+/* Ball morphology of the same foreground at a radius in mm (ABI version 22; scipy.ndimage.binary_dilation / binary_erosion / binary_closing / binary_opening with a ball
+   that follows the voxel spacing).  One volume [X][Y][Z] per call: logits [X][Y][Z][2] fp32 (pitch 2, 8-byte aligned), never written; foreground P = logits[v][1] >
+   logits[v][0] (ties and NaN are background); spacing = mm per voxel along x, y, z (fp32); radius_mm = r >= 0.
+   The ball: an integer offset d has the squared length f(d) = fmaf(ax, ax, fmaf(ay, ay, az * az)) in fp32 with a_a = spacing[a] * (float)d_a (the accumulation order of the
+   distance transform of vsseg_surface_distances), and belongs to the ball when f(d) <= t2 = (float)((double)r * (double)r); a tie belongs, as in vsseg_surface_metrics.
+   Where the products are exact (unit spacing, dyadic spacings such as 0.5 / 1.5) so is the ball; elsewhere an offset whose fp64 squared length lies within a few 2^-24
+   (relative) of r^2 may fall on either side.  At r = 0 the ball is the single offset 0 and every operation returns the one-hot of P.
+   op 0, dilate(M): every voxel of the volume with a voxel of M at a ball offset; outside the volume there is no foreground (binary_dilation, border_value = 0).
+   op 1, erode(M): every voxel of M with no BACKGROUND VOXEL OF THE VOLUME at a ball offset; positions outside the volume are ignored, they are not background
+   (binary_erosion, border_value = 1), so a mask cut by the field of view does not shrink at the border, closing is extensive and opening anti-extensive there too.
+   op 2, close(M) = erode(dilate(M)); op 3, open(M) = dilate(erode(M)), both with the same ball.  An empty P gives an empty result, an all-foreground volume is unchanged.
+   out: fp32 [X][Y][Z][2] (8-byte aligned), channel 1 = 1.0 on the result and 0.0 elsewhere, channel 0 = 1 - channel 1: the one-hot format of vsseg_keep_largest_component.
+   stats: four int64 in device memory (8-byte aligned), may be NULL: [0] |P|, [1] |result|, [2] |result \ P| (added), [3] |P \ result| (removed): exact integer counts.
+   Launches: init; one pass that reads the logits and leaves |P| and the bounding box of P (8 B per voxel); per stage (one for dilate / erode, two for close / open) two
+   kernels confined to the work box W = that box grown by reach + 1 voxels per axis, reach_a = floor(r / spacing[a]): a banded exact separable squared-distance pass
+   along z and y, and one along x fused with the compare against t2 (ball.hip states why the band of reach + 1 is exact and why W suffices); one pass that writes the
+   result (8 B per voxel) and counts.  No host synchronisation, no allocation, no kernel waits for another workgroup, the grids depend on dims alone, and only integer
+   atomics combine workgroups: a call is bit-identical from run to run.  scratch: device memory of vsseg_ball_scratch_bytes(dims) bytes (a record and 6 B per voxel),
+   256-byte aligned, overwritten (a call on another stream needs its own).
+   Domain: dims 1 .. 8192 on every axis and X * Y * Z < 2^31 - 1; spacing positive and finite; r finite and >= 0; reach_a <= 32 voxels on every axis (13 mm at 0.41 mm).
+   Argument checks, before anything is launched: logits / spacing / scratch / out not null, alignment, pitch == 2, dims, spacing, scratch_bytes, op in 0 .. 3, radius,
+   reach; the message names the offending value. */
+int64_t vsseg_ball_scratch_bytes(const int32_t dims[3]); /* bytes of scratch, or VSSEG_EINVAL */
+int vsseg_ball_morphology(const float* logits, int32_t pitch, const int32_t dims[3], const float spacing[3], int32_t op /* 0 dilate, 1 erode, 2 close, 3 open */, double radius_mm,
+                          void* scratch, int64_t scratch_bytes, float* out, int64_t* stats /* may be NULL */, void* stream);
 
 /* Size and position of the argmax prediction P = (logits[v][1] > logits[v][0]) (the rule of vsseg_argmax2: ties and NaN are background) and of the label
    G = ((int)label[v] == 1) (the rule of vsseg_hard_dice_counts) (ABI version 17; beyond the reference, which reports the hard Dice only).  One volume [X][Y][Z] per call:

@@ -48,6 +48,7 @@ class FieldJob(C.Structure):  # vsseg_field_job: the fields of vsseg_affine_job,
 
 
 INTERP_TRILINEAR, INTERP_NEAREST = 0, 1
+OP_DILATE, OP_ERODE, OP_CLOSE, OP_OPEN = 0, 1, 2, 3  # `op` of vsseg_ball_morphology
 
 
 class FilterJob(C.Structure):  # vsseg_filter_job
@@ -251,6 +252,7 @@ SYMBOLS = [
     "vsseg_adam", "vsseg_swi_accumulate", "vsseg_swi_finalize", "vsseg_swi_finalize_mirrored", "vsseg_hard_dice_counts", "vsseg_argmax2",
     "vsseg_surface_scratch_bytes", "vsseg_surface_distances", "vsseg_surface_metrics",
     "vsseg_components_scratch_bytes", "vsseg_components_label", "vsseg_keep_largest_component", "vsseg_fill_holes", "vsseg_remove_small_components",
+    "vsseg_ball_scratch_bytes", "vsseg_ball_morphology",
     "vsseg_measure_scratch_bytes", "vsseg_measurements",
     "vsseg_grad_norm_scratch_bytes", "vsseg_grad_norm", "vsseg_sgd", "vsseg_adam_clipped",
     "vsseg_topk_scratch_bytes", "vsseg_topk_select", "vsseg_ce_topk_select", "vsseg_dice_ce_topk_finalize", "vsseg_dice_ce_topk_pred_bwd", "vsseg_dice_ce_topk_pred_bwd_to",
@@ -353,6 +355,8 @@ def lib():
         L.vsseg_keep_largest_component.argtypes = [vp, i32, I3, i32, vp, i64, vp, vp, vp]
         L.vsseg_fill_holes.argtypes = [vp, i32, I3, i32, vp, i64, vp, vp, vp]
         L.vsseg_remove_small_components.argtypes = [vp, i32, I3, i32, i64, vp, i64, vp, vp, vp]
+        L.vsseg_ball_scratch_bytes.argtypes, L.vsseg_ball_scratch_bytes.restype = [I3], i64
+        L.vsseg_ball_morphology.argtypes = [vp, i32, I3, C.POINTER(C.c_float), i32, f64, vp, i64, vp, vp, vp]
         L.vsseg_measure_scratch_bytes.argtypes, L.vsseg_measure_scratch_bytes.restype = [I3], i64
         L.vsseg_measurements.argtypes = [vp, i32, vp, I3, C.POINTER(C.c_float), vp, i64, vp, vp]
         L.vsseg_grad_norm_scratch_bytes.argtypes, L.vsseg_grad_norm_scratch_bytes.restype = [i64], i64

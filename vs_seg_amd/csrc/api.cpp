@@ -13,7 +13,7 @@ extern "C" void vsseg_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 extern "C" const char* vsseg_last_error(void) { return g_err; }
-extern "C" int vsseg_version(void) { return 21; }
+extern "C" int vsseg_version(void) { return 22; }
 
 // Forks without a marker packet (common.h, vsseg_launch_kernel): between vsseg_fork_arm(ev) and vsseg_fork_disarm() every kernel the library launches on the calling
 // thread carries `ev` as the stop event of its own dispatch; a later record replaces an earlier one, so after a launch record of several kernels the event stands for the

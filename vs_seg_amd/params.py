@@ -30,7 +30,7 @@ from . import SGD, Adam, AdamW, Dice_spvPA, UNet2d5_spvPA, check_ce, check_ce_to
 from .optim import DEFAULT_WEIGHT_DECAY, LR_SCHEDULES, OPTIMIZERS
 from .inferers import argmax_segmentation, tta_masks
 from .metrics import MEASUREMENT_FIELDS, check_tolerances, compute_measurements, compute_surface_distances, compute_surface_metrics, surface_metric_fields, voxel_spacing
-from .postprocess import connected_components, fill_holes, keep_largest_component, min_component_voxels, remove_small_components
+from .postprocess import binary_close, binary_open, check_radius_mm, connected_components, fill_holes, keep_largest_component, min_component_voxels, remove_small_components
 from . import parallel as DP
 from .data import nifti
 from .data.transforms import ACQUISITION_KEYS, APPEARANCE_KEYS, AUGMENT_KEYS, FIELD_KEYS, PatchSampler, check_acquisition_augment, check_appearance_augment, check_augment, check_field_augment, epoch_batches, load_case
@@ -43,9 +43,11 @@ HP = dict(
 )
 
 
-def postprocessing_csv_header(fill_holes: bool, min_component: bool) -> str:
-    """Columns of figures/test_postprocessing.csv: the six of --keep_largest_component, then those of --fill_holes and of --min_component_mm3 as switched on."""
-    return "case,dice_raw,dice,components,foreground_voxels,kept_voxels" + (",holes,filled_voxels" if fill_holes else "") + (",small_components,small_voxels" if min_component else "")
+def postprocessing_csv_header(fill_holes: bool, min_component: bool, closing: bool = False, opening: bool = False) -> str:
+    """Columns of figures/test_postprocessing.csv: the six of --keep_largest_component, then those of --fill_holes, --min_component_mm3, --closing_mm and --opening_mm as
+    switched on."""
+    return "case,dice_raw,dice,components,foreground_voxels,kept_voxels" + (",holes,filled_voxels" if fill_holes else "") + (",small_components,small_voxels" if min_component else "") + (
+        ",closed_voxels" if closing else "") + (",opened_voxels" if opening else "")
 
 
 def surface_dice_csv_header(tolerances) -> str:
@@ -105,6 +107,8 @@ class VSparams:
         parser.add_argument("--data_root", type=str, default="./data/VS_defaced/", help="data set root (the reference hard-codes this path)")
         parser.add_argument("--compute_dtype", type=str, default="bf16", choices=["bf16", "fp32"], help="bf16 MFMA (benchmark) or exact-fp32 MFMA (parity)")
         parser.add_argument("--num_epochs", type=int, default=None)
+        parser.add_argument("--closing_mm", type=float, default=0.0, metavar="R", help="run_inference closes each predicted segmentation with a ball of R mm (dilation, then erosion, with the voxel spacing of the case; on the GPU, after --fill_holes and before --opening_mm, --min_component_mm3 and --keep_largest_component, so that fragments less than about 2 R apart are bridged before the component filters see them) and adds closed_voxels to figures/test_postprocessing.csv (0: off; the ball may reach 32 voxels per axis)")
+        parser.add_argument("--opening_mm", type=float, default=0.0, metavar="R", help="run_inference opens each predicted segmentation with a ball of R mm (erosion, then dilation: spurs and islands thinner than the ball go; on the GPU, after --closing_mm and before --min_component_mm3 and --keep_largest_component) and adds opened_voxels to figures/test_postprocessing.csv (0: off)")
         parser.add_argument("--surface_metrics", action="store_true", help="run_inference also reports HD95 and ASSD per test case (mm, on the GPU) and writes figures/test_surface_metrics.csv")
         parser.add_argument("--surface_dice_mm", type=float, nargs="+", default=None, metavar="TAU", help="run_inference also reports per test case the normalised surface Dice (the share of the two boundaries within TAU mm of the other one), the surface precision and recall at each of 1 to 8 distinct tolerances and the mean of the two directed mean surface distances (on the GPU, from the one edge pass and distance transform that also serve --surface_metrics), and writes figures/test_surface_dice.csv")
         parser.add_argument("--keep_largest_component", action="store_true", help="run_inference keeps only the largest connected component of each predicted segmentation (on the GPU) before the Dice, the surface metrics and the NIfTI export, and writes figures/test_postprocessing.csv")
@@ -158,6 +162,8 @@ class VSparams:
             appearance = check_appearance_augment(*(getattr(args, "aug_" + k) for k in APPEARANCE_KEYS))
             acquisition = check_acquisition_augment(*(getattr(args, "aug_" + k) for k in ACQUISITION_KEYS))
             min_component_voxels(args.min_component_mm3, (1.0, 1.0, 1.0))  # a finite value >= 0
+            check_radius_mm(args.closing_mm, what="--closing_mm")  # (the reach depends on the spacing of the case: checked per case)
+            check_radius_mm(args.opening_mm, what="--opening_mm")
             surface_dice_mm = tuple(sorted(check_tolerances(args.surface_dice_mm or (), "--surface_dice_mm", distinct=True)))
         except ValueError as e:
             parser.error(str(e))
@@ -187,6 +193,7 @@ class VSparams:
         self.measurements = args.measurements
         self.keep_largest_component, self.component_connectivity = args.keep_largest_component, args.component_connectivity
         self.fill_holes, self.hole_connectivity, self.min_component_mm3 = args.fill_holes, args.hole_connectivity, float(args.min_component_mm3)
+        self.closing_mm, self.opening_mm = float(args.closing_mm), float(args.opening_mm)
         self.tta_flips, self.tta_average = tuple(args.tta_flips or ()), args.tta_average
         self.aug_rotate_deg, self.aug_scale, self.aug_intensity_scale, self.aug_intensity_shift, self.aug_noise_std = (augment[k] for k in AUGMENT_KEYS)
         self.aug_elastic_mag, self.aug_bias_field, self.aug_field_spacing = (field[k] for k in FIELD_KEYS)
@@ -229,7 +236,7 @@ class VSparams:
         for k in ("dataset", "data_root", "split_csv", "pad_crop_shape", "pad_crop_shape_test", "num_workers", "torch_device_arg", "train_batch_size", "initial_learning_rate",
                   "epochs_with_const_lr", "lr_divisor", "weight_decay", "num_epochs", "val_interval", "model", "sliding_window_inferer_roi_size", "attention", "hardness",
                   "results_folder_path", "export_inferred_segmentations", "compute_dtype") + (("surface_metrics",) if self.surface_metrics else ()) + (("surface_dice_mm",) if self.surface_dice_mm else ()) + (("measurements",) if self.measurements else ()) + (
-                      ("fill_holes", "hole_connectivity") if self.fill_holes else ()) + (("min_component_mm3",) if self.min_component_mm3 > 0 else ()) + (
+                      ("fill_holes", "hole_connectivity") if self.fill_holes else ()) + (("closing_mm",) if self.closing_mm > 0 else ()) + (("opening_mm",) if self.opening_mm > 0 else ()) + (("min_component_mm3",) if self.min_component_mm3 > 0 else ()) + (
                       ("keep_largest_component", "component_connectivity") if self.keep_largest_component else ("component_connectivity",) if self.min_component_mm3 > 0 else ()) + (("tta_flips", "tta_average") if self.tta_flips else ()) + (
                           tuple("aug_" + k for k in AUGMENT_KEYS) if any(self.augment.values()) else ()) + (
                               ("aug_elastic_mag", "aug_bias_field", "aug_field_spacing") if self.aug_elastic_mag or self.aug_bias_field else ()) + (
@@ -492,10 +499,11 @@ class VSparams:
         n = len(data_loader)
         dice_dev = torch.zeros(n, dtype=torch.float32, device=self.device)
         surf_dev = torch.zeros((2, n), dtype=torch.float32, device=self.device) if self.surface_metrics else None  # [hd95, assd] per case, mm
-        # --fill_holes / --min_component_mm3 / --keep_largest_component: [raw Dice, foreground voxels, components, kept voxels] per case, then [holes, filled voxels] and
-        # [small components, small voxels] for the first two (fp64: the voxel counts of a full volume are not exact in fp32)
-        small = self.min_component_mm3 > 0
-        post_rows = 4 + 2 * self.fill_holes + 2 * small if (self.fill_holes or small or self.keep_largest_component) else 0
+        # --fill_holes / --closing_mm / --opening_mm / --min_component_mm3 / --keep_largest_component: [raw Dice, foreground voxels, components, kept voxels] per case, then
+        # [holes, filled voxels], [small components, small voxels], [closed voxels] and [opened voxels] as switched on (fp64: the voxel counts of a full volume are not
+        # exact in fp32)
+        small, closing, opening = self.min_component_mm3 > 0, self.closing_mm > 0, self.opening_mm > 0
+        post_rows = 4 + 2 * self.fill_holes + 2 * small + closing + opening if (self.fill_holes or small or closing or opening or self.keep_largest_component) else 0
         post_dev = torch.zeros((post_rows, n), dtype=torch.float64, device=self.device) if post_rows else None
         meas_dev = torch.zeros((len(MEASUREMENT_FIELDS), n), dtype=torch.float64, device=self.device) if self.measurements else None  # --measurements: the nine values per case
         # --surface_dice_mm: [masd, then nsd, surface precision, surface recall per tolerance] per case
@@ -555,16 +563,25 @@ class VSparams:
         return dice_scores
 
     def _postprocess(self, outputs, spacing):
-        """The post-processing steps that are switched on, each on the output of the previous one: fill holes, remove small components, keep the largest.  Returns the
-        final one-hot prediction and the rows of the case for the all-reduce, all on the device: foreground voxels of the raw prediction, components of the prediction
-        that enters the first component filter (with --fill_holes alone: of the filled prediction), voxels of the final prediction, then [holes, filled voxels] and
-        [small components, small voxels] as switched on."""
+        """The post-processing steps that are switched on, each on the output of the previous one: fill holes, closing, opening, remove small components, keep the
+        largest (closing before the component filters, so that they see the bridged prediction).  Returns the final one-hot prediction and the rows of the case for the
+        all-reduce, all on the device: foreground voxels of the raw prediction, components of the prediction that enters the first component filter (without one: of the
+        final prediction), voxels of the final prediction, then [holes, filled voxels], [small components, small voxels], [closed voxels] and [opened voxels] as
+        switched on."""
         foreground = components = None
-        extra = []
+        extra, ball = [], []
         if self.fill_holes:
             outputs, st = fill_holes(outputs, self.hole_connectivity, return_stats=True)
             foreground, kept = st[0, 0], st[0, 3]
             extra += [st[0, 1], st[0, 2]]
+        if self.closing_mm > 0:
+            outputs, st = binary_close(outputs, self.closing_mm, spacing, return_stats=True)
+            foreground, kept = st[0, 0] if foreground is None else foreground, st[0, 1]
+            ball.append(st[0, 2])  # closing only adds
+        if self.opening_mm > 0:
+            outputs, st = binary_open(outputs, self.opening_mm, spacing, return_stats=True)
+            foreground, kept = st[0, 0] if foreground is None else foreground, st[0, 1]
+            ball.append(st[0, 3])  # opening only removes
         if self.min_component_mm3 > 0:
             outputs, st = remove_small_components(outputs, min_component_voxels(self.min_component_mm3, spacing), self.component_connectivity, return_stats=True)
             foreground, components, kept = st[0, 0] if foreground is None else foreground, st[0, 1], st[0, 2]
@@ -572,35 +589,43 @@ class VSparams:
         if self.keep_largest_component:
             outputs, st = keep_largest_component(outputs, self.component_connectivity, return_stats=True)
             foreground, components, kept = st[0, 0] if foreground is None else foreground, st[0, 1] if components is None else components, st[0, 2]
-        if components is None:  # --fill_holes alone
+        if components is None:  # no component filter: --fill_holes, --closing_mm, --opening_mm alone or together
             components = connected_components(outputs, self.component_connectivity)[1][0, 1]
-        return outputs, torch.stack([foreground, components, kept] + extra).double()
+        return outputs, torch.stack([foreground, components, kept] + extra + ball).double()
 
     def _log_postprocessing(self, dice, dice_raw, foreground, components, kept, *extra):
-        """Per-case lines of --fill_holes / --min_component_mm3 / --keep_largest_component beside the (post-processed) dice_score lines, and
-        figures/test_postprocessing.csv (rank 0).  extra: [holes, filled voxels] with --fill_holes, then [small components, small voxels] with --min_component_mm3."""
+        """Per-case lines of --fill_holes / --closing_mm / --opening_mm / --min_component_mm3 / --keep_largest_component beside the (post-processed) dice_score lines, and
+        figures/test_postprocessing.csv (rank 0).  extra: [holes, filled voxels] with --fill_holes, then [small components, small voxels] with --min_component_mm3, then
+        [closed voxels] with --closing_mm and [opened voxels] with --opening_mm."""
         log = self.logger.info
         extra = list(extra)
         holes, filled = (extra.pop(0), extra.pop(0)) if self.fill_holes else (None, None)
         small_components, small_voxels = (extra.pop(0), extra.pop(0)) if self.min_component_mm3 > 0 else (None, None)
+        closed = extra.pop(0) if self.closing_mm > 0 else None
+        opened = extra.pop(0) if self.opening_mm > 0 else None
         for i, (d, f, c, k) in enumerate(zip(dice_raw, foreground, components, kept)):
             log(f"dice_score_raw[{i}] = {d}")
             if holes is not None:
                 log(f"holes[{i}] = {int(holes[i])}")
                 log(f"filled_voxels[{i}] = {int(filled[i])}")
+            if closed is not None:
+                log(f"closed_voxels[{i}] = {int(closed[i])}")
+            if opened is not None:
+                log(f"opened_voxels[{i}] = {int(opened[i])}")
             log(f"components[{i}] = {int(c)}")
             if small_components is not None:
                 log(f"small_components_removed[{i}] = {int(small_components[i])}")
                 log(f"small_voxels_removed[{i}] = {int(small_voxels[i])}")
-            if self.keep_largest_component or small_components is not None:  # what the component filters took away
-                log(f"removed_voxels[{i}] = {int(f) + (int(filled[i]) if filled is not None else 0) - int(k)}")
+            if self.keep_largest_component or small_components is not None or opened is not None:  # everything taken away after the additions: by the opening and the component filters
+                log(f"removed_voxels[{i}] = {int(f) + (int(filled[i]) if filled is not None else 0) + (int(closed[i]) if closed is not None else 0) - int(k)}")
         log(f"mean_dice_score_raw = {dice_raw.mean()} +- {dice_raw.std()}")
         if self.rank == 0:
             os.makedirs(self.figures_path, exist_ok=True)
             with open(os.path.join(self.figures_path, "test_postprocessing.csv"), "w") as f:
-                f.write(postprocessing_csv_header(self.fill_holes, self.min_component_mm3 > 0) + "\n")
+                f.write(postprocessing_csv_header(self.fill_holes, self.min_component_mm3 > 0, closed is not None, opened is not None) + "\n")
                 for i, (r, d, c, fg, k) in enumerate(zip(dice_raw, dice, components, foreground, kept)):
-                    more = ([holes[i], filled[i]] if holes is not None else []) + ([small_components[i], small_voxels[i]] if small_components is not None else [])
+                    more = ([holes[i], filled[i]] if holes is not None else []) + ([small_components[i], small_voxels[i]] if small_components is not None else []) + (
+                        [closed[i]] if closed is not None else []) + ([opened[i]] if opened is not None else [])
                     f.write(f"{i},{float(r)!r},{float(d)!r},{int(c)},{int(fg)},{int(k)}" + "".join(f",{int(v)}" for v in more) + "\n")
 
     def _log_surface_metrics(self, dice, hd95, assd):

@@ -1,6 +1,7 @@
 """Post-processing of a two-class prediction on the device: 3-D connected components of its foreground, "keep the largest connected component"
 (MONAI's `KeepLargestConnectedComponent` after `AsDiscrete`), "fill holes" (`FillHoles`) and "remove small components" (`RemoveSmallObjects`), through
-`vsseg_components_label` / `vsseg_keep_largest_component` / `vsseg_fill_holes` / `vsseg_remove_small_components` (csrc/components.hip).
+`vsseg_components_label` / `vsseg_keep_largest_component` / `vsseg_fill_holes` / `vsseg_remove_small_components` (csrc/components.hip); and ball morphology at a
+radius in mm, `binary_dilate` / `binary_erode` / `binary_close` / `binary_open`, through `vsseg_ball_morphology` (csrc/ball.hip).
 
 Conventions: the foreground is the argmax over the two class channels as `compute_dice_score` and `argmax_segmentation` read it (ties and NaN are
 background); connectivity 6, 18 or 26 (26 = `skimage.measure.label` with full connectivity, which MONAI uses); a component's label is 1 + the smallest
@@ -85,3 +86,64 @@ def remove_small_components(outputs: torch.Tensor, min_voxels: int, connectivity
     if isinstance(min_voxels, bool) or not isinstance(min_voxels, int) or not 0 <= min_voxels < 2**63:
         raise ValueError(f"min_voxels must be an integer >= 0, got {min_voxels!r}")
     return _one_hot("remove_small_components", outputs, connectivity, return_stats, (min_voxels,))
+
+
+MAX_BALL_REACH = 32  # voxels per axis that a ball may reach (csrc/ball.hip)
+
+
+def check_radius_mm(radius_mm, spacing=None, what: str = "radius_mm") -> float:
+    """`radius_mm` as a float once it is a finite number >= 0 whose ball reaches at most 32 voxels along every axis of `spacing` (None: not checked)."""
+    if isinstance(radius_mm, bool) or not isinstance(radius_mm, (int, float, np.integer, np.floating)) or not math.isfinite(radius_mm) or radius_mm < 0:
+        raise ValueError(f"{what} must be a finite number >= 0 (mm), got {radius_mm!r}")
+    radius_mm = float(radius_mm)
+    for axis, s in enumerate(spacing or ()):
+        reach = math.floor(radius_mm / float(np.float32(s)))  # the fp32 spacing that the library is given
+        if reach > MAX_BALL_REACH:
+            raise ValueError(f"{what} = {radius_mm} reaches {reach} voxels along axis {axis} (spacing {s} mm); at most {MAX_BALL_REACH} are supported")
+    return radius_mm
+
+
+def _ball(caller: str, op: int, outputs, radius_mm, spacing, return_stats: bool):
+    """The body of the four ball operations: vsseg_ball_morphology with `op` once per volume."""
+    B, dims = V.check_prediction("outputs", outputs)
+    spacing = V.spacing3(spacing)
+    radius_mm = check_radius_mm(radius_mm, spacing)
+    lg, _ = V.on_device(caller, "outputs", outputs)
+    stream = torch.cuda.current_stream(lg.device).cuda_stream
+    nv = dims[0] * dims[1] * dims[2]
+    scratch = V.scratch("ball_scratch_bytes", lg.device, dims, stream)
+    out = torch.empty((B, *dims, 2), dtype=torch.float32, device=lg.device)
+    stats = torch.empty((B, 4), dtype=torch.int64, device=lg.device) if return_stats else None
+    V.each_volume("ball_morphology", B, stream, (lg, 2 * nv), 2, L.i3(dims), V.float3(spacing), op, radius_mm, scratch.data_ptr(), scratch.numel(), (out, 2 * nv), (stats, 4))
+    result = out.permute(0, 4, 1, 2, 3)
+    return (result, stats) if return_stats else result
+
+
+def binary_dilate(outputs: torch.Tensor, radius_mm: float, spacing=None, return_stats: bool = False):
+    """The prediction `outputs` [B,2,X,Y,Z] (logits or probabilities, any layout) with its foreground P dilated by a ball of `radius_mm` mm: every voxel of the
+    volume that has a voxel of P at an offset d with (sx dx)^2 + (sy dy)^2 + (sz dz)^2 <= radius_mm^2 (a tie belongs; `spacing` = mm per voxel, None = 1 mm; outside
+    the volume there is no foreground: `scipy.ndimage.binary_dilation` with that ball and border_value 0).  Returns the one-hot fp32 [B,2,X,Y,Z] of
+    `keep_largest_component`; `outputs` is not written.  With `return_stats` also int64 [B,4] on the device: |P|, |result|, voxels added, voxels removed.  The
+    ball may reach 32 voxels per axis; radius 0 returns the one-hot of P.  No host synchronisation."""
+    return _ball("binary_dilate", L.OP_DILATE, outputs, radius_mm, spacing, return_stats)
+
+
+def binary_erode(outputs: torch.Tensor, radius_mm: float, spacing=None, return_stats: bool = False):
+    """The prediction `outputs` [B,2,X,Y,Z] with its foreground P eroded by a ball of `radius_mm` mm: every voxel of P that has no background voxel OF THE VOLUME
+    at a ball offset (the ball of `binary_dilate`).  Positions outside the volume are ignored, they are not background (`scipy.ndimage.binary_erosion` with
+    border_value 1): a tumour cut by the field of view does not shrink at the cut.  The same one-hot result and statistics as `binary_dilate`."""
+    return _ball("binary_erode", L.OP_ERODE, outputs, radius_mm, spacing, return_stats)
+
+
+def binary_close(outputs: torch.Tensor, radius_mm: float, spacing=None, return_stats: bool = False):
+    """The prediction `outputs` [B,2,X,Y,Z] with its foreground closed by a ball of `radius_mm` mm: `binary_erode` of `binary_dilate`, both with the same ball.
+    Fragments less than about 2 * radius_mm apart are bridged and gaps narrower than that are filled; the result contains P (also at the border of the volume)
+    and closing it again changes nothing.  The same one-hot result and statistics as `binary_dilate`."""
+    return _ball("binary_close", L.OP_CLOSE, outputs, radius_mm, spacing, return_stats)
+
+
+def binary_open(outputs: torch.Tensor, radius_mm: float, spacing=None, return_stats: bool = False):
+    """The prediction `outputs` [B,2,X,Y,Z] with its foreground opened by a ball of `radius_mm` mm: `binary_dilate` of `binary_erode`, both with the same ball.
+    Spurs and islands into which the ball does not fit are removed; the result lies inside P and opening it again changes nothing.  The same one-hot result and
+    statistics as `binary_dilate`."""
+    return _ball("binary_open", L.OP_OPEN, outputs, radius_mm, spacing, return_stats)
