@@ -39,6 +39,21 @@ def _crop(vol, wins, roi, pad_before):
     return torch.cat([x[b : b + 1, :, s[0] : s[0] + roi[0], s[1] : s[1] + roi[1], s[2] : s[2] + roi[2]] for b, s in wins])
 
 
+TABLE_ROWS = ("dice", "hd95_mm", "assd_mm", "foreground_voxels", "kept_voxels")
+
+
+def _case_table(cases):
+    """The table of 5 cases with the rows of `cases` written: values that depend on (name, case), one of them NaN, one inf, one past 2^24."""
+    from vs_seg_amd.report import CaseTable
+
+    table = CaseTable(TABLE_ROWS, 5, "cpu")
+    for gi in cases:
+        table.set(gi, ("dice",), torch.tensor([1.0 / (gi + 3)], dtype=torch.float64))
+        table.set(gi, ("hd95_mm", "assd_mm"), torch.tensor([float("nan") if gi == 3 else 1.5 + gi, float("inf") if gi == 2 else 0.25 * gi]))
+        table.set(gi, ("foreground_voxels", "kept_voxels"), torch.tensor([31457280 - gi, 2**24 + 1 + gi]))
+    return table
+
+
 def _worker(rank, world, port, out):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     torch.set_num_threads(2)
@@ -63,6 +78,9 @@ def _worker(rank, world, port, out):
     # 4. per-case scores gathered in case order
     mine = [10.0 * i for i in DP.shard_indices(7)]
     res["scores"] = DP.all_gather_scalars(mine, 7)
+    # 5. the per-case table of run_inference: every rank writes its own cases, one all-reduce, the full table by name on every rank
+    table = _case_table(DP.shard_indices(5))
+    res["table"] = table.gather(DP.allreduce_sum)
     out[rank] = res
     dist.barrier()
     dist.destroy_process_group()
@@ -108,6 +126,16 @@ def test_window_sharded_inference_matches_single_process(two_rank_results):
 def test_scores_gathered_in_case_order(two_rank_results):
     for r in (0, 1):
         assert two_rank_results[r]["scores"] == [0.0, 10.0, 20.0, 30.0, 40.0, 50.0, 60.0]
+
+
+def test_case_table_gathers_the_same_full_dictionary_on_both_ranks(two_rank_results):
+    want = _case_table(range(5)).gather()  # the single-process table
+    assert np.isnan(want["hd95_mm"][3]) and np.isinf(want["assd_mm"][2]) and want["kept_voxels"][4] == 2**24 + 5
+    for r in (0, 1):
+        got = two_rank_results[r]["table"]
+        assert list(got) == list(TABLE_ROWS)
+        for name in TABLE_ROWS:
+            np.testing.assert_array_equal(got[name], want[name])  # (NaN equal to NaN)
 
 
 def _lower_worker(rank, world, port, out, fail, modes):

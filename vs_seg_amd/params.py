@@ -32,6 +32,8 @@ from .inferers import argmax_segmentation, tta_masks
 from .metrics import MEASUREMENT_FIELDS, check_tolerances, compute_measurements, compute_surface_distances, compute_surface_metrics, surface_metric_fields, voxel_spacing
 from .postprocess import binary_close, binary_open, check_radius_mm, connected_components, fill_holes, keep_largest_component, min_component_voxels, remove_small_components
 from . import parallel as DP
+from . import report as R
+from .report import postprocessing_csv_header  # noqa: F401  (part of this module's interface)
 from .data import nifti
 from .data.transforms import ACQUISITION_KEYS, APPEARANCE_KEYS, AUGMENT_KEYS, FIELD_KEYS, PatchSampler, check_acquisition_augment, check_appearance_augment, check_augment, check_field_augment, epoch_batches, load_case
 
@@ -43,16 +45,44 @@ HP = dict(
 )
 
 
-def postprocessing_csv_header(fill_holes: bool, min_component: bool, closing: bool = False, opening: bool = False) -> str:
-    """Columns of figures/test_postprocessing.csv: the six of --keep_largest_component, then those of --fill_holes, --min_component_mm3, --closing_mm and --opening_mm as
-    switched on."""
-    return "case,dice_raw,dice,components,foreground_voxels,kept_voxels" + (",holes,filled_voxels" if fill_holes else "") + (",small_components,small_voxels" if min_component else "") + (
-        ",closed_voxels" if closing else "") + (",opened_voxels" if opening else "")
+def surface_dice_rows(tolerances) -> tuple:
+    """The rows of --surface_dice_mm: masd_mm, then nsd, surface precision and surface recall per tolerance (the columns of compute_surface_metrics after hd and assd)."""
+    return ("masd_mm",) + surface_metric_fields(tolerances)[3:]
 
 
 def surface_dice_csv_header(tolerances) -> str:
     """Columns of figures/test_surface_dice.csv: case, dice, masd_mm, then nsd, surface precision and surface recall per tolerance of --surface_dice_mm."""
-    return "case,dice,masd_mm," + ",".join(surface_metric_fields(tolerances)[3:])
+    return R.csv_header(R.surface_dice(surface_dice_rows(tolerances)))
+
+
+def _fill_step(p, outputs, spacing):
+    outputs, st = fill_holes(outputs, p.hole_connectivity, return_stats=True)
+    return outputs, dict(foreground_voxels=st[0, 0], holes=st[0, 1], filled_voxels=st[0, 2], kept_voxels=st[0, 3])
+
+
+def _closing_step(p, outputs, spacing):
+    outputs, st = binary_close(outputs, p.closing_mm, spacing, return_stats=True)
+    return outputs, dict(foreground_voxels=st[0, 0], kept_voxels=st[0, 1], closed_voxels=st[0, 2])  # closing only adds
+
+
+def _opening_step(p, outputs, spacing):
+    outputs, st = binary_open(outputs, p.opening_mm, spacing, return_stats=True)
+    return outputs, dict(foreground_voxels=st[0, 0], kept_voxels=st[0, 1], opened_voxels=st[0, 3])  # opening only removes
+
+
+def _small_step(p, outputs, spacing):
+    outputs, st = remove_small_components(outputs, min_component_voxels(p.min_component_mm3, spacing), p.component_connectivity, return_stats=True)
+    return outputs, dict(foreground_voxels=st[0, 0], components=st[0, 1], kept_voxels=st[0, 2], small_components=st[0, 1] - st[0, 3], small_voxels=st[0, 0] - st[0, 2])
+
+
+def _largest_step(p, outputs, spacing):
+    outputs, st = keep_largest_component(outputs, p.component_connectivity, return_stats=True)
+    return outputs, dict(foreground_voxels=st[0, 0], components=st[0, 1], kept_voxels=st[0, 2])
+
+
+# the post-processing chain in the order it runs, under the flag names of report.postprocessing (closing before the component filters, so that they see the bridged
+# prediction).  A step maps (params, one-hot prediction, spacing) to the new prediction and its statistics by name: what it was given, what it left, what it did
+POST_STEPS = dict(fill_holes=_fill_step, closing=_closing_step, opening=_opening_step, min_component=_small_step, keep_largest=_largest_step)
 
 
 class CachedLoader:
@@ -233,18 +263,36 @@ class VSparams:
         log = self.logger.info
         log("-" * 10)
         log("Parameters: ")
-        for k in ("dataset", "data_root", "split_csv", "pad_crop_shape", "pad_crop_shape_test", "num_workers", "torch_device_arg", "train_batch_size", "initial_learning_rate",
-                  "epochs_with_const_lr", "lr_divisor", "weight_decay", "num_epochs", "val_interval", "model", "sliding_window_inferer_roi_size", "attention", "hardness",
-                  "results_folder_path", "export_inferred_segmentations", "compute_dtype") + (("surface_metrics",) if self.surface_metrics else ()) + (("surface_dice_mm",) if self.surface_dice_mm else ()) + (("measurements",) if self.measurements else ()) + (
-                      ("fill_holes", "hole_connectivity") if self.fill_holes else ()) + (("closing_mm",) if self.closing_mm > 0 else ()) + (("opening_mm",) if self.opening_mm > 0 else ()) + (("min_component_mm3",) if self.min_component_mm3 > 0 else ()) + (
-                      ("keep_largest_component", "component_connectivity") if self.keep_largest_component else ("component_connectivity",) if self.min_component_mm3 > 0 else ()) + (("tta_flips", "tta_average") if self.tta_flips else ()) + (
-                          tuple("aug_" + k for k in AUGMENT_KEYS) if any(self.augment.values()) else ()) + (
-                              ("aug_elastic_mag", "aug_bias_field", "aug_field_spacing") if self.aug_elastic_mag or self.aug_bias_field else ()) + (
-                                  tuple("aug_" + k for k in APPEARANCE_KEYS) if self._appearance_on else ()) + (tuple("aug_" + k for k in ACQUISITION_KEYS) if self._acquisition_on else ()) + (("ce_weight", "ce_foreground_weight") if self.ce_weight > 0 else ()) + (("ce_topk",) if self.ce_topk > 0 else ()) + (
-                                      ("tversky_beta", "focal_tversky_gamma", "batch_dice") if self.tversky_beta is not None else ()) + (("ce_focal_gamma",) if self.ce_focal_gamma > 0 else ()) + (
-                                      (("optimizer",) + (("momentum", "nesterov") if self.optimizer == "sgd" else ())) if self.optimizer != "adam" else ()) + (
-                                          ("clip_grad_norm",) if self.clip_grad_norm > 0 else ()) + (("lr_schedule", "poly_power") if self.lr_schedule == "poly" else ()):
-            log("{:<34s} {}".format(k + " =", getattr(self, k)))
+        logged = [  # (parameter names, logged when), in log order: an addition of this implementation is logged only where it is switched on
+            (("dataset", "data_root", "split_csv", "pad_crop_shape", "pad_crop_shape_test", "num_workers", "torch_device_arg", "train_batch_size", "initial_learning_rate",
+              "epochs_with_const_lr", "lr_divisor", "weight_decay", "num_epochs", "val_interval", "model", "sliding_window_inferer_roi_size", "attention", "hardness",
+              "results_folder_path", "export_inferred_segmentations", "compute_dtype"), True),
+            (("surface_metrics",), self.surface_metrics),
+            (("surface_dice_mm",), self.surface_dice_mm),
+            (("measurements",), self.measurements),
+            (("fill_holes", "hole_connectivity"), self.fill_holes),
+            (("closing_mm",), self.closing_mm > 0),
+            (("opening_mm",), self.opening_mm > 0),
+            (("min_component_mm3",), self.min_component_mm3 > 0),
+            (("keep_largest_component",), self.keep_largest_component),
+            (("component_connectivity",), self.keep_largest_component or self.min_component_mm3 > 0),
+            (("tta_flips", "tta_average"), self.tta_flips),
+            (tuple("aug_" + k for k in AUGMENT_KEYS), any(self.augment.values())),
+            (("aug_elastic_mag", "aug_bias_field", "aug_field_spacing"), self.aug_elastic_mag or self.aug_bias_field),
+            (tuple("aug_" + k for k in APPEARANCE_KEYS), self._appearance_on),
+            (tuple("aug_" + k for k in ACQUISITION_KEYS), self._acquisition_on),
+            (("ce_weight", "ce_foreground_weight"), self.ce_weight > 0),
+            (("ce_topk",), self.ce_topk > 0),
+            (("tversky_beta", "focal_tversky_gamma", "batch_dice"), self.tversky_beta is not None),
+            (("ce_focal_gamma",), self.ce_focal_gamma > 0),
+            (("optimizer",), self.optimizer != "adam"),
+            (("momentum", "nesterov"), self.optimizer == "sgd"),
+            (("clip_grad_norm",), self.clip_grad_norm > 0),
+            (("lr_schedule", "poly_power"), self.lr_schedule == "poly"),
+        ]
+        for names, on in logged:
+            for k in names if on else ():
+                log("{:<34s} {}".format(k + " =", getattr(self, k)))
         log("-" * 10)
 
     # ------------------------------------------------------------------ data
@@ -492,22 +540,24 @@ class VSparams:
         load_checkpoint(model, os.path.join(self.model_path, "best_metric_model.pth"))
         return model
 
+    @property
+    def _post_flags(self) -> Dict[str, bool]:
+        """Which steps of the post-processing chain are on, under the names of POST_STEPS and report.postprocessing."""
+        return dict(fill_holes=self.fill_holes, closing=self.closing_mm > 0, opening=self.opening_mm > 0, min_component=self.min_component_mm3 > 0, keep_largest=self.keep_largest_component)
+
+    def _reports(self) -> List[R.Report]:
+        """The reports that are switched on, in the order of their sections in the log."""
+        return ([R.postprocessing(**self._post_flags)] if any(self._post_flags.values()) else []) + ([R.surface_metrics()] if self.surface_metrics else []) + (
+            [R.surface_dice(surface_dice_rows(self.surface_dice_mm))] if self.surface_dice_mm else []) + ([R.measurements(MEASUREMENT_FIELDS)] if self.measurements else [])
+
     def run_inference(self, model, data_loader):
         logger = self.logger
         logger.info("Running inference...")
         model.eval()
         n = len(data_loader)
-        dice_dev = torch.zeros(n, dtype=torch.float32, device=self.device)
-        surf_dev = torch.zeros((2, n), dtype=torch.float32, device=self.device) if self.surface_metrics else None  # [hd95, assd] per case, mm
-        # --fill_holes / --closing_mm / --opening_mm / --min_component_mm3 / --keep_largest_component: [raw Dice, foreground voxels, components, kept voxels] per case, then
-        # [holes, filled voxels], [small components, small voxels], [closed voxels] and [opened voxels] as switched on (fp64: the voxel counts of a full volume are not
-        # exact in fp32)
-        small, closing, opening = self.min_component_mm3 > 0, self.closing_mm > 0, self.opening_mm > 0
-        post_rows = 4 + 2 * self.fill_holes + 2 * small + closing + opening if (self.fill_holes or small or closing or opening or self.keep_largest_component) else 0
-        post_dev = torch.zeros((post_rows, n), dtype=torch.float64, device=self.device) if post_rows else None
-        meas_dev = torch.zeros((len(MEASUREMENT_FIELDS), n), dtype=torch.float64, device=self.device) if self.measurements else None  # --measurements: the nine values per case
-        # --surface_dice_mm: [masd, then nsd, surface precision, surface recall per tolerance] per case
-        sdice_dev = torch.zeros((1 + 3 * len(self.surface_dice_mm), n), dtype=torch.float32, device=self.device) if self.surface_dice_mm else None
+        reports = self._reports()
+        table = R.CaseTable(("dice",) + tuple(k for rep in reports for k in rep.rows), n, self.device)
+        post_rows = R.postprocessing(**self._post_flags).rows[1:] if any(self._post_flags.values()) else ()  # after dice_raw: the statistics of the chain
         predictor = model.segmentation_predictor() if hasattr(model, "segmentation_predictor") else (lambda *a, **k: model(*a, **k)[0])  # model_segmentation, ref:params/VSparams.py:560
         mine = DP.shard_indices(n)  # the unpadded, unshuffled test loader yields exactly these cases, in this order
         with torch.no_grad():
@@ -516,180 +566,39 @@ class VSparams:
                 logger.info("starting image {}".format(mine[i]))
                 outputs = sliding_window_inference(inputs=data["image"], roi_size=self.sliding_window_inferer_roi_size, sw_batch_size=1, predictor=predictor, mode="gaussian",
                                                    tta_flips=self.tta_flips, tta_average=self.tta_average)
-                gi = mine[i]
-                if post_dev is not None:  # everything below describes the filtered prediction; the raw Dice is kept beside it
-                    post_dev[0, gi] = self.compute_dice_score(outputs, data["label"]).reshape(())
-                    outputs, post_dev[1:, gi] = self._postprocess(outputs, voxel_spacing(data["label_meta_dict"]["affine"]))
-                dice_dev[gi] = self.compute_dice_score(outputs, data["label"]).reshape(())
-                if sdice_dev is not None:  # one call: its first two columns are the bits compute_surface_distances returns
-                    sm = compute_surface_metrics(outputs, data["label"], voxel_spacing(data["label_meta_dict"]["affine"]), 95.0, self.surface_dice_mm)[0]
-                    sdice_dev[:, gi] = sm[2:]
-                    if surf_dev is not None:
-                        surf_dev[:, gi] = sm[:2]
-                elif surf_dev is not None:
-                    surf_dev[:, gi] = compute_surface_distances(outputs, data["label"], voxel_spacing(data["label_meta_dict"]["affine"]), 95.0)[0]
-                if meas_dev is not None:
-                    meas_dev[:, gi] = compute_measurements(outputs, data["label"], voxel_spacing(data["label_meta_dict"]["affine"]))[0]
+                gi, label, spacing = mine[i], data["label"], voxel_spacing(data["label_meta_dict"]["affine"])
+                if post_rows:  # everything below describes the filtered prediction; the raw Dice is kept beside it
+                    table.set(gi, ("dice_raw",), self.compute_dice_score(outputs, label).reshape(1))
+                    outputs, stats = self._postprocess(outputs, spacing)
+                    table.set(gi, post_rows, torch.stack([stats[k] for k in post_rows]))
+                table.set(gi, ("dice",), self.compute_dice_score(outputs, label).reshape(1))
+                if self.surface_dice_mm:  # one call: its first two columns are the bits compute_surface_distances returns
+                    sm = compute_surface_metrics(outputs, label, spacing, 95.0, self.surface_dice_mm)[0]
+                    table.set(gi, surface_dice_rows(self.surface_dice_mm), sm[2:])
+                    if self.surface_metrics:
+                        table.set(gi, R.SURFACE_ROWS, sm[:2])
+                elif self.surface_metrics:
+                    table.set(gi, R.SURFACE_ROWS, compute_surface_distances(outputs, label, spacing, 95.0)[0])
+                if self.measurements:
+                    table.set(gi, MEASUREMENT_FIELDS, compute_measurements(outputs, label, spacing)[0])
                 if self.export_inferred_segmentations:
                     self.export_segmentation(outputs, data["label_meta_dict"])
-        surf = post = meas = sdice = None
-        if surf_dev is not None or post_dev is not None or meas_dev is not None or sdice_dev is not None:
-            rows = [dice_dev[None]] + [r for r in (surf_dev, post_dev, meas_dev, sdice_dev) if r is not None]
-            both = torch.cat(rows)  # one all-reduce; a case that is not this rank's is 0 here (NaN / inf + 0 stay NaN / inf)
-            both = (DP.allreduce_sum(both) if self.world > 1 else both).double().cpu().numpy()
-            dice_scores = both[0]
-            if sdice_dev is not None:
-                both, sdice = both[:-len(sdice_dev)], both[-len(sdice_dev):]
-            if surf_dev is not None:
-                surf = both[1:3]
-            if meas_dev is not None:
-                both, meas = both[:-len(MEASUREMENT_FIELDS)], both[-len(MEASUREMENT_FIELDS):]
-            if post_dev is not None:
-                post = both[-post_rows:]
-        else:
-            dice_scores = DP.allreduce_sum(dice_dev).double().cpu().numpy() if self.world > 1 else dice_dev.double().cpu().numpy()
-        for i, v in enumerate(dice_scores):
-            logger.info(f"dice_score[{i}] = {v}")
-        logger.info(f"all_dice_scores = {dice_scores}")
-        logger.info(f"mean_dice_score = {dice_scores.mean()} +- {dice_scores.std()}")
-        if post is not None:
-            self._log_postprocessing(dice_scores, *post)
-        if surf is not None:
-            self._log_surface_metrics(dice_scores, surf[0], surf[1])
-        if sdice is not None:
-            self._log_surface_dice(dice_scores, sdice)
-        if meas is not None:
-            self._log_measurements(dice_scores, meas)
-        return dice_scores
+        values = table.gather(DP.allreduce_sum if self.world > 1 else None)  # one all-reduce, one host read
+        R.emit(reports, values, logger.info, self.figures_path if self.rank == 0 else None)
+        return values["dice"]
 
     def _postprocess(self, outputs, spacing):
-        """The post-processing steps that are switched on, each on the output of the previous one: fill holes, closing, opening, remove small components, keep the
-        largest (closing before the component filters, so that they see the bridged prediction).  Returns the final one-hot prediction and the rows of the case for the
-        all-reduce, all on the device: foreground voxels of the raw prediction, components of the prediction that enters the first component filter (without one: of the
-        final prediction), voxels of the final prediction, then [holes, filled voxels], [small components, small voxels], [closed voxels] and [opened voxels] as
-        switched on."""
-        foreground = components = None
-        extra, ball = [], []
-        if self.fill_holes:
-            outputs, st = fill_holes(outputs, self.hole_connectivity, return_stats=True)
-            foreground, kept = st[0, 0], st[0, 3]
-            extra += [st[0, 1], st[0, 2]]
-        if self.closing_mm > 0:
-            outputs, st = binary_close(outputs, self.closing_mm, spacing, return_stats=True)
-            foreground, kept = st[0, 0] if foreground is None else foreground, st[0, 1]
-            ball.append(st[0, 2])  # closing only adds
-        if self.opening_mm > 0:
-            outputs, st = binary_open(outputs, self.opening_mm, spacing, return_stats=True)
-            foreground, kept = st[0, 0] if foreground is None else foreground, st[0, 1]
-            ball.append(st[0, 3])  # opening only removes
-        if self.min_component_mm3 > 0:
-            outputs, st = remove_small_components(outputs, min_component_voxels(self.min_component_mm3, spacing), self.component_connectivity, return_stats=True)
-            foreground, components, kept = st[0, 0] if foreground is None else foreground, st[0, 1], st[0, 2]
-            extra += [st[0, 1] - st[0, 3], st[0, 0] - st[0, 2]]
-        if self.keep_largest_component:
-            outputs, st = keep_largest_component(outputs, self.component_connectivity, return_stats=True)
-            foreground, components, kept = st[0, 0] if foreground is None else foreground, st[0, 1] if components is None else components, st[0, 2]
-        if components is None:  # no component filter: --fill_holes, --closing_mm, --opening_mm alone or together
-            components = connected_components(outputs, self.component_connectivity)[1][0, 1]
-        return outputs, torch.stack([foreground, components, kept] + extra + ball).double()
-
-    def _log_postprocessing(self, dice, dice_raw, foreground, components, kept, *extra):
-        """Per-case lines of --fill_holes / --closing_mm / --opening_mm / --min_component_mm3 / --keep_largest_component beside the (post-processed) dice_score lines, and
-        figures/test_postprocessing.csv (rank 0).  extra: [holes, filled voxels] with --fill_holes, then [small components, small voxels] with --min_component_mm3, then
-        [closed voxels] with --closing_mm and [opened voxels] with --opening_mm."""
-        log = self.logger.info
-        extra = list(extra)
-        holes, filled = (extra.pop(0), extra.pop(0)) if self.fill_holes else (None, None)
-        small_components, small_voxels = (extra.pop(0), extra.pop(0)) if self.min_component_mm3 > 0 else (None, None)
-        closed = extra.pop(0) if self.closing_mm > 0 else None
-        opened = extra.pop(0) if self.opening_mm > 0 else None
-        for i, (d, f, c, k) in enumerate(zip(dice_raw, foreground, components, kept)):
-            log(f"dice_score_raw[{i}] = {d}")
-            if holes is not None:
-                log(f"holes[{i}] = {int(holes[i])}")
-                log(f"filled_voxels[{i}] = {int(filled[i])}")
-            if closed is not None:
-                log(f"closed_voxels[{i}] = {int(closed[i])}")
-            if opened is not None:
-                log(f"opened_voxels[{i}] = {int(opened[i])}")
-            log(f"components[{i}] = {int(c)}")
-            if small_components is not None:
-                log(f"small_components_removed[{i}] = {int(small_components[i])}")
-                log(f"small_voxels_removed[{i}] = {int(small_voxels[i])}")
-            if self.keep_largest_component or small_components is not None or opened is not None:  # everything taken away after the additions: by the opening and the component filters
-                log(f"removed_voxels[{i}] = {int(f) + (int(filled[i]) if filled is not None else 0) + (int(closed[i]) if closed is not None else 0) - int(k)}")
-        log(f"mean_dice_score_raw = {dice_raw.mean()} +- {dice_raw.std()}")
-        if self.rank == 0:
-            os.makedirs(self.figures_path, exist_ok=True)
-            with open(os.path.join(self.figures_path, "test_postprocessing.csv"), "w") as f:
-                f.write(postprocessing_csv_header(self.fill_holes, self.min_component_mm3 > 0, closed is not None, opened is not None) + "\n")
-                for i, (r, d, c, fg, k) in enumerate(zip(dice_raw, dice, components, foreground, kept)):
-                    more = ([holes[i], filled[i]] if holes is not None else []) + ([small_components[i], small_voxels[i]] if small_components is not None else []) + (
-                        [closed[i]] if closed is not None else []) + ([opened[i]] if opened is not None else [])
-                    f.write(f"{i},{float(r)!r},{float(d)!r},{int(c)},{int(fg)},{int(k)}" + "".join(f",{int(v)}" for v in more) + "\n")
-
-    def _log_surface_metrics(self, dice, hd95, assd):
-        """Per-case HD95 / ASSD lines, their mean +- std over the finite cases, and figures/test_surface_metrics.csv (rank 0)."""
-        log = self.logger.info
-        for i, (h, a) in enumerate(zip(hd95, assd)):
-            log(f"hd95_mm[{i}] = {h}")
-            log(f"assd_mm[{i}] = {a}")
-        for name, v in (("mean_hd95_mm", hd95), ("mean_assd_mm", assd)):
-            fin = v[np.isfinite(v)]
-            m, sd = (fin.mean(), fin.std()) if len(fin) else (float("nan"), float("nan"))
-            log(f"{name} = {m} +- {sd} ({len(v) - len(fin)} of {len(v)} cases non-finite)")
-        if self.rank == 0:
-            os.makedirs(self.figures_path, exist_ok=True)
-            with open(os.path.join(self.figures_path, "test_surface_metrics.csv"), "w") as f:
-                f.write("case,dice,hd95_mm,assd_mm\n")
-                for i, (d, h, a) in enumerate(zip(dice, hd95, assd)):
-                    f.write(f"{i},{float(d)!r},{float(h)!r},{float(a)!r}\n")
-
-    def _log_surface_dice(self, dice, rows):
-        """Per-case lines of --surface_dice_mm (masd, then nsd / surface precision / surface recall per tolerance), their mean +- std over the finite cases, and
-        figures/test_surface_dice.csv (rank 0)."""
-        log = self.logger.info
-        names = ("masd_mm",) + surface_metric_fields(self.surface_dice_mm)[3:]
-        for i in range(len(dice)):
-            for name, v in zip(names, rows):
-                log(f"{name}[{i}] = {v[i]}")
-        for name, v in zip(names, rows):
-            fin = v[np.isfinite(v)]
-            m, sd = (fin.mean(), fin.std()) if len(fin) else (float("nan"), float("nan"))
-            log(f"mean_{name} = {m} +- {sd} ({len(v) - len(fin)} of {len(v)} cases non-finite)")
-        if self.rank == 0:
-            os.makedirs(self.figures_path, exist_ok=True)
-            with open(os.path.join(self.figures_path, "test_surface_dice.csv"), "w") as f:
-                f.write(surface_dice_csv_header(self.surface_dice_mm) + "\n")
-                for i, d in enumerate(dice):
-                    f.write(",".join([str(i), repr(float(d))] + [repr(float(v[i])) for v in rows]) + "\n")
-
-    def _log_measurements(self, dice, meas):
-        """Per-case volume / centroid / diameter lines of --measurements, the volume and diameter errors over the cases, and figures/test_measurements.csv (rank 0)."""
-        log = self.logger.info
-        m = dict(zip(MEASUREMENT_FIELDS, meas))
-        n = len(dice)
-        vol_err = m["volume_pred_mm3"] - m["volume_label_mm3"]
-        with np.errstate(divide="ignore", invalid="ignore"):
-            rel_err = np.where(m["voxels_label"] > 0, np.abs(vol_err) / m["volume_label_mm3"], np.nan)  # NaN: the label is empty
-        for i in range(n):
-            for name in ("volume_pred_mm3", "volume_label_mm3"):
-                log(f"{name}[{i}] = {m[name][i]}")
-            log(f"volume_error_mm3[{i}] = {vol_err[i]}")
-            for name in MEASUREMENT_FIELDS[4:]:
-                log(f"{name}[{i}] = {m[name][i]}")
-        diffs = [("mean_abs_volume_error_mm3", np.abs(vol_err), "non-finite"), ("mean_rel_volume_error", rel_err, "with an empty label")] + [
-            (f"mean_abs_{d}_error_mm", np.abs(m[f"{d}_pred_mm"] - m[f"{d}_label_mm"]), "with an empty mask") for d in ("max_diameter", "max_axial_diameter")]
-        for name, v, why in diffs:
-            fin = v[np.isfinite(v)]
-            mean, sd = (fin.mean(), fin.std()) if len(fin) else (float("nan"), float("nan"))
-            log(f"{name} = {mean} +- {sd} ({n - len(fin)} of {n} cases {why} left out)")
-        if self.rank == 0:
-            os.makedirs(self.figures_path, exist_ok=True)
-            with open(os.path.join(self.figures_path, "test_measurements.csv"), "w") as f:
-                f.write("case,dice," + ",".join(MEASUREMENT_FIELDS) + ",volume_error_mm3,volume_rel_error\n")
-                for i in range(n):
-                    f.write(",".join([str(i), repr(float(dice[i]))] + [repr(float(m[k][i])) for k in MEASUREMENT_FIELDS] + [repr(float(vol_err[i])), repr(float(rel_err[i]))]) + "\n")
+        """The steps of POST_STEPS that are switched on, each on the output of the previous one.  Returns the final one-hot prediction and the statistics of the case by name,
+        on the device: foreground_voxels of the raw prediction, components of the input of the first component filter (without one: of the final prediction), kept_voxels of
+        the final prediction, and what each step filled, closed, opened or removed."""
+        stats = {}
+        for name, step in POST_STEPS.items():
+            if self._post_flags[name]:
+                outputs, st = step(self, outputs, spacing)
+                stats = {**st, **stats, "kept_voxels": st["kept_voxels"]}  # a name belongs to the first step that reports it (foreground_voxels, components); kept_voxels to the last
+        if "components" not in stats:  # no component filter: --fill_holes, --closing_mm, --opening_mm alone or together
+            stats["components"] = connected_components(outputs, self.component_connectivity)[1][0, 1]
+        return outputs, stats
 
     def export_segmentation(self, outputs, label_meta):
         """N3: argmax → uint8 NIfTI in the label's original orientation / affine, under
