@@ -23,7 +23,8 @@ is the product path: cached volumes live in HBM, one launch crops/flips image an
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional, Sequence, Tuple
+from dataclasses import dataclass
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -46,52 +47,36 @@ def pad_widths(shape: Sequence[int], spatial_size: Sequence[int]) -> List[Tuple[
     return out
 
 
-AUGMENT_KEYS = ("rotate_deg", "scale", "intensity_scale", "intensity_shift", "noise_std")
+def _bind(defaults: Dict, values: Sequence, named: Dict, what: str) -> Dict:
+    """`values`, then `named`, over `defaults`, as a Python call binds them: TypeError for too many values, an unknown name and a name given twice."""
+    if len(values) > len(defaults):
+        raise TypeError(f"{what} takes at most {len(defaults)} positional ranges ({len(values)} given)")
+    given = dict(zip(defaults, values))
+    for k in named:
+        if k not in defaults or k in given:
+            raise TypeError(f"{what} got " + ("multiple values for argument" if k in given else "an unexpected keyword argument") + f" '{k}'")
+    return {**defaults, **given, **named}
 
 
-def check_augment(rotate_deg=0.0, scale=0.0, intensity_scale=0.0, intensity_shift=0.0, noise_std=0.0) -> Dict[str, float]:
-    """The five augmentation ranges as floats (0 = off); ValueError for a negative or non-finite range, rotate_deg > 180, scale or intensity_scale >= 1."""
-    a = dict(rotate_deg=float(rotate_deg), scale=float(scale), intensity_scale=float(intensity_scale), intensity_shift=float(intensity_shift), noise_std=float(noise_std))
-    for k, v in a.items():
-        if not (np.isfinite(v) and v >= 0.0):
-            raise ValueError(f"augmentation range {k} = {v}: must be finite and >= 0")
+def _augment_rules(a, raw):
     if a["rotate_deg"] > 180.0:
         raise ValueError(f"rotate_deg = {a['rotate_deg']}: at most 180")
     for k in ("scale", "intensity_scale"):
         if a[k] >= 1.0:
             raise ValueError(f"{k} = {a[k]}: must be < 1 (the factor 1 + u stays positive)")
-    return a
 
 
-FIELD_KEYS = ("elastic_mag", "bias_field", "field_spacing")
-
-
-def check_field_augment(elastic_mag=0.0, bias_field=0.0, field_spacing=64) -> Dict[str, float]:
-    """The two field ranges as floats (0 = off) and the in-plane control-point spacing as an int; ValueError for a negative or non-finite range, a spacing that is no
-    integer >= 1, and elastic_mag > field_spacing / 4 (beyond it the deformation could fold: include/vsseg_hip.h)."""
-    f = dict(elastic_mag=float(elastic_mag), bias_field=float(bias_field))
-    for k, v in f.items():
-        if not (np.isfinite(v) and v >= 0.0):
-            raise ValueError(f"augmentation range {k} = {v}: must be finite and >= 0")
-    sp = float(field_spacing)
+def _field_rules(a, raw):
+    """The in-plane control-point spacing is an integer >= 1 (returned as an int); elastic_mag <= field_spacing / 4 (beyond it the deformation could fold: vsseg_hip.h)."""
+    sp = float(raw["field_spacing"])
     if not (np.isfinite(sp) and sp >= 1.0 and sp == int(sp)):
-        raise ValueError(f"field_spacing = {field_spacing}: must be an integer >= 1 (voxels)")
-    if f["elastic_mag"] > sp / 4.0:
-        raise ValueError(f"elastic_mag = {f['elastic_mag']}: at most field_spacing / 4 = {sp / 4.0} (the deformation must not fold)")
-    f["field_spacing"] = int(sp)
-    return f
+        raise ValueError(f"field_spacing = {raw['field_spacing']}: must be an integer >= 1 (voxels)")
+    if a["elastic_mag"] > sp / 4.0:
+        raise ValueError(f"elastic_mag = {a['elastic_mag']}: at most field_spacing / 4 = {sp / 4.0} (the deformation must not fold)")
+    a["field_spacing"] = int(sp)
 
 
-APPEARANCE_KEYS = ("blur_sigma", "lowres", "contrast", "gamma", "appearance_prob")
-
-
-def check_appearance_augment(blur_sigma=0.0, lowres=0.0, contrast=0.0, gamma=0.0, appearance_prob=0.25) -> Dict[str, float]:
-    """The four appearance ranges (0 = off) and the per-sample, per-family probability as floats; ValueError for a non-finite value, blur_sigma outside [0, 1.5]
-    (the radius ceil(3 sigma) stays <= 5), lowres that is neither 0 nor in [0.25, 1), contrast or gamma outside [0, 1) and appearance_prob outside [0, 1]."""
-    a = dict(blur_sigma=float(blur_sigma), lowres=float(lowres), contrast=float(contrast), gamma=float(gamma), appearance_prob=float(appearance_prob))
-    for k, v in a.items():
-        if not (np.isfinite(v) and v >= 0.0):
-            raise ValueError(f"augmentation range {k} = {v}: must be finite and >= 0")
+def _appearance_rules(a, raw):
     if a["blur_sigma"] > 1.5:
         raise ValueError(f"blur_sigma = {a['blur_sigma']}: at most 1.5 in-plane voxels (a radius of 5)")
     if a["lowres"] != 0.0 and not 0.25 <= a["lowres"] < 1.0:
@@ -101,29 +86,81 @@ def check_appearance_augment(blur_sigma=0.0, lowres=0.0, contrast=0.0, gamma=0.0
             raise ValueError(f"{k} = {a[k]}: must be < 1 (the factor 1 + u stays positive)")
     if a["appearance_prob"] > 1.0:
         raise ValueError(f"appearance_prob = {a['appearance_prob']}: a probability, at most 1")
-    return a
 
 
-ACQUISITION_KEYS = ("thick_slices", "ghost", "spike", "acquisition_prob")
-GHOST_COUNTS = (2, 3, 4, 6, 8)  # the ghost counts a sample may draw: those that divide the axis
-
-
-def check_acquisition_augment(thick_slices=0, ghost=0.0, spike=0.0, acquisition_prob=0.25) -> Dict[str, float]:
-    """The three acquisition ranges (0 = off) and the per-sample, per-family probability; ValueError for a non-finite value, thick_slices that is neither 0 nor an
-    integer in 2..4 (the largest slab height in voxels along z: 4 x 1.5 mm = 6 mm slices), ghost outside [0, 1] (the largest attenuation of the ghosted k-space
-    lines), spike < 0 (the largest amplitude, in standard deviations of the normalised image) and acquisition_prob outside [0, 1]."""
-    a = dict(thick_slices=float(thick_slices), ghost=float(ghost), spike=float(spike), acquisition_prob=float(acquisition_prob))
-    for k, v in a.items():
-        if not (np.isfinite(v) and v >= 0.0):
-            raise ValueError(f"augmentation range {k} = {v}: must be finite and >= 0")
+def _acquisition_rules(a, raw):
+    """thick_slices 0 or an integer in 2..4 (the largest slab height in voxels along z: 4 x 1.5 mm = 6 mm slices; returned as an int), ghost <= 1 (the largest
+    attenuation of the ghosted k-space lines), acquisition_prob <= 1; spike is the largest amplitude in standard deviations of the normalised image."""
     if a["thick_slices"] != int(a["thick_slices"]) or int(a["thick_slices"]) not in (0, 2, 3, 4):
-        raise ValueError(f"thick_slices = {thick_slices}: 0 (off) or an integer slab height in 2..4 voxels")
+        raise ValueError(f"thick_slices = {raw['thick_slices']}: 0 (off) or an integer slab height in 2..4 voxels")
     a["thick_slices"] = int(a["thick_slices"])
     if a["ghost"] > 1.0:
         raise ValueError(f"ghost = {a['ghost']}: an attenuation, at most 1")
     if a["acquisition_prob"] > 1.0:
         raise ValueError(f"acquisition_prob = {a['acquisition_prob']}: a probability, at most 1")
-    return a
+
+
+@dataclass(frozen=True)
+class Family:
+    """One row of FAMILIES: everything between a flag and a launch that knows an augmentation family by name reads it from here."""
+
+    name: str  # the attribute of RandomTail and the key of Augmentation.values that hold its validated arguments
+    defaults: Dict[str, float]  # its arguments in positional order with their defaults (0 = off)
+    ranges: Tuple[str, ...]  # those whose non-zero value switches the family on (a probability and field_spacing are no ranges)
+    flag: str  # the attribute of RandomTail that says whether it is on
+    rng: str  # the attribute of RandomTail that holds its RandomState (None while it is off)
+    key: str  # the key it travels under in a transform description (VSparams.get_transforms, CachedLoader)
+    rules: Callable[[Dict, Dict], None]  # its own rules beyond "finite and >= 0", over (the floats, the arguments as given)
+    own: Tuple[str, ...] = ()  # arguments that only `rules` looks at and adds
+
+    def check(self, *values, **named) -> Dict[str, float]:
+        """The arguments as floats (or what `rules` makes of them), in positional order; ValueError for a negative or non-finite value and for what `rules` rejects."""
+        raw = _bind(self.defaults, values, named, "check_" + self.key)
+        a = {k: float(v) for k, v in raw.items() if k not in self.own}
+        for k, v in a.items():
+            if not (np.isfinite(v) and v >= 0.0):
+                raise ValueError(f"augmentation range {k} = {v}: must be finite and >= 0")
+        self.rules(a, raw)
+        return a
+
+
+# In SEEDING ORDER: RandomTail seeds flip, crop, then one state per family that is on, in this order.  A family that is off draws no seed, so switching a family on never
+# moves the draws of the families before it, and a new family goes LAST: that alone keeps the flips, crops and draws of every earlier training run reproducible.
+FAMILIES = (
+    Family("augment", dict(rotate_deg=0.0, scale=0.0, intensity_scale=0.0, intensity_shift=0.0, noise_std=0.0), ("rotate_deg", "scale", "intensity_scale", "intensity_shift", "noise_std"),
+           "augmenting", "_augR", "augment", _augment_rules),
+    Family("field", dict(elastic_mag=0.0, bias_field=0.0, field_spacing=64), ("elastic_mag", "bias_field"), "fielding", "_fieldR", "field_augment", _field_rules, own=("field_spacing",)),
+    Family("appearance", dict(blur_sigma=0.0, lowres=0.0, contrast=0.0, gamma=0.0, appearance_prob=0.25), ("blur_sigma", "lowres", "contrast", "gamma"),
+           "appearing", "_appR", "appearance_augment", _appearance_rules),
+    Family("acquisition", dict(thick_slices=0, ghost=0.0, spike=0.0, acquisition_prob=0.25), ("thick_slices", "ghost", "spike"), "acquiring", "_acqR", "acquisition_augment", _acquisition_rules),
+)
+AUGMENT_KEYS, FIELD_KEYS, APPEARANCE_KEYS, ACQUISITION_KEYS = (tuple(f.defaults) for f in FAMILIES)
+check_augment, check_field_augment, check_appearance_augment, check_acquisition_augment = (f.check for f in FAMILIES)
+DEFAULTS = {k: v for f in FAMILIES for k, v in f.defaults.items()}  # every argument of every family, in table order
+GHOST_COUNTS = (2, 3, 4, 6, 8)  # the ghost counts a sample may draw: those that divide the axis
+
+
+@dataclass(frozen=True)
+class Augmentation:
+    """The validated arguments of every family, made once where they enter (a constructor, the command line) and handed on whole."""
+
+    values: Dict[str, Dict[str, float]]  # Family.name -> what its `check` returned
+
+    @classmethod
+    def of(cls, *ranges, **named) -> "Augmentation":
+        """From the arguments of all families in table order, by position, by name or both (a record is returned as it is); TypeError as a call, ValueError of a family."""
+        if len(ranges) == 1 and isinstance(ranges[0], cls) and not named:
+            return ranges[0]
+        flat = _bind(DEFAULTS, ranges, named, "Augmentation.of")
+        return cls({f.name: f.check(*(flat[k] for k in f.defaults)) for f in FAMILIES})
+
+    def on(self, family: Family) -> bool:
+        return any(self.values[family.name][k] != 0 for k in family.ranges)
+
+    def flat(self) -> Dict[str, float]:
+        return {k: v for d in self.values.values() for k, v in d.items()}
+
+
 
 
 NEUTRAL_ACQUISITION = dict(thick=1, thick_offset=0, ghost_axis=0, ghosts=0, ghost_alpha=np.float32(0.0), spike_amp=np.float32(0.0), spike_k=(0, 0), spike_phase=np.float32(0.0))
@@ -172,23 +209,22 @@ class RandomTail:
     `R.randint(MAX_SEED, dtype=uint32)`; RandFlipd draws `R.random_sample() < prob`, RandSpatialCropd draws
     `R.randint(0, size - roi + 1)` per axis where size > roi.
 
-    With a non-zero augmentation range a THIRD state is seeded from `R` after those two, so the flip and crop draws are the same with
-    augmentation on or off.  `draw_augment()` draws per sample, in this order and only for the families whose range is non-zero:
-    angle ~ U(-rotate_deg, rotate_deg), scale factor 1 + U(-scale, scale), gain 1 + U(-intensity_scale, intensity_scale),
-    bias ~ U(-intensity_shift, intensity_shift); `draw_noise_seed()` draws one randint(2^32) per batch when noise_std != 0.
+    After those two, every family of FAMILIES that is on (a range non-zero) gets a state of its own, seeded from `R` in table order; one that is off draws no seed.  So
+    flip, crop and every family earlier in the table draw the same with a family on or off.  `*ranges, **named` are the arguments of all families (Augmentation.of) or
+    one Augmentation; per family the tail holds the validated dict (`augment`, `field`, `appearance`, `acquisition`), its on-flag (`augmenting`, ...) and its state.
 
-    With a non-zero field range (`elastic_mag`, `bias_field`) a FOURTH state is seeded from `R` after those, so the flip, crop and five-family draws are the same with
-    the fields on or off.  `draw_field_seed()` draws one randint(2^32) per batch (the high half of the launch seed: the lattice differs from batch to batch, noise or no
-    noise); `draw_field()` draws per sample, in this order and only for the families that are on: a ~ U(0, elastic_mag), beta ~ U(0, bias_field).
+    augment: `draw_augment()` draws per sample, in this order and only for the ranges that are non-zero: angle ~ U(-rotate_deg, rotate_deg), scale factor
+    1 + U(-scale, scale), gain 1 + U(-intensity_scale, intensity_scale), bias ~ U(-intensity_shift, intensity_shift); `draw_noise_seed()` draws one randint(2^32) per
+    batch when noise_std != 0.
 
-    With a non-zero appearance range (`blur_sigma`, `lowres`, `contrast`, `gamma`) a FIFTH state is seeded from `R` after those, so all the draws above are the same with
-    the appearance families on or off.  `draw_appearance()` draws per sample, for each family whose range is non-zero, in the order blur, low resolution, contrast, gamma:
-    first `random_sample() < appearance_prob`, then the value (sigma ~ U(S/2, S), f ~ U(F, 1), c ~ U(1 - C, 1 + C), gamma ~ U(1 - G, 1 + G)).  Both numbers are always
-    drawn, so the position in the stream does not depend on the outcome; a family that is not hit gets its neutral value (sigma = 0, f = 1, c = 1, gamma = 1).
+    field: `draw_field_seed()` draws one randint(2^32) per batch (the high half of the launch seed: the lattice differs from batch to batch, noise or no noise);
+    `draw_field()` draws per sample, in this order and only for the ranges that are non-zero: a ~ U(0, elastic_mag), beta ~ U(0, bias_field).
 
-    With a non-zero acquisition range (`thick_slices`, `ghost`, `spike`) a SIXTH state is seeded from `R` after those, so all the draws above are the same with the
-    acquisition families on or off.  `draw_acquisition(roi)` draws per sample, for each family whose range is non-zero, in the order thick slices, ghosting, spike, and
-    a family that is on always draws all its numbers:
+    appearance: `draw_appearance()` draws per sample, for each range that is non-zero, in the order blur, low resolution, contrast, gamma: first
+    `random_sample() < appearance_prob`, then the value (sigma ~ U(S/2, S), f ~ U(F, 1), c ~ U(1 - C, 1 + C), gamma ~ U(1 - G, 1 + G)).  Both numbers are always
+    drawn, so the position in the stream does not depend on the outcome; a range that is not hit gets its neutral value (sigma = 0, f = 1, c = 1, gamma = 1).
+
+    acquisition: `draw_acquisition(roi)` draws per sample, for each range that is non-zero, in the order thick slices, ghosting, spike, and always all its numbers:
       thick   random_sample() < acquisition_prob, f = randint(2, F + 1), o = randint(0, 12) % f
       ghost   random_sample() < acquisition_prob, alpha = uniform(0, A), axis = randint(0, 2), r = randint(0, 120); n = cands[r % len(cands)] with cands the members of
               GHOST_COUNTS that divide roi[axis]; no candidate, or alpha == 0 in fp32: neutral
@@ -196,30 +232,20 @@ class RandomTail:
               amp == 0 in fp32: neutral
     The result has the fields of `vsseg_acquisition_job`; NEUTRAL_ACQUISITION is the job that copies."""
 
-    def __init__(self, roi: Sequence[int], flip_prob: Optional[float] = 0.5, seed: Optional[int] = None, rotate_deg: float = 0.0, scale: float = 0.0,
-                 intensity_scale: float = 0.0, intensity_shift: float = 0.0, noise_std: float = 0.0, elastic_mag: float = 0.0, bias_field: float = 0.0, field_spacing: int = 64,
-                 blur_sigma: float = 0.0, lowres: float = 0.0, contrast: float = 0.0, gamma: float = 0.0, appearance_prob: float = 0.25,
-                 thick_slices: int = 0, ghost: float = 0.0, spike: float = 0.0, acquisition_prob: float = 0.25):
-        self.roi = tuple(int(r) for r in roi)
-        self.flip_prob = flip_prob
-        self.augment = check_augment(rotate_deg, scale, intensity_scale, intensity_shift, noise_std)
-        self.augmenting = any(v != 0.0 for v in self.augment.values())
-        self.field = check_field_augment(elastic_mag, bias_field, field_spacing)
-        self.fielding = self.field["elastic_mag"] != 0.0 or self.field["bias_field"] != 0.0
-        self.appearance = check_appearance_augment(blur_sigma, lowres, contrast, gamma, appearance_prob)
-        self.appearing = any(self.appearance[k] != 0.0 for k in APPEARANCE_KEYS[:4])
-        self.acquisition = check_acquisition_augment(thick_slices, ghost, spike, acquisition_prob)
-        self.acquiring = any(self.acquisition[k] != 0 for k in ACQUISITION_KEYS[:3])
+    def __init__(self, roi: Sequence[int], flip_prob: Optional[float] = 0.5, seed: Optional[int] = None, *ranges, **named):
+        self.roi, self.flip_prob = tuple(int(r) for r in roi), flip_prob
+        self.augmentation = Augmentation.of(*ranges, **named)
+        for fam in FAMILIES:
+            setattr(self, fam.name, self.augmentation.values[fam.name])
+            setattr(self, fam.flag, self.augmentation.on(fam))
         self.set_random_state(seed)
 
     def set_random_state(self, seed: Optional[int] = None):
         R = np.random.RandomState(seed)
-        self._flipR = np.random.RandomState(R.randint(MAX_SEED, dtype="uint32")) if self.flip_prob is not None else None
-        self._cropR = np.random.RandomState(R.randint(MAX_SEED, dtype="uint32"))
-        self._augR = np.random.RandomState(R.randint(MAX_SEED, dtype="uint32")) if self.augmenting else None
-        self._fieldR = np.random.RandomState(R.randint(MAX_SEED, dtype="uint32")) if self.fielding else None
-        self._appR = np.random.RandomState(R.randint(MAX_SEED, dtype="uint32")) if self.appearing else None
-        self._acqR = np.random.RandomState(R.randint(MAX_SEED, dtype="uint32")) if self.acquiring else None
+        state = lambda on: np.random.RandomState(R.randint(MAX_SEED, dtype="uint32")) if on else None  # noqa: E731
+        self._flipR, self._cropR = state(self.flip_prob is not None), state(True)
+        for fam in FAMILIES:
+            setattr(self, fam.rng, state(getattr(self, fam.flag)))
         return self
 
     def draw(self, shape: Sequence[int]) -> Tuple[bool, Tuple[int, int, int]]:
@@ -310,7 +336,8 @@ class PatchSampler:
 
     `sample(indices)` → (inputs [B,1,*roi], labels [B,1,*roi]) fp32 on the device, the tensors the reference's DataLoader
     yields as batch["image"], batch["label"] (ref:params/VSparams.py:455).  `flip_prob=None` = the validation chain
-    (no RandFlipd, ref:params/VSparams.py:224-236).
+    (no RandFlipd, ref:params/VSparams.py:224-236).  `*ranges, **named` are RandomTail's; the tail gets the one validated record.  Draws within a batch: noise seed,
+    field seed, then per sample flip / crop, augment, field; after the crop launch the acquisition draws per sample, then the appearance draws per sample.
 
     A non-zero `rotate_deg`, `scale`, `intensity_scale`, `intensity_shift` or `noise_std` (see RandomTail) replaces that launch by one
     `vsseg_crop_affine` launch: the image is resampled trilinearly and gets gain, bias and noise, the label goes through the same matrix
@@ -333,13 +360,9 @@ class PatchSampler:
     The scratch of the launch belongs to the sampler; nothing reads device memory or synchronises.  With the three ranges 0, or `acquisition_prob` 0, the sampler takes
     the paths above, launch for launch."""
 
-    def __init__(self, cases: List[Dict], roi: Sequence[int], flip_prob: Optional[float] = 0.5, seed: Optional[int] = 0, rotate_deg: float = 0.0, scale: float = 0.0,
-                 intensity_scale: float = 0.0, intensity_shift: float = 0.0, noise_std: float = 0.0, elastic_mag: float = 0.0, bias_field: float = 0.0, field_spacing: int = 64,
-                 blur_sigma: float = 0.0, lowres: float = 0.0, contrast: float = 0.0, gamma: float = 0.0, appearance_prob: float = 0.25,
-                 thick_slices: int = 0, ghost: float = 0.0, spike: float = 0.0, acquisition_prob: float = 0.25):
+    def __init__(self, cases: List[Dict], roi: Sequence[int], flip_prob: Optional[float] = 0.5, seed: Optional[int] = 0, *ranges, **named):
         self.cases, self.roi = cases, tuple(int(r) for r in roi)
-        self.tail = RandomTail(self.roi, flip_prob, seed, rotate_deg, scale, intensity_scale, intensity_shift, noise_std, elastic_mag, bias_field, field_spacing,
-                               blur_sigma, lowres, contrast, gamma, appearance_prob, thick_slices, ghost, spike, acquisition_prob)
+        self.tail = RandomTail(self.roi, flip_prob, seed, Augmentation.of(*ranges, **named))
         self.appearing = self.tail.appearing and self.tail.appearance["appearance_prob"] > 0.0
         self.acquiring = self.tail.acquiring and self.tail.acquisition["acquisition_prob"] > 0.0
         self.acquisition_launches = 0
@@ -353,6 +376,17 @@ class PatchSampler:
 
     def __len__(self):
         return len(self.cases)
+
+    @staticmethod
+    def _stage(jobs, dev) -> torch.Tensor:  # the bytes of a ctypes job table on the device; the caller issues `record_stream` on them after the launch that reads them
+        return torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(dev)
+
+    def _scratch(self, attr: str, shape: Tuple[int, ...], dtype: torch.dtype, dev) -> torch.Tensor:  # the sampler's buffer `attr`: that of the largest batch so far on this device
+        t = getattr(self, attr)
+        if t is None or t.shape[0] < shape[0] or t.device != dev:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+            setattr(self, attr, t)
+        return t
 
     def sample(self, indices: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:
         img, lab = self._sample_affine(indices) if self.tail.augmenting or self.tail.fielding else self._sample_crop(indices)
@@ -377,11 +411,10 @@ class PatchSampler:
             any_on, staged = any_on or later or j.thick != 1, staged or (later and j.thick != 1)
         if not any_on:
             return img
-        if staged and (self._acquisition_scratch is None or self._acquisition_scratch.shape[0] < B or self._acquisition_scratch.device != dev):
-            self._acquisition_scratch = torch.empty((B, *self.roi), dtype=torch.float32, device=dev)
-        jbuf = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(dev)
+        scratch = self._scratch("_acquisition_scratch", (B, *self.roi), torch.float32, dev).data_ptr() if staged else None
+        jbuf = self._stage(jobs, dev)
         out = torch.empty_like(img)
-        L.check(self.lib.vsseg_patch_acquisition(jobs, jbuf.data_ptr(), B, img.data_ptr(), out.data_ptr(), self._acquisition_scratch.data_ptr() if staged else None, L.i3(self.roi), stream.cuda_stream), "patch_acquisition")
+        L.check(self.lib.vsseg_patch_acquisition(jobs, jbuf.data_ptr(), B, img.data_ptr(), out.data_ptr(), scratch, L.i3(self.roi), stream.cuda_stream), "patch_acquisition")
         jbuf.record_stream(stream)
         self.acquisition_launches += 1
         return out
@@ -403,20 +436,18 @@ class PatchSampler:
             filtering, both = filtering or low or len(taps) > 0, both or (low and len(taps) > 0)
             toning = toning or tjobs[b].contrast != 1.0 or tjobs[b].gamma != 1.0
         if filtering:
-            if both and (self._filter_scratch is None or self._filter_scratch.shape[0] < B or self._filter_scratch.device != dev):
-                self._filter_scratch = torch.empty((B, *self.roi), dtype=torch.float32, device=dev)
-            jbuf = torch.frombuffer(bytearray(bytes(fjobs)), dtype=torch.uint8).to(dev)
+            scratch = self._scratch("_filter_scratch", (B, *self.roi), torch.float32, dev).data_ptr() if both else None
+            jbuf = self._stage(fjobs, dev)
             out = torch.empty_like(img)
-            L.check(self.lib.vsseg_patch_filter(fjobs, jbuf.data_ptr(), B, img.data_ptr(), out.data_ptr(), self._filter_scratch.data_ptr() if both else None, L.i3(self.roi), stream.cuda_stream), "patch_filter")
+            L.check(self.lib.vsseg_patch_filter(fjobs, jbuf.data_ptr(), B, img.data_ptr(), out.data_ptr(), scratch, L.i3(self.roi), stream.cuda_stream), "patch_filter")
             jbuf.record_stream(stream)
             img = out
         self.last_tone_stats = None
         if toning:
-            if self._tone_work is None or self._tone_work.shape[0] < B or self._tone_work.device != dev:
-                self._tone_work = torch.empty((B, L.TONE_SHARDS, 3), dtype=torch.float64, device=dev)
-            jbuf = torch.frombuffer(bytearray(bytes(tjobs)), dtype=torch.uint8).to(dev)
+            work = self._scratch("_tone_work", (B, L.TONE_SHARDS, 3), torch.float64, dev)
+            jbuf = self._stage(tjobs, dev)
             self.last_tone_stats = torch.empty((B, 4), dtype=torch.float32, device=dev)
-            L.check(self.lib.vsseg_patch_tone(tjobs, jbuf.data_ptr(), B, img.data_ptr(), img[0].numel(), self.last_tone_stats.data_ptr(), self._tone_work.data_ptr(), stream.cuda_stream), "patch_tone")
+            L.check(self.lib.vsseg_patch_tone(tjobs, jbuf.data_ptr(), B, img.data_ptr(), img[0].numel(), self.last_tone_stats.data_ptr(), work.data_ptr(), stream.cuda_stream), "patch_tone")
             jbuf.record_stream(stream)
         return img
 
@@ -433,7 +464,7 @@ class PatchSampler:
             for k, key in enumerate(("image", "label")):
                 j = jobs[b + k * B]  # dst = [image_0..image_{B-1} | label_0..label_{B-1}]
                 j.src, j.sdims, j.origin, j.flip_x = case[key].data_ptr(), L.i3(shape), L.i3(start), int(flip)
-        jbuf = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(dev)
+        jbuf = self._stage(jobs, dev)
         out = torch.empty((2, B, 1, *self.roi), dtype=torch.float32, device=dev)
         L.check(self.lib.vsseg_crop_flip(jbuf.data_ptr(), 2 * B, out.data_ptr(), L.i3(self.roi), torch.cuda.current_stream().cuda_stream), "crop_flip")
         jbuf.record_stream(torch.cuda.current_stream())
@@ -468,7 +499,7 @@ class PatchSampler:
                     j.interp, j.gain, j.bias, j.noise_std = L.INTERP_NEAREST, 1.0, 0.0, 0.0
                 if fielding:  # the label follows the deformation and knows no bias field
                     j.elastic_mag, j.bias_log = float(aug["elastic_mag"]), float(aug["bias_log"]) if key == "image" else 0.0
-        jbuf = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(dev)
+        jbuf = self._stage(jobs, dev)
         out = torch.empty((2, B, 1, *self.roi), dtype=torch.float32, device=dev)
         stream = torch.cuda.current_stream().cuda_stream
         if fielding:

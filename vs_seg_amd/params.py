@@ -35,7 +35,7 @@ from . import parallel as DP
 from . import report as R
 from .report import postprocessing_csv_header  # noqa: F401  (part of this module's interface)
 from .data import nifti
-from .data.transforms import ACQUISITION_KEYS, APPEARANCE_KEYS, AUGMENT_KEYS, FIELD_KEYS, PatchSampler, check_acquisition_augment, check_appearance_augment, check_augment, check_field_augment, epoch_batches, load_case
+from .data.transforms import DEFAULTS, FAMILIES, Augmentation, PatchSampler, epoch_batches, load_case
 
 HP = dict(
     channels=(16, 32, 48, 64, 80, 96),
@@ -85,6 +85,46 @@ def _largest_step(p, outputs, spacing):
 POST_STEPS = dict(fill_holes=_fill_step, closing=_closing_step, opening=_opening_step, min_component=_small_step, keep_largest=_largest_step)
 
 
+# the --aug_<argument> flags: argument -> (type, metavar, help).  Their order, their defaults and the family each belongs to are those of data.transforms.FAMILIES
+AUG_FLAGS = dict(
+    rotate_deg=(float, "DEG", "training augmentation: rotate every training patch about the z axis by an angle drawn from [-DEG, DEG] (0: off)"),
+    scale=(float, "FRAC", "training augmentation: zoom every training patch in-plane by a factor drawn from [1 - FRAC, 1 + FRAC] (0: off)"),
+    intensity_scale=(float, "FRAC", "training augmentation: multiply the image of every training patch by a gain drawn from [1 - FRAC, 1 + FRAC] (0: off)"),
+    intensity_shift=(float, "STD", "training augmentation: add a bias drawn from [-STD, STD] to the image of every training patch, in standard deviations of the normalised image (0: off)"),
+    noise_std=(float, "STD", "training augmentation: add Gaussian noise of this standard deviation to the image of every training patch (0: off)"),
+    elastic_mag=(float, "VOX", "training augmentation: deform every training patch in-plane by a smooth random B-spline field whose control points move by at most a length drawn from [0, VOX] voxels; the peak displacement of the field is typically about half of it; at most aug_field_spacing / 4 (0: off)"),
+    bias_field=(float, "LOG", "training augmentation: multiply the image of every training patch by exp of a smooth random B-spline field whose amplitude is drawn from [0, LOG] (the MR bias field; 0: off)"),
+    field_spacing=(int, "VOX", "in-plane control-point spacing of the two B-spline fields in voxels (64: about 26 mm; along z a quarter of it)"),
+    blur_sigma=(float, "VOX", "training augmentation: blur the image of a training patch in-plane with a Gaussian whose sigma is drawn from [VOX / 2, VOX] in-plane voxels; at most 1.5 (0: off)"),
+    lowres=(float, "FRAC", "training augmentation: simulate a low-resolution acquisition of the image of a training patch: sample it in-plane at a resolution factor drawn from [FRAC, 1] and interpolate back; in [0.25, 1) (0: off)"),
+    contrast=(float, "FRAC", "training augmentation: scale the image of a training patch about its mean by a factor drawn from [1 - FRAC, 1 + FRAC], clipped to the range it had (0: off)"),
+    gamma=(float, "FRAC", "training augmentation: apply a gamma curve over the value range of the image of a training patch, with an exponent drawn from [1 - FRAC, 1 + FRAC] (0: off)"),
+    appearance_prob=(float, "P", "probability with which each of the blur, low-resolution, contrast and gamma augmentations is applied to a training sample, independently of the others"),
+    thick_slices=(float, "F", "training augmentation: simulate a thick-slice acquisition of the image of a training patch: average slabs of 2 to F voxels along z (drawn per sample, at a random offset) and interpolate linearly back between the slab centres; an integer in 2..4 (0: off)"),
+    ghost=(float, "A", "training augmentation: add phase-encode ghosts to the image of a training patch: 2 to 8 shifted copies along x or y, as left by attenuating every n-th k-space line by a factor drawn from [0, A]; in [0, 1] (0: off)"),
+    spike=(float, "S", "training augmentation: add a k-space spike to the image of a training patch: a plane wave in-plane at a random frequency and phase with an amplitude drawn from [0, S], in standard deviations of the normalised image (the herringbone artefact; 0: off)"),
+    acquisition_prob=(float, "P", "probability with which each of the thick-slice, ghosting and spike augmentations is applied to a training sample, independently of the others"),
+)
+
+# the augmentation steps of the training chain description: (the arguments of which a non-zero one switches the step on, its text over all arguments), in the order the
+# launches apply them: the deformation acts in patch space, the matrix after it; the bias field multiplies the interpolated value before the gain
+AUG_CHAIN = (
+    (("elastic_mag",), "RandElastic(aug_elastic_mag={elastic_mag}, aug_field_spacing={field_spacing}, in-plane, cubic B-spline)"),
+    (("rotate_deg", "scale"), "RandAffine(aug_rotate_deg={rotate_deg}, aug_scale={scale}, axis=z, about the crop centre)"),
+    (("bias_field",), "RandBiasField(aug_bias_field={bias_field}, aug_field_spacing={field_spacing})"),
+    (("intensity_scale",), "RandScaleIntensity(aug_intensity_scale={intensity_scale})"),
+    (("intensity_shift",), "RandShiftIntensity(aug_intensity_shift={intensity_shift})"),
+    (("noise_std",), "RandGaussianNoise(aug_noise_std={noise_std})"),
+    (("thick_slices",), "RandThickSlices(aug_thick_slices={thick_slices}, along z, p={acquisition_prob})"),
+    (("ghost",), "RandGhosting(aug_ghost={ghost}, in-plane, p={acquisition_prob})"),
+    (("spike",), "RandSpike(aug_spike={spike}, in-plane, p={acquisition_prob})"),
+    (("blur_sigma",), "RandGaussianBlur(aug_blur_sigma={blur_sigma}, in-plane, p={appearance_prob})"),
+    (("lowres",), "RandLowResolution(aug_lowres={lowres}, in-plane, p={appearance_prob})"),
+    (("contrast",), "RandContrast(aug_contrast={contrast}, preserve_range, p={appearance_prob})"),
+    (("gamma",), "RandGamma(aug_gamma={gamma}, p={appearance_prob})"),
+)
+
+
 class CachedLoader:
     """Iterable over GPU-cached cases with the random tail of the transform chain applied per epoch.
 
@@ -92,16 +132,18 @@ class CachedLoader:
     meta dicts of the cases for batch_size 1 loaders).  `len()` = number of cases, `batch_size` as in torch's DataLoader —
     the reference's first-epoch log line divides one by the other (ref:params/VSparams.py:466)."""
 
-    def __init__(self, cases: List[Dict], roi: Optional[Sequence[int]], batch_size: int, shuffle: bool, flip_prob: Optional[float], seed: int = 0, pad: Optional[bool] = None,
-                 augment: Optional[Dict[str, float]] = None, field_augment: Optional[Dict[str, float]] = None, appearance_augment: Optional[Dict[str, float]] = None,
-                 acquisition_augment: Optional[Dict[str, float]] = None):
+    def __init__(self, cases: List[Dict], roi: Optional[Sequence[int]], batch_size: int, shuffle: bool, flip_prob: Optional[float], seed: int = 0, pad: Optional[bool] = None, **families):
+        # families: the arguments of the augmentation families as dicts under the keys of a transform description (augment, field_augment, ...; None or absent: off)
+        augmentation = Augmentation.of(**{k: v for fam in FAMILIES for k, v in (families.pop(fam.key, None) or {}).items()})
+        if families:
+            raise TypeError(f"CachedLoader got an unexpected keyword argument '{next(iter(families))}'")
         self.cases, self.batch_size, self.shuffle = cases, batch_size, shuffle
         # equal step counts on every rank (wrap-around padding) only where every step issues a collective: the shuffled training loader.
         # Validation / test loaders give rank r exactly shard_indices(n, r, world) — a padded case would be counted twice in their sums
         self.pad = shuffle if pad is None else pad
         self.rank, self.world = DP.get_rank(), DP.world_size()
         # every rank shuffles with the SAME stream (the shards must partition one permutation) but draws its own flips / crops
-        self.sampler = PatchSampler(cases, roi, flip_prob, seed + 7919 * self.rank, **(augment or {}), **(field_augment or {}), **(appearance_augment or {}), **(acquisition_augment or {})) if roi is not None else None
+        self.sampler = PatchSampler(cases, roi, flip_prob, seed + 7919 * self.rank, augmentation) if roi is not None else None
         self._order = np.random.RandomState(seed)
 
     def __len__(self):
@@ -149,23 +191,9 @@ class VSparams:
         parser.add_argument("--min_component_mm3", type=float, default=0.0, metavar="V", help="run_inference drops every connected component of a predicted segmentation that is smaller than V cubic millimetres (ceil(V / voxel volume) voxels per case; on the GPU, at --component_connectivity) and adds small_components,small_voxels to figures/test_postprocessing.csv (MONAI's RemoveSmallObjects; 0: off)")
         parser.add_argument("--tta_flips", type=int, nargs="*", choices=[0, 1, 2], default=None, metavar="AXIS", help="run_inference predicts every case on mirrored copies as well (spatial axes 0 1 2 = X Y Z: one pass per subset of the given axes) and averages the un-mirrored predictions; training mirrors axis 0")
         parser.add_argument("--tta_average", type=str, default="logits", choices=["logits", "probabilities"], help="what --tta_flips averages: the blended logits, or their softmax over the classes (nnU-Net)")
-        parser.add_argument("--aug_rotate_deg", type=float, default=0.0, metavar="DEG", help="training augmentation: rotate every training patch about the z axis by an angle drawn from [-DEG, DEG] (0: off)")
-        parser.add_argument("--aug_scale", type=float, default=0.0, metavar="FRAC", help="training augmentation: zoom every training patch in-plane by a factor drawn from [1 - FRAC, 1 + FRAC] (0: off)")
-        parser.add_argument("--aug_intensity_scale", type=float, default=0.0, metavar="FRAC", help="training augmentation: multiply the image of every training patch by a gain drawn from [1 - FRAC, 1 + FRAC] (0: off)")
-        parser.add_argument("--aug_intensity_shift", type=float, default=0.0, metavar="STD", help="training augmentation: add a bias drawn from [-STD, STD] to the image of every training patch, in standard deviations of the normalised image (0: off)")
-        parser.add_argument("--aug_noise_std", type=float, default=0.0, metavar="STD", help="training augmentation: add Gaussian noise of this standard deviation to the image of every training patch (0: off)")
-        parser.add_argument("--aug_elastic_mag", type=float, default=0.0, metavar="VOX", help="training augmentation: deform every training patch in-plane by a smooth random B-spline field whose control points move by at most a length drawn from [0, VOX] voxels; the peak displacement of the field is typically about half of it; at most aug_field_spacing / 4 (0: off)")
-        parser.add_argument("--aug_bias_field", type=float, default=0.0, metavar="LOG", help="training augmentation: multiply the image of every training patch by exp of a smooth random B-spline field whose amplitude is drawn from [0, LOG] (the MR bias field; 0: off)")
-        parser.add_argument("--aug_field_spacing", type=int, default=64, metavar="VOX", help="in-plane control-point spacing of the two B-spline fields in voxels (64: about 26 mm; along z a quarter of it)")
-        parser.add_argument("--aug_blur_sigma", type=float, default=0.0, metavar="VOX", help="training augmentation: blur the image of a training patch in-plane with a Gaussian whose sigma is drawn from [VOX / 2, VOX] in-plane voxels; at most 1.5 (0: off)")
-        parser.add_argument("--aug_lowres", type=float, default=0.0, metavar="FRAC", help="training augmentation: simulate a low-resolution acquisition of the image of a training patch: sample it in-plane at a resolution factor drawn from [FRAC, 1] and interpolate back; in [0.25, 1) (0: off)")
-        parser.add_argument("--aug_contrast", type=float, default=0.0, metavar="FRAC", help="training augmentation: scale the image of a training patch about its mean by a factor drawn from [1 - FRAC, 1 + FRAC], clipped to the range it had (0: off)")
-        parser.add_argument("--aug_gamma", type=float, default=0.0, metavar="FRAC", help="training augmentation: apply a gamma curve over the value range of the image of a training patch, with an exponent drawn from [1 - FRAC, 1 + FRAC] (0: off)")
-        parser.add_argument("--aug_appearance_prob", type=float, default=0.25, metavar="P", help="probability with which each of the blur, low-resolution, contrast and gamma augmentations is applied to a training sample, independently of the others")
-        parser.add_argument("--aug_thick_slices", type=float, default=0, metavar="F", help="training augmentation: simulate a thick-slice acquisition of the image of a training patch: average slabs of 2 to F voxels along z (drawn per sample, at a random offset) and interpolate linearly back between the slab centres; an integer in 2..4 (0: off)")
-        parser.add_argument("--aug_ghost", type=float, default=0.0, metavar="A", help="training augmentation: add phase-encode ghosts to the image of a training patch: 2 to 8 shifted copies along x or y, as left by attenuating every n-th k-space line by a factor drawn from [0, A]; in [0, 1] (0: off)")
-        parser.add_argument("--aug_spike", type=float, default=0.0, metavar="S", help="training augmentation: add a k-space spike to the image of a training patch: a plane wave in-plane at a random frequency and phase with an amplitude drawn from [0, S], in standard deviations of the normalised image (the herringbone artefact; 0: off)")
-        parser.add_argument("--aug_acquisition_prob", type=float, default=0.25, metavar="P", help="probability with which each of the thick-slice, ghosting and spike augmentations is applied to a training sample, independently of the others")
+        for k, default in DEFAULTS.items():
+            kind, metavar, text = AUG_FLAGS[k]
+            parser.add_argument("--aug_" + k, type=kind, default=default, metavar=metavar, help=text)
         parser.add_argument("--ce_weight", type=float, default=0.0, metavar="LAMBDA", help="training loss: add LAMBDA times the voxel-wise cross-entropy of the final logits to the Dice loss (the Dice + CE loss of nnU-Net, MONAI's DiceCELoss; 0: off, the reference's loss)")
         parser.add_argument("--ce_foreground_weight", type=float, default=1.0, metavar="W", help="class weight of the foreground voxels in the cross-entropy term, the background's being 1 (needs --ce_weight > 0)")
         parser.add_argument("--ce_topk", type=float, default=0.0, metavar="PCT", help="training loss: average the cross-entropy term over the hardest PCT percent of the voxels of the batch only, selected on the GPU, and divide by their number K, not by the class-weight sum (the Dice + TopK loss of nnU-Net, DC_and_topk_loss: --ce_weight 1 --ce_topk 10; in (0, 100], needs --ce_weight > 0; 0: off, the mean over every voxel)")
@@ -187,10 +215,7 @@ class VSparams:
             ce_weight, ce_foreground_weight = check_ce(args.ce_weight, args.ce_foreground_weight)
             ce_topk = check_ce_topk(args.ce_topk, ce_weight)
             region, ce_focal_gamma = check_region(args.tversky_beta, args.focal_tversky_gamma, args.batch_dice, args.ce_focal_gamma, ce_weight, ce_topk)
-            augment = check_augment(*(getattr(args, "aug_" + k) for k in AUGMENT_KEYS))
-            field = check_field_augment(args.aug_elastic_mag, args.aug_bias_field, args.aug_field_spacing)
-            appearance = check_appearance_augment(*(getattr(args, "aug_" + k) for k in APPEARANCE_KEYS))
-            acquisition = check_acquisition_augment(*(getattr(args, "aug_" + k) for k in ACQUISITION_KEYS))
+            augmentation = Augmentation.of(**{k: getattr(args, "aug_" + k) for k in AUG_FLAGS})
             min_component_voxels(args.min_component_mm3, (1.0, 1.0, 1.0))  # a finite value >= 0
             check_radius_mm(args.closing_mm, what="--closing_mm")  # (the reach depends on the spacing of the case: checked per case)
             check_radius_mm(args.opening_mm, what="--opening_mm")
@@ -225,10 +250,8 @@ class VSparams:
         self.fill_holes, self.hole_connectivity, self.min_component_mm3 = args.fill_holes, args.hole_connectivity, float(args.min_component_mm3)
         self.closing_mm, self.opening_mm = float(args.closing_mm), float(args.opening_mm)
         self.tta_flips, self.tta_average = tuple(args.tta_flips or ()), args.tta_average
-        self.aug_rotate_deg, self.aug_scale, self.aug_intensity_scale, self.aug_intensity_shift, self.aug_noise_std = (augment[k] for k in AUGMENT_KEYS)
-        self.aug_elastic_mag, self.aug_bias_field, self.aug_field_spacing = (field[k] for k in FIELD_KEYS)
-        self.aug_blur_sigma, self.aug_lowres, self.aug_contrast, self.aug_gamma, self.aug_appearance_prob = (appearance[k] for k in APPEARANCE_KEYS)
-        self.aug_thick_slices, self.aug_ghost, self.aug_spike, self.aug_acquisition_prob = (acquisition[k] for k in ACQUISITION_KEYS)
+        for k, v in augmentation.flat().items():  # aug_rotate_deg ... aug_acquisition_prob, as validated
+            setattr(self, "aug_" + k, v)
         self.ce_weight, self.ce_foreground_weight, self.ce_topk = ce_weight, ce_foreground_weight, ce_topk
         self.tversky_beta, self.focal_tversky_gamma, self.batch_dice = region if region is not None else (None, 1.0, False)  # (None: the reference's Dice ratio per sample)
         self.ce_focal_gamma = ce_focal_gamma
@@ -277,10 +300,7 @@ class VSparams:
             (("keep_largest_component",), self.keep_largest_component),
             (("component_connectivity",), self.keep_largest_component or self.min_component_mm3 > 0),
             (("tta_flips", "tta_average"), self.tta_flips),
-            (tuple("aug_" + k for k in AUGMENT_KEYS), any(self.augment.values())),
-            (("aug_elastic_mag", "aug_bias_field", "aug_field_spacing"), self.aug_elastic_mag or self.aug_bias_field),
-            (tuple("aug_" + k for k in APPEARANCE_KEYS), self._appearance_on),
-            (tuple("aug_" + k for k in ACQUISITION_KEYS), self._acquisition_on),
+            *((tuple("aug_" + k for k in fam.defaults), any(getattr(self, "aug_" + k) for k in fam.ranges)) for fam in FAMILIES),  # a family is logged when one of its ranges is non-zero
             (("ce_weight", "ce_foreground_weight"), self.ce_weight > 0),
             (("ce_topk",), self.ce_topk > 0),
             (("tversky_beta", "focal_tversky_gamma", "batch_dice"), self.tversky_beta is not None),
@@ -312,56 +332,15 @@ class VSparams:
         self.logger.info("Number of images in test set       = {}".format(len(sets["test"])))
         return sets["training"], sets["validation"], sets["test"]
 
-    @property
-    def augment(self) -> Dict[str, float]:
-        """The training augmentation ranges under PatchSampler's argument names (all 0: off)."""
-        return {k: getattr(self, "aug_" + k) for k in AUGMENT_KEYS}
-
-    @property
-    def field_augment(self) -> Dict[str, float]:
-        """The two B-spline field ranges and their spacing under PatchSampler's argument names (both ranges 0: off)."""
-        return dict(elastic_mag=self.aug_elastic_mag, bias_field=self.aug_bias_field, field_spacing=self.aug_field_spacing)
-
-    @property
-    def appearance_augment(self) -> Dict[str, float]:
-        """The four appearance ranges and their probability under PatchSampler's argument names (all four ranges 0: off)."""
-        return {k: getattr(self, "aug_" + k) for k in APPEARANCE_KEYS}
-
-    @property
-    def _appearance_on(self) -> bool:
-        return any(getattr(self, "aug_" + k) for k in APPEARANCE_KEYS[:4])
-
-    @property
-    def acquisition_augment(self) -> Dict[str, float]:
-        """The three acquisition ranges and their probability under PatchSampler's argument names (all three ranges 0: off)."""
-        return {k: getattr(self, "aug_" + k) for k in ACQUISITION_KEYS}
-
-    @property
-    def _acquisition_on(self) -> bool:
-        return any(getattr(self, "aug_" + k) for k in ACQUISITION_KEYS[:3])
-
     def get_transforms(self):
         """The three chains as plain descriptions; `cache_transformed_*_data` executes them (deterministic head cached in
-        HBM, random tail per batch).  The augmentation flags reach the training chain only: the five ranges under "augment", the field ranges under "field_augment",
-        the appearance ranges under "appearance_augment", the acquisition ranges under "acquisition_augment"."""
+        HBM, random tail per batch).  The augmentation flags reach the training chain only: the arguments of every family of FAMILIES as a dict under its key
+        (`augment`, `field_augment`, `appearance_augment`, `acquisition_augment`; these dicts are also properties of that name, defined below the class)."""
         head = ["LoadNifti", "AddChannel", "Orientation(RAS)", "NormalizeIntensity(image)"]
-        a, f, ap, aq = self.augment, self.field_augment, self.appearance_augment, self.acquisition_augment
-        p, pq = f"p={ap['appearance_prob']}", f"p={aq['acquisition_prob']}"
-        # in the order the launch applies them: the deformation acts in patch space, the matrix after it; the bias field multiplies the interpolated value before the gain
-        aug = ([f"RandElastic(aug_elastic_mag={f['elastic_mag']}, aug_field_spacing={f['field_spacing']}, in-plane, cubic B-spline)"] if f["elastic_mag"] else []) + (
-            [f"RandAffine(aug_rotate_deg={a['rotate_deg']}, aug_scale={a['scale']}, axis=z, about the crop centre)"] if a["rotate_deg"] or a["scale"] else []) + (
-            [f"RandBiasField(aug_bias_field={f['bias_field']}, aug_field_spacing={f['field_spacing']})"] if f["bias_field"] else []) + (
-            [f"RandScaleIntensity(aug_intensity_scale={a['intensity_scale']})"] if a["intensity_scale"] else []) + (
-            [f"RandShiftIntensity(aug_intensity_shift={a['intensity_shift']})"] if a["intensity_shift"] else []) + (
-            [f"RandGaussianNoise(aug_noise_std={a['noise_std']})"] if a["noise_std"] else []) + (
-            [f"RandThickSlices(aug_thick_slices={aq['thick_slices']}, along z, {pq})"] if aq["thick_slices"] else []) + (
-            [f"RandGhosting(aug_ghost={aq['ghost']}, in-plane, {pq})"] if aq["ghost"] else []) + (
-            [f"RandSpike(aug_spike={aq['spike']}, in-plane, {pq})"] if aq["spike"] else []) + (
-            [f"RandGaussianBlur(aug_blur_sigma={ap['blur_sigma']}, in-plane, {p})"] if ap["blur_sigma"] else []) + (
-            [f"RandLowResolution(aug_lowres={ap['lowres']}, in-plane, {p})"] if ap["lowres"] else []) + (
-            [f"RandContrast(aug_contrast={ap['contrast']}, preserve_range, {p})"] if ap["contrast"] else []) + (
-            [f"RandGamma(aug_gamma={ap['gamma']}, {p})"] if ap["gamma"] else [])
-        train = dict(chain=head + [f"SpatialPad({self.pad_crop_shape})", "RandFlip(p=0.5, axis=0)", f"RandSpatialCrop({self.pad_crop_shape})"] + aug, pad=self.pad_crop_shape, roi=self.pad_crop_shape, flip_prob=0.5, augment=a, field_augment=f, appearance_augment=ap, acquisition_augment=aq)
+        families = {fam.key: getattr(self, fam.key) for fam in FAMILIES}
+        flat = {k: v for d in families.values() for k, v in d.items()}
+        aug = [text.format(**flat) for keys, text in AUG_CHAIN if any(flat[k] for k in keys)]
+        train = dict(chain=head + [f"SpatialPad({self.pad_crop_shape})", "RandFlip(p=0.5, axis=0)", f"RandSpatialCrop({self.pad_crop_shape})"] + aug, pad=self.pad_crop_shape, roi=self.pad_crop_shape, flip_prob=0.5, **families)
         val = dict(chain=head + [f"SpatialPad({self.pad_crop_shape})", f"RandSpatialCrop({self.pad_crop_shape})"], pad=self.pad_crop_shape, roi=self.pad_crop_shape, flip_prob=None)
         test = dict(chain=head, pad=None, roi=None, flip_prob=None)
         return train, val, test
@@ -399,7 +378,7 @@ class VSparams:
     def _cache(self, files, tf, batch_size, shuffle, what):
         self.logger.info(f"Caching {what} data set...")
         cases = [load_case(fd, tf["pad"], self.device) for fd in files]
-        return CachedLoader(cases, tf["roi"], batch_size, shuffle, tf["flip_prob"], seed=0, augment=tf.get("augment"), field_augment=tf.get("field_augment"), appearance_augment=tf.get("appearance_augment"), acquisition_augment=tf.get("acquisition_augment"))  # the crop/flip stream is decorrelated per rank inside CachedLoader
+        return CachedLoader(cases, tf["roi"], batch_size, shuffle, tf["flip_prob"], seed=0, **{fam.key: tf.get(fam.key) for fam in FAMILIES})  # the crop/flip stream is decorrelated per rank inside CachedLoader
 
     def cache_transformed_train_data(self, train_files, train_transforms):
         return self._cache(train_files, train_transforms, self.train_batch_size, True, "training")
@@ -613,3 +592,8 @@ class VSparams:
         nifti.write_nifti(path, seg, label_meta["original_affine"], dtype=np.uint8)
         self.logger.info(f"export to nifti... {path}")
         return path
+
+
+for _fam in FAMILIES:  # VSparams.augment, .field_augment, .appearance_augment, .acquisition_augment
+    setattr(VSparams, _fam.key, property(lambda self, fam=_fam: {k: getattr(self, "aug_" + k) for k in fam.defaults}))  # under PatchSampler's argument names (every range 0: off)
+
